@@ -2,6 +2,7 @@
 """Headline benchmark: Gram entries/s of the signature-PDE-kernel hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c4mini|c5] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,10 +20,15 @@ split over the ranks, every rank solves its block with no data-path collective, 
 full matrix on every rank.  --scaling weak (default for gram configs): X has N x rows_per_gpu rows; --scaling strong
 (default and only choice for c4, the config BASELINE names for 8 GPUs): the batch is fixed and divided.
 
-With N > 1 (or --force-dist) the line's `configs` holds BASELINE configs[3] (the config BASELINE.json names for 8 GPUs) and configs[4]
-STRONG-scaled under the same process group (dist_configs); at N = 1 without it, `configs` holds c2, two training-sized MMD steps, c5, c4.
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, the outputs of the last step
+(--dump-outputs DIR: DIR/<name>.npy, see dump_outputs) and rank 0's JSON line with the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step) and the config.  Everything else is measured only with --full:
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+With N > 1 (or --force-dist) the line's `configs` holds BASELINE configs[3] (the config BASELINE.json names for 8 GPUs) and configs[4]
+STRONG-scaled under the same process group (dist_configs), beside the other scaling of the headline config and the per-step time in the
+collectives; at N = 1 without it, `configs` holds c2, two training-sized MMD steps, c5, c4.
+
+With --full, rank 0's JSON line also carries
   roofline     : the kernel that dominates the step against the ceiling that binds it (fp64 vector issue for the fused
                  kernels, with the HBM-equivalent rate of the increments they never materialise as a second figure;
                  HBM for the streaming solver), from HIP-event timings of its launches on the launch stream
@@ -414,6 +420,28 @@ def timed(step, steps, warmup, dist, dev):
     return elapsed, out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, wl, out):
+    """--dump-outputs DIR: what the timed step returned in its last step, as DIR/<name>.npy -- float64 for fp64 configs, float32 for
+    fp32 I/O: gram configs `gram` (the full matrix, A x B); mmd configs `mmd` (the scalar) and `grad` (d mmd / d X, A x M x D).  The
+    inputs are seeded, so two builds run with the same arguments compare output for output.  An array beyond its share of the 64 MB
+    budget (none of CONFIGS is, at up to 8 GPUs) is written as a fixed sample: its flat entries at seeded indices, which go to
+    DIR/<name>_index.npy."""
+    arrays = {"gram": out} if wl.mode == "gram" else {"mmd": out[0], "grad": out[1]}
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // (a.itemsize + 8), replace=False)).astype(np.int64)
+            np.save(os.path.join(outdir, name + "_index.npy"), idx)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -421,6 +449,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)     # (the first launches of a process run at lower clocks)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, the legs below: roofline / adjoint / parity / cpu_baseline, the other configs (N = 1); "
+                         "the other scaling, collective times and configs[3], [4] under the process group (N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the roofline / adjoint / parity / cpu_baseline legs")
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the round's committed PMC pass instead of a rocprofv3 child run")
@@ -430,6 +463,8 @@ def main():
                     help="initialise torch.distributed (RCCL) even with one rank: exercises the N>1 code path on a 1-GPU box")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous only (no kernels): checks the launch path")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))       # plain `python bench.py --gpus N`: spawn the N ranks ourselves
@@ -462,6 +497,8 @@ def main():
     assert isinstance(be, _lib.HipBackend), "bench must run on the HIP back-end"
 
     elapsed, out = timed(wl.step, args.steps, args.warmup, dist, dev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl, out)
     value = wl.entries_per_step * args.steps / elapsed
     dname = "f64" if wl.dtype == torch.float64 else "f32"
 
@@ -484,7 +521,7 @@ def main():
         "world_size_seen": dist.get_world_size() if use_dist else 1,
     }
 
-    if use_dist and wl.mode == "gram" and args.scaling is None:
+    if args.full and use_dist and wl.mode == "gram" and args.scaling is None:
         # the other scaling of the same config in the same line: BASELINE's ">= 6x at 8 GPUs" reads on the FIXED batch (strong:
         # the batch divided over the ranks); `value` above is the weak figure (the batch per GPU fixed).  At N = 1 they coincide.
         other = Workload(args.config, world, "strong" if wl.scaling == "weak" else "weak", dev, group)
@@ -495,18 +532,18 @@ def main():
             "collectives": collectives_per_step(other.step, min(args.steps, 5), dist, dev),
             "note": "same config, same steps / warmup / barriers, timed right after the headline region"}
         del other
-    if use_dist:
+    if args.full and use_dist:
         # per-step time inside RCCL (all ranks take part; after the timed regions): what a shortfall of the scaling curve is made of
         result["collectives"] = collectives_per_step(wl.step, min(args.steps, 5), dist, dev)
 
     t_ex = time.perf_counter()
-    if rank == 0 and not args.no_extras:
+    if args.full and rank == 0 and not args.no_extras:
         extras(result, args, wl.cfg, wl.sk1, be, wl.X, wl.Y, wl.Xc, wl.Yc, out, wl.A_total, world, value)
     t_cf = time.perf_counter()
-    if rank == 0 and not use_dist and not args.no_extras and not args.no_configs and args.config == "c3":
+    if args.full and rank == 0 and not use_dist and not args.no_extras and not args.no_configs and args.config == "c3":
         del out
         result["configs"] = other_configs(dev, args)
-    if use_dist and not args.no_configs and args.config == "c3":
+    if args.full and use_dist and not args.no_configs and args.config == "c3":
         # N > 1 (or --force-dist): the configs BASELINE names for several GPUs -- configs[3] above all -- strong-scaled under the
         # same process group, every rank taking part, rank 0 checking its output against the oracle
         out = None

@@ -9,8 +9,8 @@ cuda_backend.py:2, static_kernels.py:4) and numba is not installed.
 
 The reference is Python: per the travel rule nothing under oracle/_ref/ goes to
 the GPU box (.gpurunignore) or into history (.gitignore).  It is used only by
-tests/golden/make_golden.py and tests/test_oracle_vs_reference.py (skipped when
-/root/reference is absent).
+tests/golden/make_golden.py, which stores what the reference returns under
+tests/golden/ for the tests.
 """
 import os
 import subprocess

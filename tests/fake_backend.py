@@ -84,6 +84,18 @@ class OracleBackend:
         return tuple(torch.from_numpy(v).to(inc3.dtype) for v in O.solve_deriv_coarse(a[0], a[1], a[2], dyadic))
 
     def static_deriv_increments(self, kind, param, X0, X1, X2, Y, eps):
-        import sigkernel_amd
-        k = sigkernel_amd.LinearKernel() if kind == 0 else sigkernel_amd.RBFKernel(param)
-        return self.deriv_increments(k.Gram_matrix(X0, Y), k.Gram_matrix(X1, Y), k.Gram_matrix(X2, Y), eps)
+        return self.deriv_increments(*(_rowwise_gram(kind, param, X, Y) for X in (X0, X1, X2)), eps)
+
+
+def _rowwise_gram(kind, param, X, Y):
+    """The static Gram matrix (A,B,M,N) of LinearKernel / RBFKernel(param) with the inner products summed over the path dimension
+    in index order by elementwise operations: every entry is rounded the same however many rows of X come with it.  (A batched
+    GEMM may choose its kernel, and so its rounding, by the batch shape -- and the tiling tests compare tiles with the whole
+    batch bit for bit.)"""
+    dot = sum(X[:, None, :, None, d] * Y[None, :, None, :, d] for d in range(X.shape[-1]))
+    if kind == 0:
+        return dot
+    xs = sum(X[..., d] ** 2 for d in range(X.shape[-1]))
+    ys = sum(Y[..., d] ** 2 for d in range(Y.shape[-1]))
+    dist = -2. * dot + (xs[:, None, :, None] + ys[None, :, None, :])
+    return torch.exp(-dist / param)

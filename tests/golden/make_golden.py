@@ -253,9 +253,47 @@ def derivative_cases():
     save("derivatives", **out)
 
 
+# ---------------------------------------------------------------------------------------------
+# 7. tests/test_oracle_vs_reference.py: its own inputs (seeds other than the fixtures above) and what
+# the reference returns for them -- the raw solver on increments of several shapes (bit-identity),
+# compute_Gram + backward of a weighted sum, the derivative stencil's full grids
+# ---------------------------------------------------------------------------------------------
+def reference_checks_case():
+    from sigkernel.mps_backend import sigkernel_derivatives_Gram_mps
+    out = {}
+    for naive in (0, 1):
+        rng = np.random.default_rng(20240917 + naive)
+        for i, shape in enumerate([(4, 11, 6), (2, 5, 23), (1, 1, 1)]):
+            inc = rng.normal(scale=0.4, size=shape)
+            out.update({"solver_n%d_inc%d" % (naive, i): inc, "solver_n%d_grid%d" % (naive, i): sigkernel_cython(inc, bool(naive))})
+        inc4 = rng.normal(scale=0.4, size=(3, 2, 7, 9))
+        incs = rng.normal(scale=0.4, size=(3, 3, 6, 6))
+        out.update({"solver_n%d_inc4" % naive: inc4, "solver_n%d_grid4" % naive: sigkernel_Gram_cython(inc4, False, bool(naive)),
+                    "solver_n%d_incs" % naive: incs, "solver_n%d_grids" % naive: sigkernel_Gram_cython(incs, True, bool(naive))})
+    for kind, d in [("linear", 0), ("linear", 2), ("rbf", 1), ("rbf", 3)]:
+        gen = torch.Generator().manual_seed(99 + d)
+        X, Y = walk(gen, 4, 9, 3) * 2, walk(gen, 3, 12, 3) * 2
+        rs = ref.SigKernel(kernel_of(kind, 0.8), dyadic_order=d)
+        Xg = X.clone().requires_grad_(True)
+        K = rs.compute_Gram(Xg, Y)
+        w = torch.randn(4, 3, generator=gen, dtype=torch.float64)
+        (K * w).sum().backward()
+        key = "gram_%s_d%d_" % (kind, d)
+        out.update({key + "X": X, key + "Y": Y, key + "w": w, key + "K": K, key + "grad": Xg.grad})
+    rng = np.random.default_rng(5)
+    inc, inc_d, inc_dd = (torch.tensor(rng.normal(scale=0.4, size=(2, 2, 5, 8))) for _ in range(3))
+    K = torch.zeros(2, 2, 6, 9, dtype=torch.float64)
+    Kd, Kdd = torch.zeros_like(K), torch.zeros_like(K)
+    K[:, :, 0, :] = 1.
+    K[:, :, :, 0] = 1.
+    sigkernel_derivatives_Gram_mps(inc, inc_d, inc_dd, 5, 8, K, Kd, Kdd)
+    out.update(deriv_inc=inc, deriv_inc_d=inc_d, deriv_inc_dd=inc_dd, deriv_K=K, deriv_Kd=Kd, deriv_Kdd=Kdd)
+    save("reference_checks", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["solver", "readme", "gram", "gram_wide", "kat", "wrappers", "derivatives"]
+    which = sys.argv[1:] or ["solver", "readme", "gram", "gram_wide", "kat", "wrappers", "derivatives", "reference_checks"]
     table = dict(solver=solver_cases, readme=readme_case, gram=gram_cases, gram_wide=gram_wide_cases, kat=kat_case, wrappers=wrappers_case,
-                 derivatives=derivative_cases)
+                 derivatives=derivative_cases, reference_checks=reference_checks_case)
     for w in which:
         table[w]()

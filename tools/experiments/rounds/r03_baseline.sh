@@ -4,7 +4,7 @@ set -u
 OUT=$PWD/gpurun_out/r03a; rm -rf $OUT; mkdir -p $OUT; REPO=$PWD; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc $?" >> $OUT/pytest.log
 for cfg in c3 c4 c2 c5; do
-  timeout 600 python bench.py --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
+  timeout 600 python bench.py --full --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err
 done
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace_c4 -o trace -- python $REPO/bench.py --config c4 --steps 2 --warmup 1 --no-extras > $OUT/trace_c4.json 2> $OUT/trace_c4.err

@@ -4,7 +4,7 @@
 # Usage: tools/profile_bench.sh <tag> [bench args...]     -> gpurun_out/prof_<tag>/
 set -u
 TAG=${1:-r01}; shift || true
-ARGS=${*:-"--steps 5 --warmup 2"}
+ARGS=${*:-"--full --steps 5 --warmup 2"}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
@@ -13,7 +13,7 @@ cd /tmp
 
 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o trace -- python "$REPO/bench.py" $ARGS > "$OUT/bench_under_trace.json" 2> "$OUT/trace.err"
 
-PMC_ARGS="--steps 2 --warmup 1 --no-cpu-baseline"
+PMC_ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline"
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL" \
            "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS" \
            "GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum" \

@@ -3,9 +3,9 @@
 # the kernel's average duration in the stats must agree with roofline.avg_launch_ms of the line.  usage: profile_default_bench.sh <tag>
 set -u
 TAG=${1:-r04}; OUT=$PWD/gpurun_out/${TAG}d; rm -rf $OUT; mkdir -p $OUT; REPO=$PWD; export TMPDIR=/tmp
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o trace -- python $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --no-live-traffic --no-cpu-baseline > $OUT/bench_under_trace.json 2> $OUT/trace.err
+timeout 900 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o trace -- python $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-live-traffic --no-cpu-baseline > $OUT/bench_under_trace.json 2> $OUT/trace.err
 cd $REPO
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1); cp "$f" $OUT/kernel_stats.csv
 python - $OUT <<'PY'

@@ -62,5 +62,5 @@ bash tools/pmc_fwd.sh ${TAG}fwd > $OUT/pmc_fwd_solver.txt 2>&1
 python tools/traffic.py $OUT gpurun_out/pmc_${TAG}fwd $TAG > $OUT/traffic.log 2>&1
 timeout 900 python tools/shard_times.py c4 $OUT/c4_shard_times.json > $OUT/shard_c4.log 2>&1
 timeout 900 python tools/shard_times.py c3 $OUT/c3_shard_times.json > $OUT/shard_c3.log 2>&1
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-for cfg in c2 c4 c5; do timeout 900 python bench.py --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err; done
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+for cfg in c2 c4 c5; do timeout 900 python bench.py --full --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err; done
