@@ -59,9 +59,10 @@ typedef enum sk_status {
 #define SK_FLAG_FAST_ONLY 4 /* never fall back: SK_ERR_UNSUPPORTED if the tiled kernels do not
                                cover the shape/layout (used by tests and benchmarks)            */
 
-/* 330.  The number moves whenever an exported signature changes incompatibly: 310 -> 320 gave sk_solve_fwd_{linear,rbf}_sym_* their
+/* 340.  The number moves whenever an exported signature changes incompatibly: 310 -> 320 gave sk_solve_fwd_{linear,rbf}_sym_* their
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
- * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums).  A binding
+ * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
+ * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -145,7 +146,9 @@ int sk_increments_f32(const float *G, int64_t P, int M, int N, float *inc_c, int
  *           equal to the D <= 8 form's left-to-right sum to rounding
  *   kind 1: rbf,    G = exp(-|x_p - y_q|^2 / param) (param = sigma), inc = ((G11 + G00) - G10) - G01
  *   X [A,M,D], Y [B,N,D] dense; B > 0: Gram, pair (a,b) at a*B+b; B == 0: paired, pair a = (x_a, y_a), Y [A,N,D].
- *   inc_c [P,M-1,ld] with zero-filled padding columns.  D <= 32 (else SK_ERR_UNSUPPORTED: use the generic path). */
+ *   inc_c [P,M-1,ld] with zero-filled padding columns.  Any D >= 1: beyond 32 dims the node Gram runs as a K-looped GEMM on
+ *   v_mfma_f64_16x16x4_f64 (one workgroup per 64-row tile of x_a and several y_b, dims staged through LDS; fp32 paths up-cast on
+ *   load) -- dims summed in a different order than the generic route's, equal to it to rounding. */
 int sk_static_increments_f64(int kind, double param, const double *X, const double *Y, int64_t A, int64_t B, int M, int N,
                              int D, double *inc_c, int64_t ld, void *stream);
 int sk_static_increments_f32(int kind, double param, const float *X, const float *Y, int64_t A, int64_t B, int M, int N,
@@ -155,7 +158,9 @@ int sk_static_increments_f32(int kind, double param, const float *X, const float
  * nor dL/dG_static materialised.  Replaces the finite-difference contraction (sigkernel.py:313-341, :472-500) and the
  * `grad_output * grad_points` reduction over the second batch index (:343, :410-416) for these two static kernels.
  *   W [P,M-1,ldw]; scale [P] = upstream gradient per pair (NULL = 1); pairs as in sk_static_increments_*.
- *   kind 1 (rbf):    out = dL/dX [A,M,D].
+ *   kind 1 (rbf):    out = dL/dX [A,M,D] for D <= 32.  D > 32: out = H [P,M,ldh], ldh = N rounded up to whole 128-byte rows,
+ *                    H[p][m][n] = scale_p dL/dG[m][n] G[m][n] (dL/dG: the 4-corner adjoint of W) -- the first pass of the chain rule;
+ *                    the caller finishes dL/dx_a[m] = -(2/param) (sum_{b,n} H[a,b,m,n] x_m - sum_b H[a,b] @ y_b) with library GEMMs.
  *   kind 0 (linear): out = T [A,M-1,D], T[a][p] = sum_b scale_ab sum_q W[a,b,p,q] (y[b,q+1]-y[b,q]) (the caller differences it along
  *                    the path and applies scale^2), for 9 <= D <= 32 and N <= 128 (k_static_linear_adj_tiled: W read once, y_b through
  *                    LDS).  SK_ERR_UNSUPPORTED otherwise: dim <= 8 runs from pre-differenced paths in sk_linear_adjoint_*, wider or

@@ -143,7 +143,7 @@ def _stage_rows(kind, M, gram):
     return 64 if need <= 64 else (128 if need <= 128 else 256)
 
 
-ABI_VERSION = 330      # include/sigkernel_amd.h: sk_version()
+ABI_VERSION = 340      # include/sigkernel_amd.h: sk_version()
 
 
 def load():
@@ -366,6 +366,28 @@ class _WorstResidual:
         return float(self.err.max())
 
 
+def _pair_gemm_sum(Wv, Yv, scale, gram):
+    """sum_b scale[a, b] Wv[a, b] @ Yv[b] -> (A, R, D) for Wv (A, B, R, C), Yv (B, C, D) (gram), or scale[a] Wv[a] @ Yv[a] for Wv (A, R, C),
+    Yv (A, C, D) (paired); scale None: 1.  The chain rules' contraction with the second paths, as batched library GEMMs."""
+    if not gram:
+        T = torch.matmul(Wv, Yv)                                    # (A, R, D)
+        return T * scale[:, None, None] if scale is not None else T
+    A, B, R, D = Wv.shape[0], Wv.shape[1], Wv.shape[2], Yv.shape[2]
+    # in column blocks of Y, so that the (A, b, R, D) products stay below ~256 MB whatever B is (ADVICE r4: for D close to N the
+    # un-blocked product was up to twice the size of W, outside the caller's tile accounting)
+    step = max(1, int((256 << 20) // max(1, A * R * D * Wv.element_size())))
+    T = None
+    for b0 in range(0, B, step):
+        Tm = torch.matmul(Wv[:, b0:b0 + step], Yv[b0:b0 + step])    # (A, b, R, D)
+        if scale is not None:
+            Tm = Tm.mul_(scale[:, b0:b0 + step, None, None])
+        T = Tm.sum(1) if T is None else T.add_(Tm.sum(1))
+        del Tm
+    if T is None:
+        T = torch.zeros(A, R, D, dtype=Wv.dtype, device=Wv.device)
+    return T
+
+
 class HipBackend:
     """The product back-end: every method enqueues HIP kernels on the current stream."""
 
@@ -398,12 +420,13 @@ class HipBackend:
         """Static kernel + increments in one pass (kind 0 = linear with param = scale, 1 = rbf with param = sigma).
 
         gram=True: X (A,M,D), Y (B,N,D) -> inc_c (A,B,M-1,N-1); gram=False (paired): Y (A,N,D) -> (A,M-1,N-1).
-        Returns None when the shape is outside the fused kernels (D > 32): the caller takes the generic path."""
+        Any path dim: beyond MAX_FUSED_DIM the node Gram runs as a K-looped GEMM on the matrix cores (k_static_wide_mfma).
+        Returns None for paths of fewer than two points: the caller takes the generic path."""
         _dev(X, "X")
         _dev(Y, "Y")
         A, M, D = X.shape
         B, N = Y.shape[0], Y.shape[1]
-        if D > self.MAX_FUSED_DIM or M < 2 or N < 2:
+        if M < 2 or N < 2:
             return None
         ld = _padded_ld(N - 1, X.element_size())
         shape = (A, B, M - 1, ld) if gram else (A, M - 1, ld)
@@ -1004,27 +1027,24 @@ class HipBackend:
                     # wider or longer paths: T[a] = sum_b scale[a, b] W[a, b] (Mc x Nc) @ dY[b] (Nc x D) IS a batched matrix product --
                     # a plain library GEMM (rocBLAS under torch.matmul)
                     # (256 x 256 pairs of 100 points: dim 12 / 20 / 32 7.2 / 24.4 / 42.9 -> 2.3 / 2.5 / 4.9 ms, equal to 1e-15)
-                    dY = Y[:, 1:] - Y[:, :-1]
-                    Wv = W[..., :N - 1]
-                    if gram:
-                        # in column blocks of Y, so that the (A, b, Mc, D) products stay below ~256 MB whatever B is (for D
-                        # close to N the un-blocked product was up to twice the size of W, outside the caller's tile accounting)
-                        step = max(1, int((256 << 20) // max(1, A * (M - 1) * D * X.element_size())))
-                        T = None
-                        for b0 in range(0, B, step):
-                            Tm = torch.matmul(Wv[:, b0:b0 + step], dY[b0:b0 + step])    # (A, b, Mc, D)
-                            if scale is not None:
-                                Tm = Tm.mul_(scale[:, b0:b0 + step, None, None])
-                            T = Tm.sum(1) if T is None else T.add_(Tm.sum(1))
-                            del Tm
-                    else:
-                        T = torch.matmul(Wv, dY)                                    # (A, Mc, D)
-                        if scale is not None:
-                            T = T * scale[:, None, None]
+                    T = _pair_gemm_sum(W[..., :N - 1], Y[:, 1:] - Y[:, :-1], scale, gram)
                 g = torch.zeros(A, M, D, dtype=X.dtype, device=X.device)
                 g[:, 1:] += T          # d inc[p,q] / d x[p+1] = +s^2 dy[q]
                 g[:, :-1] -= T         # d inc[p,q] / d x[p]   = -s^2 dy[q]
                 return g * (float(param) ** 2) if float(param) != 1.0 else g
+            if D > self.MAX_FUSED_DIM:
+                # wide paths: the kernel writes H = go_ab dL/dG (.) G per node (k_static_wide_mfma, first pass); with
+                # dG/dx_m = -(2 / sigma) G (x_m - y_n):  dL/dx_a[m] = -(2 / sigma) (rowsum_bn(H) x_m - sum_b H[a, b] @ y_b) -- the
+                # second term is the batched GEMM of the linear branch above
+                H = torch.empty((A, B, M, _padded_ld(N, X.element_size())) if gram else (A, M, _padded_ld(N, X.element_size())),
+                                dtype=X.dtype, device=X.device)
+                _check(fn(1, float(param), _ptr(X), _ptr(Y), _ptr(W), ldw, _ptr(scale), A, B if gram else 0, M, N, D, _ptr(H),
+                          _stream(X)), "sk_static_adjoint")
+                H = H[..., :N]
+                rs = H.sum((1, 3)) if gram else H.sum(2)                                 # (A, M)
+                g = _pair_gemm_sum(H, Y, None, gram)
+                del H
+                return g.sub_(rs[..., None] * X).mul_(2. / float(param))
             g = torch.empty(A, M, D, dtype=X.dtype, device=X.device)
             _check(fn(1, float(param), _ptr(X), _ptr(Y), _ptr(W), ldw, _ptr(scale), A, B if gram else 0, M, N, D, _ptr(g),
                       _stream(X)), "sk_static_adjoint")

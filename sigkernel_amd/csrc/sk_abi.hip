@@ -205,11 +205,13 @@ int device_cu_count() {
 
 extern "C" {
 
+// 340: sk_static_increments_* serve any path dim (D > 32: k_static_wide_mfma); sk_static_adjoint_* kind 1 with D > 32 writes the first
+// pass H [P][M][ldh] of the rbf chain rule instead of dL/dX
 // 330 (round 6): sk_linear_adjoint_fused_f64 takes ypart / ypart_doubles / ycols_out (the second-argument sums, route FUSED_SWAP)
 // 320 (round 5/6): sk_solve_fwd_{linear,rbf}_sym_* take the pair table (argument 3), sk_prep_cat_*, sk_solve_fwd_loss_f64, sk_loss_*,
 // sk_*_adjoint_finish_f64, sk_cost_query; the SK_WAVE_PF / SK_DERIV_PF / SK_ADJR_ALL knobs are gone; split mode's status word
 // (310: edges argument of sk_solve_fwd_static_*, the multi-band adjoints, the fused derivative solver)
-int sk_version(void) { return 330; }
+int sk_version(void) { return 340; }
 
 int sk_launch_trace(int enable) {
     const int prev = sk::g_trace.load(std::memory_order_relaxed);

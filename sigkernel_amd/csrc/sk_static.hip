@@ -15,6 +15,7 @@
 // node arrays of the directional derivative); their adjoints k_static_rbf_adj (dim <= 16, or second paths of more than 128 points),
 // k_static_rbf_adj_tiled (17..32 dims) and k_static_linear_adj_tiled (9..32 dims) -- y_b through LDS, pairs loaded a chunk ahead --,
 // k_linear_adj_dyt (dim <= 8, pre-differenced dimension-major y), and the second-argument forms k_linear_adj2 / k_rbf_adj2.
+// Beyond 32 dims: k_static_wide_mfma (the node Gram as a K-looped fp64 GEMM; linear and rbf increments, the rbf chain rule's first pass).
 #include <type_traits>
 
 #include "sk_internal.h"
@@ -1085,6 +1086,249 @@ int launch_static_deriv_d(int kind, double param, const T *X0, const T *X1, cons
     return check_launch();
 }
 
+// ---- wide paths (D > 32): the node Gram of a pair as a K-looped fp64 GEMM on the matrix cores -----------------------------------
+//
+// Beyond 32 dims a node costs 2 D flops of inner product against ~30 for the exponential and the differences: GEMM work.  One
+// workgroup of four waves owns a 64-row tile of x_a and walks WD_NB consecutive y_b (Gram; one pair in paired mode) over a 64-column
+// tile of each: the dims are staged through LDS in chunks of WD_KC (double-buffered: the next chunk's global loads are in flight
+// while v_mfma_f64_16x16x4_f64 consumes the current one), so x_a's fragments are loaded once per chunk for all WD_NB y_b.  Wave w
+// holds rows 16 w .. 16 w + 15 of every tile: C[row (lane >> 4) + 4 r][col lane & 15] in register r.  fp32 paths are up-cast on load.
+// One instance per element type; the epilogue is chosen at run time:
+//   WIDE_LINEAR   rows / columns are the row-differenced paths: inc = s^2 <dx_p, dy_q>, written straight from the accumulators
+//   WIDE_RBF      rows / columns are nodes, tiles overlap by one node row and column (stride 63): G = exp(-(|x|^2 + |y|^2 - 2<x,y>) / sigma)
+//                 goes through LDS, inc = ((G11 + G00) - G10) - G01 -- the operand order of k_static_nodes
+//   WIDE_RBF_ADJ  nodes at stride 64: H[m][n] = go_ab dG[m][n] G[m][n], dG = the 4-corner adjoint of W = dL/d inc around the node --
+//                 the first pass of the rbf chain rule; the caller finishes dL/dx_a[m] = -(2 / sigma) (rowsum(H) x_m - sum_b H y_b)
+constexpr int WD_KC = 8, WD_LDK = WD_KC + 1, WD_NB = 4, WD_TPB = 256;
+enum { WIDE_LINEAR = 0, WIDE_RBF = 1, WIDE_RBF_ADJ = 2 };
+
+template <typename T>
+__global__ __launch_bounds__(WD_TPB) void k_static_wide_mfma(const T *__restrict__ X, const T *__restrict__ Y, int64_t B, int M, int N, int D,
+                                                             int mode, double param, T *__restrict__ out, int64_t ld,
+                                                             const T *__restrict__ W, int64_t ldw, const T *__restrict__ scale,
+                                                             int row_tiles, int col_tiles, int b_groups) {
+    // staging: two buffers of (1 + WD_NB) tiles of 64 rows x WD_KC dims (46 KB); the rbf epilogue's 64 x 65 node tile reuses it
+    __shared__ double stage[2 * (1 + WD_NB) * 64 * WD_LDK];
+    __shared__ double xn[64], yn[WD_NB][64];
+    const int Mc = M - 1, Nc = N - 1;
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63, li = lane & 15, lk = lane >> 4;
+    int64_t blk = blockIdx.x;
+    const int ct = (int)(blk % col_tiles);
+    blk /= col_tiles;
+    const int rt = (int)(blk % row_tiles);
+    blk /= row_tiles;
+    const int bg = (int)(blk % b_groups);
+    const int64_t a = blk / b_groups;
+    const bool gram = B > 0;
+    const int64_t b0 = gram ? (int64_t)bg * WD_NB : a;
+    const int nb = gram ? (int)min((int64_t)WD_NB, B - b0) : 1;
+    const bool diff = mode == WIDE_LINEAR;
+    const int step = mode == WIDE_RBF ? 63 : 64;
+    const int r0 = rt * step, c0 = ct * step;
+
+    // this thread's share of every chunk: row lr of each tile, dims 2 (t & 3) and 2 (t & 3) + 1
+    const int lr = t >> 2, lkk = (t & 3) * 2;
+    const T *xp1, *xp0;
+    bool xok;
+    {
+        const T *x = X + a * (int64_t)M * D;
+        const int r = r0 + lr;
+        if (diff) {
+            const int rc = min(r, Mc - 1);
+            xok = r < Mc;
+            xp1 = x + (int64_t)(rc + 1) * D;
+            xp0 = x + (int64_t)rc * D;
+        } else {
+            xok = true;
+            xp1 = xp0 = x + (int64_t)min(r, M - 1) * D;
+        }
+    }
+    const T *yp1[WD_NB], *yp0[WD_NB];
+    bool yok[WD_NB];
+#pragma unroll
+    for (int j = 0; j < WD_NB; ++j) {
+        const T *y = Y + min(b0 + j, b0 + nb - 1) * (int64_t)N * D;
+        const int q = c0 + lr;
+        if (diff) {
+            const int qc = min(q, Nc - 1);
+            yok[j] = q < Nc && j < nb;
+            yp1[j] = y + (int64_t)(qc + 1) * D;
+            yp0[j] = y + (int64_t)qc * D;
+        } else {
+            yok[j] = j < nb;
+            yp1[j] = yp0[j] = y + (int64_t)min(q, N - 1) * D;
+        }
+    }
+    const double s2 = diff ? param * param : 1.0;
+    auto fetch = [&](const T *p1, const T *p0, bool ok, int k, double mul) -> double {
+        if (!ok || k >= D) return 0.0;
+        return diff ? mul * ((double)p1[k] - (double)p0[k]) : (double)p0[k];
+    };
+    double rx[2], ry[WD_NB][2], xsq = 0.0, ysq[WD_NB];
+#pragma unroll
+    for (int j = 0; j < WD_NB; ++j) ysq[j] = 0.0;
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            rx[e] = fetch(xp1, xp0, xok, k0 + lkk + e, 1.0);
+            xsq = fma(rx[e], rx[e], xsq);
+#pragma unroll
+            for (int j = 0; j < WD_NB; ++j) {
+                ry[j][e] = fetch(yp1[j], yp0[j], yok[j], k0 + lkk + e, s2);
+                ysq[j] = fma(ry[j][e], ry[j][e], ysq[j]);
+            }
+        }
+    };
+    auto store = [&](int buf) {
+        double *s = stage + buf * (1 + WD_NB) * 64 * WD_LDK;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            s[lr * WD_LDK + lkk + e] = rx[e];
+#pragma unroll
+            for (int j = 0; j < WD_NB; ++j) s[(1 + j) * 64 * WD_LDK + lr * WD_LDK + lkk + e] = ry[j][e];
+        }
+    };
+
+    d4_t acc[WD_NB][4];
+#pragma unroll
+    for (int j = 0; j < WD_NB; ++j)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[j][nt] = d4_t{0.0, 0.0, 0.0, 0.0};
+
+    const int chunks = (D + WD_KC - 1) / WD_KC;
+    load(0);
+    store(0);
+    __syncthreads();
+#pragma unroll 1
+    for (int c = 0; c < chunks; ++c) {
+        const int cur = c & 1;
+        if (c + 1 < chunks) load((c + 1) * WD_KC);      // in flight while the matrix cores consume chunk c
+        const double *s = stage + cur * (1 + WD_NB) * 64 * WD_LDK;
+#pragma unroll
+        for (int ks = 0; ks < WD_KC / 4; ++ks) {
+            const double af = s[(16 * w + li) * WD_LDK + ks * 4 + lk];
+#pragma unroll
+            for (int j = 0; j < WD_NB; ++j) {
+                if (j < nb) {
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) {
+                        const double bf = s[(1 + j) * 64 * WD_LDK + (nt * 16 + li) * WD_LDK + ks * 4 + lk];
+                        acc[j][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[j][nt], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        if (c + 1 < chunks) store(cur ^ 1);
+        __syncthreads();
+    }
+
+    if (mode == WIDE_LINEAR) {
+#pragma unroll
+        for (int j = 0; j < WD_NB; ++j) {
+            if (j >= nb) break;
+            T *o = out + (gram ? a * B + b0 + j : a) * (int64_t)Mc * ld;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const int col = c0 + nt * 16 + li;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = r0 + 16 * w + lk + 4 * r;
+                    if (row < Mc && col < ld) o[(int64_t)row * ld + col] = (T)acc[j][nt][r];
+                }
+            }
+        }
+        return;
+    }
+
+    // squared norms of the nodes: the four threads of a row hold a quarter of its dims each (lanes t ^ 1, t ^ 2: the same wave)
+    xsq += __shfl_xor(xsq, 1, 64);
+    xsq += __shfl_xor(xsq, 2, 64);
+#pragma unroll
+    for (int j = 0; j < WD_NB; ++j) {
+        ysq[j] += __shfl_xor(ysq[j], 1, 64);
+        ysq[j] += __shfl_xor(ysq[j], 2, 64);
+    }
+    if ((t & 3) == 0) {
+        xn[lr] = xsq;
+#pragma unroll
+        for (int j = 0; j < WD_NB; ++j) yn[j][lr] = ysq[j];
+    }
+    __syncthreads();
+    const double inv_sigma = 1.0 / param;
+    auto node = [&](double xy, int row, int j, int col) -> double {
+        // rbf: dist = -2 xy + (xs + ys);  G = exp(-dist / sigma)          (static_kernels.py:53-56, :70-73)
+        return exp_nonpos(-(fma(-2.0, xy, xn[row] + yn[j][col])) * inv_sigma);
+    };
+
+    if (mode == WIDE_RBF) {
+        double *g = stage;           // [64][65] node values of one y_b
+#pragma unroll
+        for (int j = 0; j < WD_NB; ++j) {
+            if (j >= nb) break;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * w + lk + 4 * r, col = nt * 16 + li;
+                    g[row * 65 + col] = node(acc[j][nt][r], row, j, col);
+                }
+            __syncthreads();
+            T *o = out + (gram ? a * B + b0 + j : a) * (int64_t)Mc * ld;
+            for (int idx = t; idx < 63 * 64; idx += WD_TPB) {
+                const int i = idx >> 6, jj = idx & 63;
+                const int p = r0 + i, q = c0 + jj;
+                if (jj < 63 && p < Mc && q < ld) {
+#pragma clang fp contract(off)
+                    const double d = ((g[(i + 1) * 65 + jj + 1] + g[i * 65 + jj]) - g[(i + 1) * 65 + jj]) - g[i * 65 + jj + 1];
+                    o[(int64_t)p * ld + q] = q < Nc ? (T)d : (T)0;
+                }
+            }
+            __syncthreads();
+        }
+        return;
+    }
+
+    // WIDE_RBF_ADJ: out = H [P][M][ld]
+#pragma unroll
+    for (int j = 0; j < WD_NB; ++j) {
+        if (j >= nb) break;
+        const int64_t pr = gram ? a * B + b0 + j : a;
+        const double go = scale ? (double)scale[pr] : 1.0;
+        const T *Wp = W + pr * (int64_t)Mc * ldw;
+        T *o = out + pr * (int64_t)M * ld;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const int n = c0 + nt * 16 + li;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = r0 + 16 * w + lk + 4 * r;
+                if (m < M && n < N) {
+                    const bool up = m >= 1, lo = m < Mc, le = n >= 1, ri = n < Nc;
+                    const double dG = ((up && le ? (double)Wp[(int64_t)(m - 1) * ldw + n - 1] : 0.0) +
+                                       (lo && ri ? (double)Wp[(int64_t)m * ldw + n] : 0.0)) -
+                                      (up && ri ? (double)Wp[(int64_t)(m - 1) * ldw + n] : 0.0) -
+                                      (lo && le ? (double)Wp[(int64_t)m * ldw + n - 1] : 0.0);
+                    o[(int64_t)m * ld + n] = (T)(go * dG * node(acc[j][nt][r], m - r0, j, n - c0));
+                }
+            }
+        }
+    }
+}
+
+// mode, tiles and grid of k_static_wide_mfma; ld: the output's row stride (inc_c, or H for WIDE_RBF_ADJ)
+template <typename T>
+int launch_static_wide(int mode, double param, const T *X, const T *Y, int64_t A, int64_t B, int M, int N, int D, T *out, int64_t ld,
+                       const T *W, int64_t ldw, const T *scale, hipStream_t s) {
+    const int64_t rows = mode == WIDE_RBF_ADJ ? M : M - 1, cols = mode == WIDE_RBF_ADJ ? N : ld;
+    const int step = mode == WIDE_RBF ? 63 : 64;
+    const int64_t rts = (rows + step - 1) / step, cts = (cols + step - 1) / step, bgs = B > 0 ? (B + WD_NB - 1) / WD_NB : 1;
+    const int64_t blocks = A * bgs * rts * cts;
+    if (blocks > 0x7fffffffLL) return SK_ERR_UNSUPPORTED;
+    SK_LAUNCH((k_static_wide_mfma<T>), dim3((unsigned)blocks), dim3(WD_TPB), 0, s, X, Y, B, M, N, D, mode, param, out, ld, W, ldw, scale,
+              (int)rts, (int)cts, (int)bgs);
+    return check_launch();
+}
+
 }  // namespace
 
 template <typename T>
@@ -1112,10 +1356,13 @@ int launch_static_increments(int kind, double param, const T *X, const T *Y, int
     if (D <= 16) return launch_static_d<T, 16>(kind, param, X, Y, A, B, M, N, D, inc, ld, s);
     if (D <= 24) return launch_static_d<T, 24>(kind, param, X, Y, A, B, M, N, D, inc, ld, s);   // (lead-lag of 8..11 dims + time: 17..23)
     if (D <= 32) return launch_static_d<T, 32>(kind, param, X, Y, A, B, M, N, D, inc, ld, s);
-    return SK_ERR_UNSUPPORTED;   // wide paths: the caller uses the generic static kernel + sk_increments
+    // wide paths: the node Gram as a K-looped GEMM on the matrix cores
+    return launch_static_wide<T>(kind == 0 ? WIDE_LINEAR : WIDE_RBF, param, X, Y, A, B, M, N, D, inc, ld, (const T *)nullptr, 0,
+                                 (const T *)nullptr, s);
 }
 
-// out: kind 0 -> T [A, M-1, D] (the caller differences it along M and applies scale^2); kind 1 -> dL/dX [A, M, D]
+// out: kind 0 -> T [A, M-1, D] (the caller differences it along M and applies scale^2); kind 1 -> dL/dX [A, M, D], or for D > 32 the first
+// pass H [P, M, ldh] of k_static_wide_mfma (ldh: N padded to whole 128-byte lines; the caller contracts it with the paths)
 template <typename T>
 int launch_static_adjoint(int kind, double param, const T *X, const T *Y, const T *W, int64_t ldw, const T *scale, int64_t A,
                           int64_t B, int M, int N, int D, T *out, hipStream_t s) {
@@ -1131,7 +1378,8 @@ int launch_static_adjoint(int kind, double param, const T *X, const T *Y, const 
     if (D <= 16) return launch_static_adj_nt<T, 16>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);
     if (D <= 24) return launch_static_adj_nt<T, 24>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);   // (lead-lag of 8..11 dims + time)
     if (D <= 32) return launch_static_adj_nt<T, 32>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);
-    return SK_ERR_UNSUPPORTED;
+    constexpr int64_t q = 128 / sizeof(T);
+    return launch_static_wide<T>(WIDE_RBF_ADJ, param, X, Y, A, B, M, N, D, out, (N + q - 1) / q * q, W, ldw, scale, s);
 }
 
 // out: T [A, Mc, D] (the caller differences it along the path and applies scale^2)

@@ -330,8 +330,36 @@ def _rows_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, wor
     return grad
 
 
+def _functional(static_kernel):
+    """Whether the static kernel is a kernel of function-valued paths (static_kernels.Linear_ID_Kernel, RBF_ID_Kernel, RBF_CEXP_Kernel,
+    RBF_SQR_Kernel, or any kernel with the same two attributes): a ``features`` map (batch, T, ...) -> (batch, T, D_eff) and the
+    ``base_kernel`` (Linear / RBF) that acts on the features."""
+    return callable(getattr(static_kernel, "features", None)) and hasattr(static_kernel, "base_kernel")
+
+
+class _FeatureMap:
+    """The static kernel's feature map, applied once per distinct input tensor: where an input recurs (compute_Gram(X, X, sym=True)
+    inside the loss wrappers) the same feature tensor comes back, so the symmetric routes and the doubled gradient still see one tensor."""
+
+    def __init__(self, static_kernel):
+        self.features = static_kernel.features
+        self.seen = []
+
+    def __call__(self, X):
+        for t, f in self.seen:
+            if t is X:
+                return f
+        f = self.features(X)
+        self.seen.append((X, f))
+        return f
+
+
 def _check_inputs(X, Y, paired):
     if X.dim() != 3 or Y.dim() != 3:
+        if X.dim() == 4 or Y.dim() == 4:
+            raise ValueError("X and Y must have shape (batch, length, dim); paths of shape (batch, length, Lx, d) need a static kernel "
+                             "of function-valued paths (Linear_ID_Kernel, RBF_ID_Kernel, RBF_CEXP_Kernel, RBF_SQR_Kernel) and go "
+                             "through SigKernel's methods, which map them to features first")
         raise ValueError("X and Y must have shape (batch, length, dim)")
     if X.shape[2] != Y.shape[2]:
         raise ValueError("X and Y must have the same path dimension")
@@ -736,9 +764,22 @@ def k_kgrad(X, Y, gamma, dyadic_order, static_kernel, eps=1e-4, workspace_bytes=
     (sigkernel.py:529-541; their truncation error is part of the reference's result, so it is reproduced, not
     "fixed"); the three increment arrays then drive ONE sweep of the coupled PDE stencil (cuda_backend.py:206-220)
     in sk_solve_deriv_*.  No autograd: the reference's outputs carry none either (solution buffers are fresh
-    tensors, sigkernel.py:553-566)."""
+    tensors, sigkernel.py:553-566).
+
+    Function-valued paths (a static kernel with ``features``): the three node arrays are features(X), features(X + eps gamma) and
+    features(X + 2 eps gamma) -- the perturbation is formed in input space, as the reference's Gram_matrix sees it (sigkernel.py:526-541)
+    -- and the base kernel runs on them."""
+    nodes = None
+    if _functional(static_kernel):
+        if gamma.shape != X.shape or gamma.dtype != X.dtype or gamma.device != X.device:
+            raise ValueError("gamma must have X's shape, dtype and device")
+        with torch.no_grad():
+            phi = _FeatureMap(static_kernel)
+            Xf, Yf = phi(X.detach()), phi(Y.detach())
+            nodes = (phi(X.detach() + eps * gamma.detach()), phi(X.detach() + 2. * eps * gamma.detach()))
+        X, Y, gamma, static_kernel = Xf, Yf, None, static_kernel.base_kernel
     _check_inputs(X, Y, paired=False)
-    if gamma.shape != X.shape or gamma.dtype != X.dtype or gamma.device != X.device:
+    if gamma is not None and (gamma.shape != X.shape or gamma.dtype != X.dtype or gamma.device != X.device):
         raise ValueError("gamma must have X's shape, dtype and device")
     be = _lib.get_backend()
     A, B, M, N = X.shape[0], Y.shape[0], X.shape[1], Y.shape[1]
@@ -746,13 +787,17 @@ def k_kgrad(X, Y, gamma, dyadic_order, static_kernel, eps=1e-4, workspace_bytes=
     if M < 2 or N < 2:
         out[0] = 1.
         return out[0], out[1], out[2]
-    Xd, Yd, gd = X.detach(), Y.detach(), gamma.detach()
+    Xd, Yd, gd = X.detach(), Y.detach(), None if gamma is None else gamma.detach()
     fused = _fused_static(static_kernel, True) if hasattr(be, "static_deriv_increments") else None
     # transient bytes per row of X: three increment arrays (+ three static Gram matrices on the generic route)
     per_row = (3 if fused is not None else 6) * B * M * N * X.element_size()
     for a0, a1 in _tiles(A, per_row, _budget(X.device, workspace_bytes)):
-        Xt, gt = Xd[a0:a1], gd[a0:a1]
-        X1, X2 = Xt + eps * gt, Xt + 2. * eps * gt                                   # sigkernel.py:530, :537
+        Xt = Xd[a0:a1]
+        if nodes is None:
+            gt = gd[a0:a1]
+            X1, X2 = Xt + eps * gt, Xt + 2. * eps * gt                               # sigkernel.py:530, :537
+        else:
+            X1, X2 = nodes[0][a0:a1], nodes[1][a0:a1]
         if fused is not None and hasattr(be, "solve_deriv_fused") and not routes.no_fused_deriv:
             # static kernel, finite differences, increments AND the three-state sweep in one kernel (sk_solve_deriv_static_f64)
             res = be.solve_deriv_fused(fused[0], fused[1], Xt.contiguous(), X1, X2, Yd.contiguous(), dyadic_order, eps)
@@ -974,11 +1019,23 @@ class SigKernel:
         self.workspace_bytes = workspace_bytes
         self.process_group = process_group
 
+    def _on_features(self):
+        """(SigKernel of the base kernel, feature map) when the static kernel is one of function-valued paths, else None: the one
+        dispatch point of the methods below.  Inputs are mapped once each and the method runs on the features; gradients reach the
+        paths through torch autograd of the feature map."""
+        if not _functional(self.static_kernel):
+            return None
+        inner = SigKernel(self.static_kernel.base_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes, self.process_group)
+        return inner, _FeatureMap(self.static_kernel)
+
     def compute_kernel(self, X, Y, max_batch=100):
         """X (batch, len_x, dim), Y (batch, len_y, dim) -> (batch,) vector k(X^i_T, Y^i_T).
 
         ``max_batch`` is kept for signature compatibility (sigkernel.py:23); tiling is by HBM budget.  Under a process group the
         pairs are sharded over the ranks like Gram rows (sigkernel_amd.distributed.ShardedPaired)."""
+        f = self._on_features()
+        if f is not None:
+            return f[0].compute_kernel(f[1](X), f[1](Y), max_batch)
         if self.process_group is not None:
             from .distributed import sharded_kernel
             return sharded_kernel(self, X, Y, self.process_group)
@@ -996,6 +1053,9 @@ class SigKernel:
 
     def compute_Gram(self, X, Y, sym=False, max_batch=100):
         """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim) -> (batch_X, batch_Y) matrix k(X^i_T, Y^j_T)."""
+        f = self._on_features()
+        if f is not None:
+            return f[0].compute_Gram(f[1](X), f[1](Y), sym, max_batch)
         if self.process_group is not None:
             from .distributed import sharded_gram
             return sharded_gram(self, X, Y, sym, self.process_group)
@@ -1008,6 +1068,9 @@ class SigKernel:
     def compute_distance(self, X, Y, max_batch=100):
         """(batch,) paired squared distances reduced to their mean, as the reference does (sigkernel.py:130-144)."""
         assert not Y.requires_grad, "the second input should not require grad"
+        f = self._on_features()
+        if f is not None:
+            return f[0].compute_distance(f[1](X), f[1](Y), max_batch)
         n = X.shape[0] if X.dim() == 3 else 0
         if (not routes.no_merged_loss and X.dim() == 3 and X.shape == Y.shape and X.dtype == Y.dtype and X.device == Y.device and n > 0
                 and X.shape[1] >= 2 and float(n) * float((X.shape[1] - 1) << int(self.dyadic_order)) ** 2 < _cost("paired_merge_cells")):
@@ -1025,6 +1088,9 @@ class SigKernel:
     def compute_scoring_rule(self, X, y, max_batch=100):
         """S(X, y) = E[k(X, X)] - 2 E[k(X, y)] with y of shape (1, len_y, dim) (sigkernel.py:146-161)."""
         assert not y.requires_grad, "the second input should not require grad"
+        f = self._on_features()
+        if f is not None:
+            return f[0].compute_scoring_rule(f[1](X), f[1](y), max_batch)
         merged = self._merged_loss(X, y, with_yy=False)
         if merged is not None:
             return merged
@@ -1036,6 +1102,9 @@ class SigKernel:
     def compute_expected_scoring_rule(self, X, Y, max_batch=100):
         """S(X, Y) = E_Y[S(X, y)] (sigkernel.py:163-178)."""
         assert not Y.requires_grad, "the second input should not require grad"
+        f = self._on_features()
+        if f is not None:
+            return f[0].compute_expected_scoring_rule(f[1](X), f[1](Y), max_batch)
         merged = self._merged_loss(X, Y, with_yy=False)
         if merged is not None:
             return merged
@@ -1076,6 +1145,9 @@ class SigKernel:
         they are bound by the host's launch rate there, and the stream switches cost more than the overlap returns (0.59 -> 0.75 ms
         at 32 paths); large batches fill the chip with one launch (round 3: no gain from streams at BASELINE configs[3])."""
         assert not Y.requires_grad, "the second input should not require grad"
+        f = self._on_features()
+        if f is not None:
+            return f[0].compute_mmd(f[1](X), f[1](Y), max_batch)
         merged = self._merged_loss(X, Y, with_yy=True)
         if merged is not None:
             return merged

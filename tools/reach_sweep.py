@@ -150,6 +150,14 @@ def gated(g, be):
         sk = sigkernel_amd.SigKernel(RBF(0.9) if kname == "rbf" else LIN(), 1)
         Xg = walk(g, 3, M, 30, dt).requires_grad_(True)
         sk.compute_Gram(Xg, walk(g, 4, N, 30, dt)).sum().backward()
+    # paths of more than 32 dims, with a gradient: the K-looped matrix-core node Gram (k_static_wide_mfma: linear / rbf increments and
+    # the rbf chain rule's first pass), through a kernel of function-valued paths too
+    for kname, dt in itertools.product(("linear", "rbf"), (f64, f32)):
+        sk = sigkernel_amd.SigKernel(LIN() if kname == "linear" else RBF(0.9), 1)
+        Xg = walk(g, 3, 40, 40, dt).requires_grad_(True)
+        sk.compute_Gram(Xg, walk(g, 5, 30, 40, dt)).sum().backward()
+    sk = sigkernel_amd.SigKernel(sigkernel_amd.RBF_ID_Kernel(2.0), 1)
+    sk.compute_kernel(walk(g, 3, 20, 48, f64).reshape(3, 20, 16, 3), walk(g, 3, 25, 48, f64).reshape(3, 20 + 5, 16, 3))
     # paths of 9..32 dims with a gradient: the tiled static adjoints (LinearKernel 16 / 24 / 32 dims, RBFKernel 24 / 32; second paths of
     # <= 64 and of 65..128 points)
     for kname, D, dt, N in itertools.product(("linear", "rbf"), (12, 20, 30), (f64, f32), (50, 100)):
