@@ -25,6 +25,14 @@
 // the reference's 4-corner differences ((G11 + G00) - G10) - G01.  The last lane's missing neighbour and the one column
 // a pair's last unit borrows from the next pair are padding: M <= 64*RC and N <= 2*NUp.
 // All waves are independent (no barrier, private LDS slice) and launched four per workgroup (sk_wave_common.h).
+//
+// PAIR ORDER.  A wave of G = 64 / L lane groups runs G pairs at a time.  Paired, triangular and edge-keeping launches give lane
+// group g its own run of consecutive pairs, hence its own y ring.  A plain Gram launch without edges (G >= 2) uses the SHARED-Y
+// order instead (FusedParams::shy_A): stream position q of lane group g is the pair a = G (q / B) + g, b = q % B, so all groups
+// sweep the same y_b, ONE y ring and one y DMA per slab serve the wave, and lanes l and l + L read the same LDS address in the same
+// instruction (a broadcast).  Per-pair arithmetic is untouched: results are bit-identical in either order.  With the x windows of
+// four lanes (x_window) the headline shape (L = 32, G = 2, four rows per lane, 8 dims) takes 6 KB + 4 KB of LDS per wave instead
+// of 12 + 8, which is what lets a third wave per SIMD be resident.
 #include "sk_wave_common.h"
 #include <algorithm>
 
@@ -70,7 +78,17 @@ struct FusedParams {
     // pairs per lane group from pair rk_base[r] + (w - r rk_wpr) G rk_cnt[r] on
     int rk_n, rk_wpr;                 // (cnt packed 4 x 16 bits; rk_base[r] = G rk_wpr (cnt[0] + .. + cnt[r-1]) follows from them)
     unsigned long long rk_cnt;
+    // SHARED-Y pair order (a plain Gram launch without edges, G >= 2; shy_A = A > 0 switches it on): the G lane groups of a wave sweep
+    // the SAME y_b against G different x_a, so ONE y ring and one y DMA per slab serve the whole wave.  The stream then counts
+    // POSITIONS, one per wave and step of the stream, not pairs: P = ceil(A / G) B of them, position q of lane group g is the pair
+    // a = G (q / B) + g, b = q % B (no such pair when a >= A), and everything above that says "G C0" / "w G C0" reads without the G.
+    // Consulted in the prologue, the producers and the (rarely taken) store branch, never in the step loop.
+    int shy_A;
 };
+// lanes per x window: 8 (one window per y slab period), or 4 where four lanes' rows fill a whole 1 KiB LDS-DMA instruction anyway (the
+// linear four-row form with 8 dims and no edges: the headline's) -- half the x ring for the same number of DMA instructions, the
+// window bookkeeping every fourth step instead of every eighth
+constexpr int x_window(int kind, int nd, int rc, bool edges) { return (kind == 0 && nd == 8 && rc == 4 && !edges) ? 4 : 8; }
 
 template <int N>
 __device__ __forceinline__ void lds_read_units(d2_t (&v)[N], unsigned addr);
@@ -195,7 +213,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // x rows in LDS: 64 bytes (8 dims) each, or -- the four-dimension variants -- the 32 bytes that can be non-zero: with four or
     // eight pairs per wave (short paths) the x ring was what held a CU to one wave per SIMD at dyadic 0
     constexpr int XROW = x_row_bytes(ND);
-    constexpr int XSLAB = RC * 8 * XROW;   // 8 lanes x RC rows
+    constexpr int XW = x_window(KIND, ND, RC, EDGES);   // lanes (= macro-steps) per x window
+    constexpr int XSLAB = RC * XW * XROW;   // XW lanes x RC rows
     constexpr int Y_SLAB_PITCH = y_slab_pitch(ND);
     extern __shared__ __attribute__((aligned(16))) char lds_block[];
     char *lds;
@@ -209,7 +228,19 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     const int NUp = prm.NUp;
     const int NSLAB = (L >> 3) + 2;                       // y slabs resident per lane group
     const unsigned y_bytes = (unsigned)(NSLAB * Y_SLAB_PITCH);
-    const unsigned x_base0 = (unsigned)G * y_bytes;       // x rings behind all y rings
+    // shared-y pair order (FusedParams::shy_A): never with edges, never with one lane group per wave
+    const bool shy = !EDGES && !FULLWAVE && prm.shy_A > 0;
+    const int GY = shy ? 1 : G;                           // y rings of the wave = lane groups that own a stream of their own
+    // Inside the step loop's rare blocks (producers, store) the mode is re-derived from the ONE kernel argument behind an opaque
+    // move: hoisted out of the loop, `shy`, GY and their products each took scalar registers across it, and the loop's own values
+    // came back through v_readlane (26 -> 58 lane moves in the headline variant)
+    auto shy_a = [&]() __attribute__((always_inline)) -> int {
+        if (EDGES || FULLWAVE) return 0;
+        int v = prm.shy_A;
+        asm volatile("" : "+s"(v));
+        return v;
+    };
+    const unsigned x_base0 = (unsigned)GY * y_bytes;      // x rings behind all y rings
     const double sc = 1.0 / (double)(1 << (2 * DY));
     const double c_half = 0.5 * sc, c_12 = sc * sc / 12.0;
 
@@ -228,7 +259,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     {
         const int s0 = floor_div(-lam, 8);
         yslab = ((s0 % NSLAB) + NSLAB) % NSLAB;
-        ypar = (s0 + grp) & 1;
+        ypar = (s0 + (shy ? 0 : grp)) & 1;
     }
     const int my_uf = lam == prm.lam_f ? prm.u_f : -1;
     const int lam7 = lam & 7;
@@ -263,7 +294,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // waves evenly over the wave numbers instead was measured slower: 0.215 vs 0.197 ms on 128 x 128 symmetric pairs.)
     const int w32 = __builtin_amdgcn_readfirstlane((int)wave_id);
     int c0_ = prm.C0 + (w32 < prm.n_big ? 1 : 0);
-    unsigned cb0_ = (unsigned)(G * (w32 * prm.C0 + (w32 < prm.n_big ? w32 : prm.n_big)));
+    unsigned cb0_ = (unsigned)(GY * (w32 * prm.C0 + (w32 < prm.n_big ? w32 : prm.n_big)));
     if (prm.rk_n > 0) {   // shares by age rank (scalar selects: rk_n <= 4)
         int rr = w32 / prm.rk_wpr;
         rr = rr >= prm.rk_n ? prm.rk_n - 1 : rr;
@@ -271,7 +302,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         c0_ = (int)((pk >> (16 * rr)) & 0xffffu);
         const unsigned long long below = pk & ((1ull << (16 * rr)) - 1ull);      // the counts of the older ranks
         const unsigned used = (unsigned)(below & 0xffffu) + (unsigned)((below >> 16) & 0xffffu) + (unsigned)((below >> 32) & 0xffffu);
-        cb0_ = (used * (unsigned)prm.rk_wpr + (unsigned)((w32 - rr * prm.rk_wpr) * c0_)) * (unsigned)G;
+        cb0_ = (used * (unsigned)prm.rk_wpr + (unsigned)((w32 - rr * prm.rk_wpr) * c0_)) * (unsigned)GY;
     }
     const int C0 = __builtin_amdgcn_readfirstlane(c0_), logC = prm.logC, CQ = 1 << logC;
     unsigned cb0 = (unsigned)__builtin_amdgcn_readfirstlane((int)cb0_), cb1 = NOPAIR, cb2 = NOPAIR, cb3 = NOPAIR;   // chunk k in cb[k & 3]
@@ -287,6 +318,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         return 1 + ((i - C0) >> logC);
     };
     // pair at stream position i of lane group g (NOPAIR: none), and how many positions of its chunk follow it (left)
+    // (shared-y: the POSITION, the same for every lane group -- the callers map it to the group's pair)
     auto stream_pair_left = [&](int g, int i, int &left) __attribute__((always_inline)) -> unsigned {
         left = 0;
         if (i < 0) return NOPAIR;
@@ -295,7 +327,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         const int size = k == 0 ? C0 : CQ;
         left = size - 1 - off;
         const unsigned b = ring_at(k & 3);
-        const unsigned p = b + (unsigned)(g * size + off);
+        const unsigned p = b + (unsigned)((shy_a() > 0 ? 0 : g * size) + off);
         return (b >= P32 || p >= P32) ? NOPAIR : p;
     };
     auto stream_pair = [&](int g, int i) __attribute__((always_inline)) -> unsigned {      // wave-uniform arguments in the producers
@@ -314,7 +346,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             unsigned b = NOPAIR;
             if (prm.queue && t_end == 0x7fffffff) {
                 unsigned long long v = 0;
-                if (lane == 0) v = atomicAdd(prm.queue, (unsigned long long)(G * CQ));
+                if (lane == 0) v = atomicAdd(prm.queue, (unsigned long long)((shy_a() > 0 ? 1 : G) * CQ));
                 const unsigned long long q = (unsigned long long)prm.q_first +
                                              (((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
                                               (unsigned)__builtin_amdgcn_readfirstlane((int)v));
@@ -335,7 +367,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         }
     };
     const bool is_top = lam == 0;
-    const unsigned my_y = lds0 + (unsigned)grp * y_bytes;
+    const unsigned my_y = lds0 + (shy ? 0u : (unsigned)grp * y_bytes);
     const unsigned y_lim = my_y + y_bytes;
     const unsigned ring_bytes = FULLWAVE ? (unsigned)(((WAVE >> 3) + 2) * Y_SLAB_PITCH) : y_bytes;   // = y_bytes, as a literal when L = 64
     {
@@ -345,7 +377,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // lanes NUp apart start (different) pairs at the same macro-step: one x slab per such "lap" j = lam / NUp
     const int JMAX = (L + NUp - 1) / NUp;
     const unsigned my_x = lds0 + x_base0 + (unsigned)((grp * X_SLOTS * JMAX) * XSLAB + (lam / NUp) * XSLAB) +
-                          (unsigned)((lam & 7) * RC * XROW);
+                          (unsigned)((lam & (XW - 1)) * RC * XROW);
 
     // ---- producers (uniform control; per-lane source offsets) ------------------------------------------------
     // y slab s = virtual units [8s, 8s+8) of every lane group: dims k = lane/8, unit x = lane%8
@@ -372,7 +404,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     int y_pi = 0, y_u0 = 0, y_slot = 0, y_par = 0;   // next y slab: pair-in-group, first unit (NUp % 8 == 0: no straddling),
     auto issue_y = [&]() __attribute__((always_inline)) {                            // ring slot, parity of the virtual slab number
         ensure(y_pi);
-        for (int g = 0; g < G; ++g) {
+        const int gy = shy_a() > 0 ? 1 : G;
+        for (int g = 0; g < gy; ++g) {   // (shared-y: one ring, filled in the g = 0 form; position % B is the pair's b)
             const unsigned sp = stream_pair(g, y_pi);
             const int64_t p = sp == NOPAIR ? 0 : (int64_t)sp;   // past the end: fetch something valid, never consumed
             const int64_t b = split_b(p);
@@ -386,18 +419,26 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         y_u0 += 8;
         if (y_u0 == NUp) { y_u0 = 0; y_pi += 1; }
     };
-    // x slabs for the lanes that start a pair during macro-steps [t0, t0+8): lanes lam0 + j*NUp .. +7 start pair
-    // t0/NUp - j, rows (lam0 + j*NUp .. +7)*RC of its x
+    // x slabs for the lanes that start a pair during macro-steps [t0, t0+XW): lanes lam0 + j*NUp .. +XW-1 start pair
+    // t0/NUp - j, rows (lam0 + j*NUp .. +XW-1)*RC of its x
     int x_q0 = 0, x_lam0 = 0, x_slot = 0;   // next window: t0 / NUp, t0 % NUp, ring slot
     auto issue_x = [&]() __attribute__((always_inline)) {
         ensure(x_q0);
         for (int j = 0; j < JMAX; ++j) {
             const int lamj = x_lam0 + j * NUp, pi = x_q0 - j;
             if (lamj >= L) break;
+            // shared-y: position pi is row a = G (pi's position / B) + g for lane group g (no such row: fetch something valid, never
+            // stored) -- branch-free in the mode: a = gm a + gs g with (gm, gs, a_lim) = (G, 1, A) or (1, 0, "no limit")
+            const int sA = shy_a();
+            const int64_t gm = sA > 0 ? G : 1, gs = sA > 0 ? 1 : 0, a_lim = sA > 0 ? sA : 0x7fffffff;
             for (int g = 0; g < G; ++g) {
                 const unsigned sp = stream_pair(g, pi);
                 const int64_t p = sp == NOPAIR ? 0 : (int64_t)sp;
-                const int64_t a = split_a(p);
+                int64_t a = split_a(p);
+                if constexpr (!EDGES && !FULLWAVE) {
+                    a = a * gm + gs * g;
+                    if (a >= a_lim) a = 0;
+                }
                 const char *src = reinterpret_cast<const char *>(prm.dXr + (a * prm.Mrows + (int64_t)lamj * RC) * FD);
                 char *dst = lds + x_base0 + ((g * X_SLOTS + x_slot) * JMAX + j) * XSLAB;
 #pragma unroll
@@ -410,7 +451,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             }
         }
         x_slot = x_slot + 1 == X_SLOTS ? 0 : x_slot + 1;
-        x_lam0 += 8;
+        x_lam0 += XW;
         if (x_lam0 == NUp) { x_lam0 = 0; x_q0 += 1; }
     };
 
@@ -526,7 +567,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             lds_read_dims_issue(dyn, a_e, a_e ^ 128u);
         }
     };
-    unsigned x_rd_off = 0;   // ring slot the x rows of this 8-step window are read from: ((t >> 3) % X_SLOTS) * JMAX * XSLAB
+    unsigned x_rd_off = 0;   // ring slot the x rows of this XW-step window are read from: ((t / XW) % X_SLOTS) * JMAX * XSLAB
     static_assert(X_SLOTS == 2, "x_rd_off toggles between two slots");
     issue_y();
     issue_x();
@@ -698,8 +739,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         // a window boundary the rows are in the window whose DMA is waited for here.  Issuing the reads in the middle of the
         // step, under the sweep, was tried (MID): no faster, and the compiler copies the destination registers around.
         auto fetch_next = [&]() {
-            const bool turn = ((t + 1) & 7) == 0;   // the next step opens a y slab (for lane 0) and an x window: their DMA
-            if (__builtin_expect(turn, 0)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // was issued 8 steps ago
+            const bool turn = ((t + 1) & (XW - 1)) == 0;   // the next step opens an x window (and, every eighth step, a y slab for
+            if (__builtin_expect(turn, 0)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // lane 0): their DMA was issued XW (8) steps ago
             a_e += 16;
             if (((t + 1) & 7) == lam7) {   // next slab: the other parity, one slab less one row on, wrapping at the end of the ring
                 asm volatile("");          // (a real branch: if-converted, the update costs two more VALU instructions per step)
@@ -785,7 +826,12 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         if (__builtin_expect(CUR ? uk == my_uf : tm == c_out, 0)) {
             int pv = CUR ? psk : tq + c_kq + (tm + c_kr >= NUp ? 1 : 0);
             asm volatile("" : "+v"(pv));   // keeps the pair tests inside this (rarely taken) branch instead of in every step
-            const unsigned pair_u = lane_pair(pv);
+            unsigned pair_u = lane_pair(pv);
+            const int sA = shy_a();
+            if (sA > 0 && pair_u != NOPAIR) {   // position -> this lane group's pair: a = G (q / B) + grp, b = q % B, out index a B + b
+                const unsigned Bu = (unsigned)prm.B, qa = pair_u / Bu, a = qa * (unsigned)G + (unsigned)grp;
+                pair_u = a < (unsigned)sA ? a * Bu + (pair_u - qa * Bu) : NOPAIR;
+            }
             const int64_t pair_v = (int64_t)pair_u;
             if (pair_u != NOPAIR) {
                 double v = cand[0][0];
@@ -833,14 +879,14 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             }
         }
         if (CUR && !RBF) { uk = u; psk = ps; }
-        if (__builtin_expect(((t + 1) & 7) == 0, 0)) {
-            // everything issued 8 macro-steps ago has had a whole slab period to land (leaving this step's edge stores in
+        if (__builtin_expect(((t + 1) & (XW - 1)) == 0, 0)) {
+            // everything issued a window ago has had XW macro-steps to land (leaving this step's edge stores in
             // flight with a counted wait was measured: no gain, their cost is issue slots, not latency)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            issue_y();       // slab ((t + 1) >> 3) + 1
-            issue_x();       // window t + 9 .. t + 16
+            if (XW == 8 || ((t + 1) & 7) == 0) issue_y();       // slab ((t + 1) >> 3) + 1
+            issue_x();       // window t + 1 + XW .. t + 2 XW
             x_rd_off ^= (unsigned)(JMAX * XSLAB);
-            refresh_next();
+            if (XW == 8 || ((t + 1) & 7) == 0) refresh_next();
         }
         if (AHEAD && CUR) read_y();   // for macro-step t + 1
     }
@@ -866,8 +912,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
 
 // What the launcher has worked out before the kernel variant (and with it the register budget) is known
 struct FusedPlan {
-    int64_t P;
-    int G, NUp, L, lag;
+    int64_t P;          // stream positions (pairs; shared-y: ceil(A / G) B)
+    int G, NUp, L, lag; // G: lane groups with a stream position of their own (shared-y: 1)
     size_t lds_bytes;   // per wave
     int waves_per_cu;   // from LDS and the measured optimum; still to be capped by the variant's VGPR use
     int rcx;            // coarse rows per lane when not the strip kernels' own (0: Tile<DY>::RC)
@@ -1105,7 +1151,13 @@ int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B,
     const int G = WAVE / L;
     const int JMAX = (L + NUp - 1) / NUp;
     const int nd = (!g.naive && sizeof(TO) == 8 && D <= 4) ? 4 : 8;   // the variant launch_fused_e picks
-    const size_t lds_bytes = (size_t)G * (((L >> 3) + 2) * y_slab_pitch(nd) + X_SLOTS * JMAX * RC * 8 * x_row_bytes(nd));   // (a multiple of 256: the y reads rely on 256-byte aligned slices)
+    // shared-y pair order (FusedParams::shy_A): a plain Gram without edges and two or more lane groups per wave -- one y ring per wave
+    const bool shy = B > 0 && tri == 0 && !strip_edges && G >= 2 && A > 0 && A <= 0x7fffffff && g.P == A * B;
+    const int GY = shy ? 1 : G;
+    const int xw = x_window(KIND, nd, RC, strip_edges != nullptr);
+    const size_t lds_bytes = (size_t)GY * (((L >> 3) + 2) * y_slab_pitch(nd)) +
+                             (size_t)G * (X_SLOTS * JMAX * RC * xw * x_row_bytes(nd));   // (a multiple of 256: the y reads rely on 256-byte aligned slices)
+    const int64_t n_pos = shy ? (A + G - 1) / G * B : g.P;      // stream positions: pairs, or (shared-y) pairs of one lane group
     if (lds_bytes > 160 * 1024) return SK_ERR_UNSUPPORTED;
 
     int waves_per_cu = (int)((160 * 1024) / lds_bytes);
@@ -1121,10 +1173,10 @@ int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B,
     if (wpc_env > 0) waves_per_cu = waves_per_cu < wpc_env ? waves_per_cu : wpc_env;
     else if (waves_per_cu > 4) waves_per_cu &= ~3;   // whole four-wave workgroups
     if (waves_per_cu < 1) waves_per_cu = 1;
-    const FusedPlan pl{g.P, G, NUp, L, KIND == 1 ? 2 : 0, lds_bytes, waves_per_cu, rcx};
+    const FusedPlan pl{n_pos, GY, NUp, L, KIND == 1 ? 2 : 0, lds_bytes, waves_per_cu, rcx};
 
     FusedParams prm;
-    prm.dXr = dXr; prm.dYt = dYt; prm.out = out; prm.edges = strip_edges; prm.P = g.P; prm.B = B;
+    prm.dXr = dXr; prm.dYt = dYt; prm.out = out; prm.edges = strip_edges; prm.P = n_pos; prm.B = B;
     prm.Mrows = Mrows; prm.Ncp = Ncp; prm.Mc = g.Mc; prm.Nc = g.Nc; prm.NUp = NUp; prm.logL = logL;
     prm.inv_sigma = inv_sigma;
     prm.dims = D;
@@ -1144,7 +1196,7 @@ int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B,
     prm.lam_f = ((g.Mc - 1) / RC) % L;
     prm.sel_f = ((g.Mc - 1) % RC) * 2 + (g.Nc - 1) % 2;
     prm.naive = g.naive;
-    (void)A;
+    prm.shy_A = shy ? (int)A : 0;
     switch (DY) {
         case 0: return launch_fused_dy<TO, 0, KIND>(prm, pl, s);
         case 1: return launch_fused_dy<TO, 1, KIND>(prm, pl, s);
