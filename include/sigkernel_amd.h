@@ -105,6 +105,11 @@ const char *sk_cost_note(int which);
 #define SK_OP_ADJOINT 1
 #define SK_OP_ADJOINT_SYM 2   /* compute_Gram(X, X, sym=True) with a gradient (sigkernel.py:404-416 on the symmetric call): SK_ROUTE_FUSED =
                                  the TRIANGLE through sk_rbf_adjoint_fused_f64 with the second-argument sums; else all pairs */
+#define SK_OP_PREFIX 3        /* the grid of prefix kernels k_sig(x[:m+1], y[:n+1]) (compute_Gram_prefixes / compute_kernel_prefixes):
+                                 SK_ROUTE_FUSED = sk_solve_prefix_linear_* / _rbf_* (one band per pair, path dim <= 8, dyadic <= 2: rows <= 64 RC,
+                                 RC = 4 / 2 / 1 at dyadic 0 / 1 / 2, rows = M - 1 linear, M rbf; rbf at dyadic 0: two rows per lane, M <= 128);
+                                 SK_ROUTE_STREAM = sk_static_increments_* + sk_solve_fwd_* with out_grid, sliced.  Never a swapped route:
+                                 the grid of k(y, x) is the transpose. */
 #define SK_ROUTE_STREAM 0
 #define SK_ROUTE_FUSED 1
 #define SK_ROUTE_FUSED_MB 2
@@ -398,6 +403,27 @@ int sk_solve_fwd_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t 
                          int dyadic, int scheme, double inv_sigma, double *out_final, void *queue, void *stream);
 int sk_solve_fwd_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                          int dyadic, int scheme, double inv_sigma, float *out_final, void *queue, void *stream);
+/* The PREFIX GRID of every pair with the static kernel fused in (csrc/sk_wave_prefix.hip): the sweep of sk_solve_fwd_linear_* /
+ * sk_solve_fwd_rbf_* that stores every coarse node instead of the last one,
+ *     out[p ldo + m (Nc + 1) + n] = k_sig(x[:m+1], y[:n+1]),   1 <= m <= Mc, 0 <= n <= Nc
+ * (node (m << dyadic, n << dyadic) of the reference's grid; column n = 0 is exactly 1).  Row m = 0 of every grid -- the ones of the
+ * one-point prefix of x, Nc + 1 contiguous elements -- is NOT written: it is the caller's fill.  Nothing outside a pair's
+ * (Mc + 1) x (Nc + 1) elements is written.  Where Nc + 1 and ldo are even and out is aligned to two elements the nodes are stored two
+ * columns at a time (SK_PREFIX_STORE=1|2|3 in the environment selects a store scheme for measurements; the values are the same).
+ * Node (Mc, Nc) is bit for bit the out_final of sk_solve_fwd_linear_* / sk_solve_fwd_rbf_* on the same staged arrays.
+ *   dXr / dYt (Xr / Yt), A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, queue: as sk_solve_fwd_linear_* / sk_solve_fwd_rbf_*;
+ *   out: pair p's grid starts at out + p ldo, rows are dense (pitch Nc + 1); ldo >= (Mc + 1) (Nc + 1) elements, so that a caller
+ *        can write into a slice of a larger tensor; _f32: the sweep is fp64, the nodes are stored as float.
+ * SK_ERR_UNSUPPORTED outside sk_route_query(SK_OP_PREFIX, ...) == SK_ROUTE_FUSED: use sk_static_increments_* + sk_solve_fwd_*
+ * with out_grid. */
+int sk_solve_prefix_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                               int dyadic, int scheme, double *out, int64_t ldo, void *queue, void *stream);
+int sk_solve_prefix_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                               int dyadic, int scheme, float *out, int64_t ldo, void *queue, void *stream);
+int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                            int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream);
+int sk_solve_prefix_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                            int dyadic, int scheme, double inv_sigma, float *out, int64_t ldo, void *queue, void *stream);
 /* Symmetric Gram matrix of ONE path batch with the fused kernels above: only the A (A + 1) / 2 pairs on and above the diagonal are
  * solved (what the reference's CPU solver does for sym=True, cython_backend.pyx:74-97; its GPU path ignores `sym`), in ONE launch,
  * and each value is written to out[a][b] and out[b][a]: out [A][A] is exactly symmetric.  dXr / dXt (Xr / Xt): the row-major and

@@ -20,6 +20,8 @@ the same with its SK_* knobs, sk_abi.hip):
     SK_NO_STREAM         memory first: LinearKernel / RBFKernel calls of path dim <= 16, dyadic <= 2 NEVER hold increments in HBM, also
                          on short paths, where the multi-band kernels mostly sweep padding and the (row-tiled) streaming route is the
                          faster default (sk_route_query with SK_ROUTE_NO_STREAM)
+    SK_NO_FUSED_PREFIX   compute_Gram_prefixes / compute_kernel_prefixes never through the fused prefix kernel: increments in HBM, the
+                         streaming solver's full grid, sliced (what every shape outside that kernel's scope takes anyway)
 
 A running process flips them through the attributes of `sigkernel_amd.routes` (tests: monkeypatch.setattr), or calls
 `routes.reload()` after changing the environment."""
@@ -27,7 +29,8 @@ import os
 
 _ENV = {"no_fused_rbf": "SK_NO_FUSED_RBF", "no_fused_mb": "SK_NO_FUSED_MB", "no_fused_adjoint": "SK_NO_FUSED_ADJOINT",
         "no_fused_deriv": "SK_NO_FUSED_DERIV", "no_stream": "SK_NO_STREAM", "no_mmd_streams": "SK_NO_MMD_STREAMS",
-        "no_merged_loss": "SK_NO_MERGED_LOSS", "no_loss_launch": "SK_NO_LOSS_LAUNCH", "no_adjoint_swap": "SK_NO_ADJOINT_SWAP"}
+        "no_merged_loss": "SK_NO_MERGED_LOSS", "no_loss_launch": "SK_NO_LOSS_LAUNCH", "no_adjoint_swap": "SK_NO_ADJOINT_SWAP",
+        "no_fused_prefix": "SK_NO_FUSED_PREFIX"}
 
 
 class Routes:

@@ -137,6 +137,19 @@ int solve_fwd_sym(int kind, const double *Xr, const double *Xt, const int *pair_
     return launch_fwd_fused_rbf<TO>(Xr, Xt, A, A, Mrows, Ncp, D, g, inv_sigma, out, nullptr, queue, (hipStream_t)stream, 1);
 }
 
+// the prefix grid of every pair (sk_wave_prefix.hip); argument checks before any HIP call
+template <typename TO>
+int solve_prefix(int kind, const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
+                 int scheme, double inv_sigma, TO *out, int64_t ldo, void *queue, void *stream) {
+    if (D < 1 || !Xr || !Yt || !out || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
+    if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
+    if (kind == 1 && (!(inv_sigma > 0.0) || !(inv_sigma < 1e300))) return SK_ERR_BAD_ARG;
+    if (ldo < ((int64_t)Mc + 1) * ((int64_t)Nc + 1)) return SK_ERR_BAD_ARG;
+    if (A == 0) return SK_OK;
+    const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
+    return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, ldo, queue, (hipStream_t)stream);
+}
+
 }  // namespace
 
 // ---- the one place that reads the environment: SK_* tuning knobs, parsed when the library is loaded ------------------------
@@ -171,6 +184,7 @@ Knobs parse_knobs() {
     k.fusedmb_wpc = knob_int("SK_FUSEDMB_WPC"); k.fusedmb_wpb = knob_int("SK_FUSEDMB_WPB"); k.fusedmb_q_static = knob_int("SK_FUSEDMB_Q_STATIC");
     k.fusedmb_split = getenv("SK_FUSEDMB_SPLIT") ? knob_int("SK_FUSEDMB_SPLIT") : 1;
     k.fusedmb_lead = knob_int("SK_FUSEDMB_LEAD");
+    k.prefix_store = knob_int("SK_PREFIX_STORE");
     k.rank_w = knob_shares("SK_RANK_W"); k.wave_rank_w = knob_shares("SK_WAVE_RANK_W"); k.adj_rank_w = knob_shares("SK_ADJ_RANK_W");
     k.adjf_rank_w = knob_shares("SK_ADJF_RANK_W"); k.adjr_rank_w = knob_shares("SK_ADJR_RANK_W");
     k.deriv_rank_w = knob_shares("SK_DERIV_RANK_W"); k.fused_rank_w = knob_shares("SK_FUSED_RANK_W");
@@ -414,6 +428,23 @@ int sk_solve_fwd_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t 
     if (A == 0) return SK_OK;
     const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
     return launch_fwd_fused_rbf<float>(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out_final, nullptr, queue, (hipStream_t)stream);
+}
+
+int sk_solve_prefix_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                               int dyadic, int scheme, double *out, int64_t ldo, void *queue, void *stream) {
+    return solve_prefix<double>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, out, ldo, queue, stream);
+}
+int sk_solve_prefix_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                               int dyadic, int scheme, float *out, int64_t ldo, void *queue, void *stream) {
+    return solve_prefix<float>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, out, ldo, queue, stream);
+}
+int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                            int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream) {
+    return solve_prefix<double>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, queue, stream);
+}
+int sk_solve_prefix_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                            int dyadic, int scheme, double inv_sigma, float *out, int64_t ldo, void *queue, void *stream) {
+    return solve_prefix<float>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, queue, stream);
 }
 
 size_t sk_solve_fwd_static_workspace_bytes(int kind, int64_t P, int Mc, int Nc, int dyadic, int D) {

@@ -20,6 +20,7 @@ struct Knobs {
     int deriv_wpc, deriv_wpb;
     int fused_wpc, fused_wpb, fused_q_static, fused_mid;
     int fusedmb_wpc, fusedmb_wpb, fusedmb_q_static, fusedmb_split, fusedmb_lead;
+    int prefix_store;   // SK_PREFIX_STORE: store scheme of the prefix kernel (sk_wave_prefix.hip), 0 = its default
     RankW rank_w, wave_rank_w, adj_rank_w, adjf_rank_w, adjr_rank_w, deriv_rank_w, fused_rank_w, fusedmb_rank_w;
 };
 const Knobs &knobs();                      // sk_abi.hip
@@ -174,6 +175,13 @@ int launch_fwd_fused_rbf(const double *Xr, const double *Yt, int64_t A, int64_t 
                          double inv_sigma, TO *out, double *strip_edges, void *queue, hipStream_t s, int tri = 0, const int64_t *loss = nullptr);
 // (tri = 2, loss = {tri_n, tri_off}: the LOSS layout -- both staged arrays hold one batch Z of B paths; A B rectangle pairs (rows
 // Z[0 .. A)), which keep their edges, then the strict upper triangle of Z[tri_off .. tri_off + tri_n), which does not; out [P] linear)
+
+// ---- sk_wave_prefix.hip: the one-band fused forward that stores every coarse node (prefix kernels) ----
+// kind 0: dXr / dYt as launch_fwd_fused_linear; kind 1: as launch_fwd_fused_rbf.  out: pair p's (Mc + 1) x (Nc + 1) grid at out + p ldo.
+template <typename TO>
+int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
+                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s);
+bool prefix_in_scope(int kind, int D, int Mc, int dyadic);   // the kernel's scope = the SK_OP_PREFIX rule of sk_route_query
 
 // ---- sk_loss.hip: the glue of the loss wrappers (compute_mmd / scoring rules) as single launches ----
 template <typename T>

@@ -24,6 +24,10 @@
 //     FUSED_SWAP rbf, dim <= 4, fp64, Gram calls: the one-band adjoint on (y, x) with the second-argument sums when only the SECOND paths
 //                fit its lanes (64 points at d = 1..2, 128 at d = 0): d k(x, y) / dx = d2 k(y, x)
 //     FUSED_MB   dim <= 16, d = 0..2, any M, N (csrc/sk_wave_adj_fused_mb.hip; rbf at d = 0: two coarse rows per lane); never swapped
+//   prefix grids (SK_OP_PREFIX: k_sig of every pair of prefixes, forward only)
+//     FUSED      one band per pair, path dim <= 8 (csrc/sk_wave_prefix.hip): rows <= 64 RC as the forward's FUSED; rbf at d = 0 always
+//                sweeps two rows per lane there (rows <= 128 whatever the dim / stencil / dtype: 8 staged dims, no four-dim variants)
+//     STREAM     everything else: increments in HBM + the full grid of sk_solve_fwd_*, sliced, tiled by the host to its budget
 //   STREAM       everything else (dim > 16, d > 2, other static kernels): static kernel -> increments in HBM -> sk_solve_fwd_* /
 //                sk_static_increments -> sk_solve_adj -> sk_static_adjoint (or the generic vector-Jacobian route)
 //
@@ -167,6 +171,10 @@ int route_query(int op, int kind, int D, int M, int N, int d, int naive, int ele
         if (may_stream && prefer_stream(Mc, Nc, eff, kind == 1 && D > 8 && elem_size == 8)) return SK_ROUTE_STREAM;
         return swap ? SK_ROUTE_FUSED_MB_SWAP : SK_ROUTE_FUSED_MB;
     }
+    if (op == SK_OP_PREFIX)
+        // the prefix grid: the one-band kernel that stores every coarse node where a pair fits its lanes, else increments + the grid
+        // of the streaming solver, sliced (no multi-band form, and no swapped one: the grid of k(y, x) is the transpose)
+        return prefix_in_scope(kind, D, Mc, d) ? SK_ROUTE_FUSED : SK_ROUTE_STREAM;
     if (op == SK_OP_ADJOINT_SYM) {
         // compute_Gram(X, X, sym=True) with a gradient: FUSED = the triangle through the one-band rbf adjoint with the second-argument
         // sums (a pair above the diagonal also stands for its mirror image); anything else = all pairs / the caller's other routes.

@@ -988,6 +988,34 @@ def _loss_launch_ok(be, static_kernel, Xd, Yd, dyadic, naive, need_grad, with_yy
 _LOSS_LAUNCH_FREE_BYTES = None    # "loss_launch_free_bytes": below this the one-launch loss route does not ask the device for its free memory
 
 
+def _prefix_grid(be, static_kernel, Xd, Yd, dyadic, naive, gram, workspace_bytes):
+    """out[..., m, n] = k_sig(x[:m+1], y[:n+1]) for every pair: (A, B, M, N) for gram, (A, M, N) paired.  The fused prefix kernel where the
+    library says so (sk_route_query(SK_OP_PREFIX): no transient memory), else the existing pieces -- increments, the streaming
+    solver's full grid, its coarse nodes -- over row tiles that keep increments + fine grid within the budget."""
+    A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
+    B = Yd.shape[0] if gram else 1
+    shape = (A, Yd.shape[0], M, N) if gram else (A, M, N)
+    if M < 2 or N < 2 or A == 0 or B == 0:      # one-point paths: every prefix kernel is 1; empty batches: empty results
+        return torch.ones(shape, dtype=Xd.dtype, device=Xd.device)
+    fused = _fused_static(static_kernel, gram)
+    if fused is not None and hasattr(be, "solve_prefix_fused") and not routes.no_fused_prefix and \
+            not (fused[0] == 1 and routes.no_fused_rbf):
+        # (the back-end asks sk_route_query(SK_OP_PREFIX) and returns None where the library names the streamed route)
+        out = be.solve_prefix_fused(fused[0], fused[1], Xd.contiguous(), Yd.contiguous(), dyadic, naive, gram)
+        if out is not None:
+            return out
+    out = torch.empty(shape, dtype=Xd.dtype, device=Xd.device)
+    r = 1 << dyadic
+    # per row of the tile: the increments (padded rows) and the fine grid the streaming solver writes
+    per_row = B * ((M - 1) * (N + 16) + (((M - 1) << dyadic) + 1) * (((N - 1) << dyadic) + 1)) * Xd.element_size()
+    for a0, a1 in _tiles(A, per_row, _budget(Xd.device, workspace_bytes)):
+        inc = _increments(be, static_kernel, Xd[a0:a1], Yd if gram else Yd[a0:a1], gram=gram)
+        _, grid, _ = be.solve_fwd(inc, dyadic, naive, want_grid=True)
+        out[a0:a1] = grid[..., ::r, ::r]
+        del inc, grid
+    return out
+
+
 class _NoGradCtx:
     """What the autograd Functions' forward needs of a context when no gradient can be asked for: the call skips
     torch.autograd.Function.apply (a quarter of the host time of a C1-sized call) and returns the same values."""
@@ -1042,6 +1070,34 @@ class SigKernel:
         if not _wants_grad(X, Y):
             return _SigKernel.forward(_NoGradCtx(), X, Y, self.static_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes)
         return _SigKernel.apply(X, Y, self.static_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes)
+
+    def _prefixes(self, X, Y, gram, max_batch):
+        f = self._on_features()
+        if f is not None:
+            return f[0]._prefixes(f[1](X), f[1](Y), gram, max_batch)
+        _check_inputs(X, Y, paired=not gram)
+        if self.process_group is not None:
+            raise NotImplementedError("prefix grids are not sharded over a process group: every rank would have to gather an "
+                                      "(A, B, M, N) tensor; call it on a SigKernel without process_group")
+        if _wants_grad(X, Y):
+            raise NotImplementedError("compute_Gram_prefixes / compute_kernel_prefixes are forward only: the prefix grid has no "
+                                      "gradient.  Call them under torch.no_grad() or on detached paths")
+        return _prefix_grid(_lib.get_backend(), self.static_kernel, X.detach(), Y.detach(), self.dyadic_order, self._naive_solver, gram,
+                            self.workspace_bytes)
+
+    def compute_Gram_prefixes(self, X, Y, max_batch=100):
+        """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim) -> (batch_X, batch_Y, len_x, len_y): out[a, b, m, n] =
+        k(X^a restricted to its first m + 1 points, Y^b restricted to its first n + 1 points) -- the coarse nodes of the PDE grid the
+        solver sweeps anyway (node (m << dyadic_order, n << dyadic_order) of the reference's solver grids), all in one sweep.  Row
+        m = 0 and column n = 0 are exactly 1; out[..., -1, -1] is ``compute_Gram(X, Y)``.  Forward only: no ``grad_fn``, and paths that
+        require grad raise outside ``torch.no_grad()``.  Batches of unequal length: pad every path at its end with anything and gather
+        node (len_a - 1, len_b - 1).  ``max_batch`` is accepted and ignored, as elsewhere."""
+        return self._prefixes(X, Y, True, max_batch)
+
+    def compute_kernel_prefixes(self, X, Y, max_batch=100):
+        """X (batch, len_x, dim), Y (batch, len_y, dim) -> (batch, len_x, len_y): the paired form of ``compute_Gram_prefixes``;
+        out[..., -1, -1] is ``compute_kernel(X, Y)``."""
+        return self._prefixes(X, Y, False, max_batch)
 
     def compute_kernel_and_derivatives_Gram(self, X, Y, gamma, max_batch=100):
         """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim), gamma (batch_X, len_x, dim) -> three (batch_X, batch_Y)

@@ -180,6 +180,13 @@ def gated(g, be):
         sk = sigkernel_amd.SigKernel(RBF(0.8), d)
         X, Y = walk(g, 3, 256, D, f64), walk(g, 4, 200, D, f64)
         sk.compute_Gram(X, Y); sk.compute_kernel(X, walk(g, 3, 200, D, f64))
+    # prefix grids: every instance of the fused prefix kernel (kind x dyadic order x stencil x output dtype), Gram and paired, and the
+    # route everything else takes (increments + the streaming solver's grid)
+    for kname, d, naive, dt in itertools.product(("linear", "rbf"), (0, 1, 2), (False, True), (f64, f32)):
+        sk = sigkernel_amd.SigKernel(RBF(0.9) if kname == "rbf" else LIN(), d, _naive_solver=naive)
+        X, Y = walk(g, 3, 33, 5, dt), walk(g, 4, 20, 5, dt)
+        sk.compute_Gram_prefixes(X, Y); sk.compute_kernel_prefixes(X, Y[:3])
+    sigkernel_amd.SigKernel(LIN(), 1).compute_Gram_prefixes(walk(g, 3, 20, 12, f64), walk(g, 4, 17, 12, f64))
     # an exported entry point the host layer has no call of any more (the one-launch loss route carries its weights from the forward)
     be.loss_weights(5, 7, torch.ones((), dtype=f64).cuda(), torch.device("cuda"))
 
