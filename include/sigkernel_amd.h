@@ -110,6 +110,11 @@ const char *sk_cost_note(int which);
                                  RC = 4 / 2 / 1 at dyadic 0 / 1 / 2, rows = M - 1 linear, M rbf; rbf at dyadic 0: two rows per lane, M <= 128);
                                  SK_ROUTE_STREAM = sk_static_increments_* + sk_solve_fwd_* with out_grid, sliced.  Never a swapped route:
                                  the grid of k(y, x) is the transpose. */
+#define SK_OP_TRUNCATED 4     /* truncated_sig_kernel (transformers.py:201-236): kind = order (< 1: num_levels), dyadic = num_levels, M / N =
+                                 STEPS per path of the two batches.  SK_ROUTE_FUSED = sk_truncated_gram_*: path dim <= 16, num_levels <= 8,
+                                 order 1 with M <= 128 (two rows per lane) or order <= 4 with M <= 64 (one), and 8 (dim <= 8; else 16) x
+                                 ceil16(N) <= 2048 (the y block of a wave in 16 KB of LDS); SK_ROUTE_FUSED_SWAP = the same on (y, x), the
+                                 result transposed; SK_ROUTE_STREAM = the host layer's torch restatement (differentiable). */
 #define SK_ROUTE_STREAM 0
 #define SK_ROUTE_FUSED 1
 #define SK_ROUTE_FUSED_MB 2
@@ -424,6 +429,17 @@ int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream);
 int sk_solve_prefix_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, float *out, int64_t ldo, void *queue, void *stream);
+/* The truncated signature kernel of Kiraly and Oberhauser as ONE sweep per pair (replaces truncated_sig_kernel, transformers.py:201-236:
+ * six-dimensional numpy arrays shifted by a spline filter): out[a][b] = sigma[0] + sum_{m = 1 .. num_levels} sigma[m] * (sum of level m's
+ * planes over the step grid of (x_a, y_b)); the rows of the paths are used as STEPS (no differencing); order = num_levels (or < 1) is the
+ * signature kernel truncated at num_levels, smaller orders are the reference's lower-order approximations.
+ *   Xr [A][Mrows][fd] / Yt [B][fd][Ncp]: the path POINTS staged by sk_prep_pair_* (diff = 0, scales 1), fd = 8 for D <= 8 else 16,
+ *   Mrows >= M, Ncp >= N;  sigma: num_levels + 1 doubles in HOST memory;  out [A][B]; _f32: the sweep is fp64, the result is stored as float.
+ * Forward only.  SK_ERR_UNSUPPORTED outside sk_route_query(SK_OP_TRUNCATED, order, D, M, N, num_levels, ...) == SK_ROUTE_FUSED. */
+int sk_truncated_gram_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, int order, const double *sigma, double *out, void *stream);
+int sk_truncated_gram_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, int order, const double *sigma, float *out, void *stream);
 /* Symmetric Gram matrix of ONE path batch with the fused kernels above: only the A (A + 1) / 2 pairs on and above the diagonal are
  * solved (what the reference's CPU solver does for sym=True, cython_backend.pyx:74-97; its GPU path ignores `sym`), in ONE launch,
  * and each value is written to out[a][b] and out[b][a]: out [A][A] is exactly symmetric.  dXr / dXt (Xr / Xt): the row-major and

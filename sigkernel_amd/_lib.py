@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libsigkernel_amd.so")
 
 SK_OK = 0
 # sk_route_query: operations and answers (include/sigkernel_amd.h)
-OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX = 0, 1, 2, 3
+OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED = 0, 1, 2, 3, 4
 ROUTE_STREAM, ROUTE_FUSED, ROUTE_FUSED_MB, ROUTE_FUSED_MB_SWAP, ROUTE_FUSED_SWAP = 0, 1, 2, 3, 4
 ROUTE_NO_STREAM = 1
 ROUTE_NO_SWAP = 2
@@ -72,6 +72,8 @@ SIGNATURES = {
     "sk_solve_prefix_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _i64, _vp, _vp]),
+    "sk_truncated_gram_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "sk_truncated_gram_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_prep_pair_f64": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_prep_pair_f32": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_solve_fwd_static_workspace_bytes": (_sz, [_int, _i64, _int, _int, _int, _int]),
@@ -569,6 +571,17 @@ class HipBackend:
         _check(rc, "sk_solve_prefix")
         out[..., 0, :] = 1      # the one-point prefix of x: the kernel stores rows m >= 1 (with their column 0)
         return out
+
+    def truncated_gram(self, X, Y, num_levels, sigma, order):
+        """The truncated signature kernel's (A, B) matrix in one sweep per pair (sk_truncated_gram_*, csrc/sk_truncated.hip): X (A, M, D) /
+        Y (B, N, D) hold steps, sigma num_levels + 1 host values.  None outside the kernel's scope (sk_route_query(SK_OP_TRUNCATED) !=
+        FUSED) -- the caller takes the torch restatement (truncated.py)."""
+        from . import truncated
+        _dev(X, "X")
+        _dev(Y, "Y")
+        if truncated.truncated_route(X.shape[2], X.shape[1], Y.shape[1], num_levels, order, X.element_size()) != ROUTE_FUSED:
+            return None
+        return truncated._truncated_hip(X, Y, int(num_levels), [float(v) for v in sigma], int(order))
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):
         """The loss wrappers' forward in THREE launches (csrc/sk_loss.hip): [X; Y] staged in both layouts straight from the two

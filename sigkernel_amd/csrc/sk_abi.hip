@@ -150,6 +150,16 @@ int solve_prefix(int kind, const double *Xr, const double *Yt, int64_t A, int64_
     return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, ldo, queue, (hipStream_t)stream);
 }
 
+// the truncated signature kernel's Gram matrix (sk_truncated.hip); argument checks before any HIP call
+template <typename TO>
+int truncated_gram(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
+                   int order, const double *sigma, TO *out, void *stream) {
+    if (D < 1 || !Xr || !Yt || !out || !sigma || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D)
+        return SK_ERR_BAD_ARG;
+    if (A == 0 || B == 0) return SK_OK;
+    return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream);
+}
+
 }  // namespace
 
 // ---- the one place that reads the environment: SK_* tuning knobs, parsed when the library is loaded ------------------------
@@ -437,6 +447,14 @@ int sk_solve_prefix_linear_f64(const double *dXr, const double *dYt, int64_t A, 
 int sk_solve_prefix_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                                int dyadic, int scheme, float *out, int64_t ldo, void *queue, void *stream) {
     return solve_prefix<float>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, out, ldo, queue, stream);
+}
+int sk_truncated_gram_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, int order, const double *sigma, double *out, void *stream) {
+    return truncated_gram<double>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
+}
+int sk_truncated_gram_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, int order, const double *sigma, float *out, void *stream) {
+    return truncated_gram<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
 }
 int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream) {

@@ -65,10 +65,10 @@ __global__ __launch_bounds__(TPB) void k_increments_adjoint(const T *__restrict_
 // (1/eps^2)*G2), each is 4-corner differenced, and the differences are added left to right.  The sums cancel
 // ~1/eps^2 = 1e8 of magnitude, so the order matters at the 1e-8 level: no FMA contraction here.
 template <typename T>
-__global__ __launch_bounds__(TPB) void k_deriv_increments(const T *__restrict__ G0, const T *__restrict__ G1,
-                                                          const T *__restrict__ G2, T c1, T c2, T c3, int M, int N,
-                                                          int strips, T *__restrict__ inc, T *__restrict__ inc_d,
-                                                          T *__restrict__ inc_dd, int64_t ld) {
+__device__ __forceinline__ void deriv_increments_strip(const T *__restrict__ G0, const T *__restrict__ G1,
+                                                       const T *__restrict__ G2, T c1, T c2, T c3, int M, int N,
+                                                       int strips, T *__restrict__ inc, T *__restrict__ inc_d,
+                                                       T *__restrict__ inc_dd, int64_t ld) {
 #pragma clang fp contract(off)
     const int Mc = M - 1, Nc = N - 1;
     const int64_t p = blockIdx.x / strips;
@@ -111,6 +111,19 @@ __global__ __launch_bounds__(TPB) void k_deriv_increments(const T *__restrict__ 
     }
 }
 
+// ONE instance for both precisions: the dtype is a wave-uniform launch-time value, and each precision runs, in its own arithmetic, the
+// code it ran as an instance of its own (the scalars arrive as doubles that hold the values already rounded to T).
+__global__ __launch_bounds__(TPB) void k_deriv_increments(int f32, const void *G0, const void *G1, const void *G2, double c1, double c2,
+                                                          double c3, int M, int N, int strips, void *inc, void *inc_d, void *inc_dd,
+                                                          int64_t ld) {
+    if (f32)
+        deriv_increments_strip<float>((const float *)G0, (const float *)G1, (const float *)G2, (float)c1, (float)c2, (float)c3, M, N, strips,
+                                      (float *)inc, (float *)inc_d, (float *)inc_dd, ld);
+    else
+        deriv_increments_strip<double>((const double *)G0, (const double *)G1, (const double *)G2, c1, c2, c3, M, N, strips, (double *)inc,
+                                       (double *)inc_d, (double *)inc_dd, ld);
+}
+
 }  // namespace
 
 template <typename T>
@@ -145,8 +158,8 @@ int launch_deriv_increments(const T *G0, const T *G1, const T *G2, double eps, i
     if (blocks > 0x7fffffffLL) return SK_ERR_UNSUPPORTED;
     // the python scalars of sigkernel.py:529-539, rounded to T when they meet the tensor like torch does
     const T c1 = (T)(1. / eps), c2 = (T)(2. / eps), c3 = (T)(1. / (eps * eps));
-    SK_LAUNCH(k_deriv_increments<T>, dim3((unsigned)blocks), dim3(TPB), 0, s, G0, G1, G2, c1, c2, c3, M, N, strips,
-                       inc, inc_d, inc_dd, ld);
+    SK_LAUNCH(k_deriv_increments, dim3((unsigned)blocks), dim3(TPB), 0, s, (int)(sizeof(T) == 4), (const void *)G0, (const void *)G1,
+              (const void *)G2, (double)c1, (double)c2, (double)c3, M, N, strips, (void *)inc, (void *)inc_d, (void *)inc_dd, ld);
     return check_launch();
 }
 

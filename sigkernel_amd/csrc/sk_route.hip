@@ -152,6 +152,15 @@ double cost_by_name(const char *name) { return cost(name); }
 
 int route_query(int op, int kind, int D, int M, int N, int d, int naive, int elem_size, int flags) {
     const bool may_stream = !(flags & SK_ROUTE_NO_STREAM);
+    if (op == SK_OP_TRUNCATED) {
+        // truncated_sig_kernel: kind = order (< 1: the level count), d = num_levels, M / N = STEPS of the two batches.  FUSED = k_trunc_sig
+        // (sk_truncated.hip: truncated_in_scope is the rule), FUSED_SWAP = the same kernel on (y, x), transposed (the recursion is symmetric
+        // under swapping the batches and the plane indices); STREAM = the host layer's differentiable torch restatement.
+        if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
+        if (truncated_in_scope(D, M, N, d, kind)) return SK_ROUTE_FUSED;
+        if (!(flags & SK_ROUTE_NO_SWAP) && truncated_in_scope(D, N, M, d, kind)) return SK_ROUTE_FUSED_SWAP;
+        return SK_ROUTE_STREAM;
+    }
     if ((kind != 0 && kind != 1) || D < 1 || D > 16 || M < 2 || N < 2 || d < 0 || d > 2) return SK_ROUTE_STREAM;
     if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
     const int Mc = M - 1, Nc = N - 1;

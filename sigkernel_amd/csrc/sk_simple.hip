@@ -92,11 +92,10 @@ __global__ __launch_bounds__(WAVE) void k_adj_rescue(const T *__restrict__ inc_c
 // LDS), every cell in the operand order of sigkernel_derivatives_Gram_cuda (cuda_backend.py:206-220), so the
 // results are bit-identical to oracle/sigkernel_oracle.c:sk_oracle_solve_deriv_coarse.
 template <typename T>
-__global__ __launch_bounds__(WAVE) void k_deriv_simple(const T *__restrict__ inc0, const T *__restrict__ inc1,
-                                                       const T *__restrict__ inc2, int64_t ld, int64_t P, int Mc, int Nc,
-                                                       int d, T *__restrict__ out_k, T *__restrict__ out_kd,
-                                                       T *__restrict__ out_kdd) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
+__device__ __forceinline__ void deriv_simple_sweep(double *lds, const T *__restrict__ inc0, const T *__restrict__ inc1,
+                                                   const T *__restrict__ inc2, int64_t ld, int64_t P, int Mc, int Nc,
+                                                   int d, T *__restrict__ out_k, T *__restrict__ out_kd,
+                                                   T *__restrict__ out_kdd) {
     const int lane = threadIdx.x;
     const int MM = Mc << d, NN = Nc << d;
     const double rs = 1.0 / (double)(1 << d);
@@ -144,6 +143,19 @@ __global__ __launch_bounds__(WAVE) void k_deriv_simple(const T *__restrict__ inc
             }
         }
     }
+}
+
+// ONE instance for both precisions: the dtype of the increments and of the three outputs is a wave-uniform launch-time value (the
+// sweep itself is fp64 either way, and each precision runs the code it ran as an instance of its own).
+__global__ __launch_bounds__(WAVE) void k_deriv_simple(int f32, const void *inc0, const void *inc1, const void *inc2, int64_t ld, int64_t P,
+                                                       int Mc, int Nc, int d, void *out_k, void *out_kd, void *out_kdd) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    if (f32)
+        deriv_simple_sweep<float>(lds, (const float *)inc0, (const float *)inc1, (const float *)inc2, ld, P, Mc, Nc, d, (float *)out_k,
+                                  (float *)out_kd, (float *)out_kdd);
+    else
+        deriv_simple_sweep<double>(lds, (const double *)inc0, (const double *)inc1, (const double *)inc2, ld, P, Mc, Nc, d, (double *)out_k,
+                                   (double *)out_kd, (double *)out_kdd);
 }
 
 int pick_blocks(int64_t P) {
@@ -227,9 +239,9 @@ int launch_deriv_simple(const T *inc, const T *inc_d, const T *inc_dd, const Geo
     const size_t lds = 3 * simple_lds_bytes(g);
     if (lds > 160 * 1024) return SK_ERR_UNSUPPORTED;
     if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)k_deriv_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SK_LAUNCH(k_deriv_simple<T>, dim3(pick_blocks(g.P)), dim3(WAVE), lds, s, inc, inc_d, inc_dd, g.ld, g.P, g.Mc,
-                       g.Nc, g.dyadic, out_k, out_kd, out_kdd);
+        (void)hipFuncSetAttribute((const void *)k_deriv_simple, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    SK_LAUNCH(k_deriv_simple, dim3(pick_blocks(g.P)), dim3(WAVE), lds, s, (int)(sizeof(T) == 4), (const void *)inc, (const void *)inc_d,
+              (const void *)inc_dd, g.ld, g.P, g.Mc, g.Nc, g.dyadic, (void *)out_k, (void *)out_kd, (void *)out_kdd);
     return check_launch();
 }
 

@@ -1,0 +1,259 @@
+// sk_truncated.hip -- the truncated signature kernel of Kiraly and Oberhauser as ONE sweep of every pair's step grid
+// (truncated_sig_kernel, reference sigkernel/transformers.py:201-236, which builds six-dimensional numpy arrays and shifts them with a
+// spline filter).
+//
+// The rows of x (M steps) and y (N steps) are used as they are; G[i][j] = <x_i, y_j>.  Level m of a pair is a set of d x d planes
+// R^m[p][q], d = min(m, order):
+//     R^1[0][0]     = G
+//     R^{m+1}[0][0] = G   sum_{i' < i, j' < j} sum_{p, q} R^m[p][q]                  (2-D exclusive prefix of the level below)
+//     R^{m+1}[0][q] = G / (q + 1)   sum_{i' < i} sum_p R^m[p][q - 1]                 (column prefix, same j)
+//     R^{m+1}[p][0] = G / (p + 1)   sum_{j' < j} sum_q R^m[p - 1][q]                 (row prefix, same i)
+//     R^{m+1}[p][q] = G / ((p + 1)(q + 1))   R^m[p - 1][q - 1]                       (same node)
+//     K = sigma[0] + sum_m sigma[m] sum_{nodes, planes} R^m
+// Level m + 1 at a node needs level m at nodes <= it only, so ALL LEVELS TRAVEL TOGETHER in one skewed sweep: lane l of a lane group
+// owns RC consecutive rows and runs one column behind lane l - 1.  Per level a lane keeps its running row sums (the j' < j prefixes) and
+// receives from the lane above, by DPP wave_shr:1, the inclusive column prefixes and the 2-D prefix Q[i][j] = Q[i-1][j] + (row prefix
+// of row i up to j).  The planes of a level live only while the node is computed.  Nothing of size pairs x M x N exists anywhere: G is
+// formed in the kernel (fd FMAs per node) from the x rows in registers and the y columns in LDS, both staged in fp64 by the prep
+// launch the fused solvers use (sk_prep_pair_*, points, fd = 8 or 16).
+//
+// Pairs: SHARED-Y order, as the fused forward's -- the G = 64 / W lane groups of a wave take rows a = G (q / B) + g of ONE column
+// b = q % B, so a wave stages one y block per position q.  Every pair of a launch costs exactly the same (one M, N, level count), so
+// the positions are dealt out statically (wave w takes q = w, w + waves, ...): a work counter would have nothing to even out.
+// Padding rows and columns have G = 0 and therefore contribute nothing; no lane is ever masked.
+// The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
+// order (1: one plane per level, or TR_OMAX) and the rows per lane.
+#include "sk_wave_common.h"
+
+namespace sk {
+namespace {
+
+constexpr int TR_LMAX = 8;            // levels the unrolled sweep holds
+constexpr int TR_OMAX = 4;            // largest order of the general instance
+constexpr int TR_LDS_DOUBLES = 2048;  // y block of a wave: fd x Ncp doubles, 16 KB -- eight single-wave workgroups per CU and more
+
+struct TruncParams {
+    const double *Xr;   // [A][Mrows][fd]
+    const double *Yt;   // [B][fd][Ncp]
+    void *out;          // [A][B], double or float
+    int64_t A, B, n_pos;
+    int Mrows, Ncp, fd, M, N, L, order, logW, out_f32;
+    double sigma[TR_LMAX + 1];
+};
+
+template <int OM, int RC>
+__global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
+    extern __shared__ __attribute__((aligned(16))) double ylds[];   // [fd][Ncp]
+    constexpr int O1 = OM > 1 ? OM - 1 : 1;
+    constexpr int NS = TR_LMAX - 1;      // levels that feed a next one
+    const int lane = threadIdx.x;
+    const int W = 1 << prm.logW, G = WAVE >> prm.logW;
+    const int lam = lane & (W - 1), grp = lane >> prm.logW;
+    const int N = prm.N, Ncp = prm.Ncp, L = prm.L, ord = prm.order, fd = prm.fd;
+    const bool wide = fd > 8;
+    const int steps = N + W - 1;
+    for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
+        const int64_t at = pos / prm.B, b = pos - at * prm.B;
+        const int64_t a = at * G + grp;
+        const bool live = a < prm.A;
+        __syncthreads();
+        {
+            const double *yb = prm.Yt + b * (int64_t)fd * Ncp;
+            for (int k = lane; k < fd * Ncp; k += WAVE) ylds[k] = yb[k];
+        }
+        double xr[RC][16];
+#pragma unroll
+        for (int r = 0; r < RC; ++r) {
+            const int row = lam * RC + r;
+            const bool ok = live && row < prm.M;
+            const double *xp = prm.Xr + ((ok ? a : 0) * (int64_t)prm.Mrows + (ok ? row : 0)) * fd;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) xr[r][k] = (ok && k < fd) ? xp[k] : 0.0;
+        }
+        __syncthreads();
+        double rowS[RC][NS], rowW[RC][NS][O1], qio[NS], cpio[NS][O1];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            qio[s] = 0.0;
+#pragma unroll
+            for (int c = 0; c < O1; ++c) cpio[s][c] = 0.0;
+#pragma unroll
+            for (int r = 0; r < RC; ++r) {
+                rowS[r][s] = 0.0;
+#pragma unroll
+                for (int c = 0; c < O1; ++c) rowW[r][s][c] = 0.0;
+            }
+        }
+        double acc = 0.0;
+        for (int t = 0; t < steps; ++t) {
+            const int j = t - lam;
+            const bool act = (unsigned)j < (unsigned)N;
+            const int jc = act ? j : 0;
+            // what the row above left at this column one step ago; the first lane of a group has no row above
+            double qin[NS], cpin[NS][O1];
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (s < L - 1) {
+                    const double v = dpp_shr1_zero(qio[s]);
+                    qin[s] = lam == 0 ? 0.0 : v;
+#pragma unroll
+                    for (int c = 0; c < O1; ++c)
+                        if (OM > 1 && c < ord - 1) {
+                            const double u = dpp_shr1_zero(cpio[s][c]);
+                            cpin[s][c] = lam == 0 ? 0.0 : u;
+                        } else cpin[s][c] = 0.0;
+                } else {
+                    qin[s] = 0.0;
+#pragma unroll
+                    for (int c = 0; c < O1; ++c) cpin[s][c] = 0.0;
+                }
+            // the column of y, once for all rows of the lane: the reads go out back to back and are waited for in one piece (the wait
+            // carries the values, so nothing that uses them can move above it -- the build's hazard lint holds this unit to that)
+            double yv[16];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) yv[k] = ylds[k * Ncp + jc];
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+            if (wide) {
+#pragma unroll
+                for (int k = 8; k < 16; ++k) yv[k] = ylds[k * Ncp + jc];
+                asm volatile("s_waitcnt lgkmcnt(0)"
+                             : "+v"(yv[8]), "+v"(yv[9]), "+v"(yv[10]), "+v"(yv[11]), "+v"(yv[12]), "+v"(yv[13]), "+v"(yv[14]), "+v"(yv[15]));
+            } else {
+#pragma unroll
+                for (int k = 8; k < 16; ++k) yv[k] = 0.0;
+            }
+#pragma unroll
+            for (int r = 0; r < RC; ++r) {
+                double g = 0.0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) g = fma(xr[r][k], yv[k], g);
+                if (wide) {
+#pragma unroll
+                    for (int k = 8; k < 16; ++k) g = fma(xr[r][k], yv[k], g);
+                }
+                g = act ? g : 0.0;
+                double prev[OM][OM];
+#pragma unroll
+                for (int p = 0; p < OM; ++p)
+#pragma unroll
+                    for (int q = 0; q < OM; ++q) prev[p][q] = 0.0;
+                prev[0][0] = g;
+#pragma unroll
+                for (int lv = 1; lv <= TR_LMAX; ++lv) {
+                    if (lv <= L) {
+                        const int dm = lv < OM ? lv : OM;               // planes of this level (at most; fewer when order is smaller)
+                        const int dn = lv + 1 < OM ? lv + 1 : OM;       // ... of the next
+                        double S = 0.0, Cq[OM], Wp[OM];
+#pragma unroll
+                        for (int p = 0; p < OM; ++p) Cq[p] = Wp[p] = 0.0;
+#pragma unroll
+                        for (int p = 0; p < OM; ++p)
+#pragma unroll
+                            for (int q = 0; q < OM; ++q)
+                                if (p < dm && q < dm) {
+                                    S += prev[p][q];
+                                    Cq[q] += prev[p][q];
+                                    Wp[p] += prev[p][q];
+                                }
+                        acc = fma(prm.sigma[lv], S, acc);
+                        if (lv < TR_LMAX && lv < L) {
+                            const int s = lv - 1;
+                            double next[OM][OM];
+#pragma unroll
+                            for (int p = 0; p < OM; ++p)
+#pragma unroll
+                                for (int q = 0; q < OM; ++q) {
+                                    double v = 0.0;
+                                    if (p < dn && q < dn) {
+                                        if (p == 0 && q == 0) v = g * qin[s];
+                                        else if (p == 0) v = (g * (1.0 / (q + 1))) * cpin[s][q > 0 ? q - 1 : 0];
+                                        else if (q == 0) v = (g * (1.0 / (p + 1))) * rowW[r][s][p > 0 ? p - 1 : 0];
+                                        else v = (g * (1.0 / ((p + 1) * (q + 1)))) * prev[p > 0 ? p - 1 : 0][q > 0 ? q - 1 : 0];
+                                        v = (p < ord && q < ord) ? v : 0.0;
+                                    }
+                                    next[p][q] = v;
+                                }
+                            // this node joins the sums of its level: Q[i][j] for the row below, the row prefixes for column j + 1
+                            qin[s] = qin[s] + rowS[r][s];
+                            rowS[r][s] += S;
+#pragma unroll
+                            for (int c = 0; c < O1; ++c)
+                                if (OM > 1 && c < dn - 1) {
+                                    cpin[s][c] += Cq[c];
+                                    rowW[r][s][c] += Wp[c];
+                                }
+#pragma unroll
+                            for (int p = 0; p < OM; ++p)
+#pragma unroll
+                                for (int q = 0; q < OM; ++q) prev[p][q] = next[p][q];
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                qio[s] = qin[s];
+#pragma unroll
+                for (int c = 0; c < O1; ++c) cpio[s][c] = cpin[s][c];
+            }
+        }
+        // the pair's total: a butterfly over the lanes of the group, the same order on every call
+        for (int off = 1; off < W; off <<= 1) acc += __shfl_xor(acc, off, WAVE);
+        if (lam == 0 && live) {
+            const double v = prm.sigma[0] + acc;
+            if (prm.out_f32) reinterpret_cast<float *>(prm.out)[a * prm.B + b] = (float)v;
+            else reinterpret_cast<double *>(prm.out)[a * prm.B + b] = v;
+        }
+    }
+}
+
+inline int trunc_fd(int D) { return D <= 8 ? 8 : 16; }
+inline int trunc_order(int L, int order) { return (order < 1 || order > L) ? L : order; }
+
+}  // namespace
+
+// THE scope of the kernel (the SK_OP_TRUNCATED rule of sk_route_query): rows of the FIRST batch per pair M, columns N, path dim D.
+// order 1: two rows per lane, M <= 128; orders 2 .. 4: one row per lane, M <= 64 (seven levels of row sums and hand-downs, three
+// plane columns each, fill the 256 registers two waves per SIMD leave a lane); the y block of a wave, fd x ceil16(N) doubles, in 16 KB.
+bool truncated_in_scope(int D, int M, int N, int L, int order) {
+    if (D < 1 || D > 16 || M < 1 || N < 1 || L < 1 || L > TR_LMAX) return false;
+    const int o = trunc_order(L, order);
+    if (o > TR_OMAX) return false;
+    if (M > (o == 1 ? 128 : 64)) return false;
+    return (int64_t)trunc_fd(D) * ((N + 15) / 16 * 16) <= TR_LDS_DOUBLES;
+}
+
+template <typename TO>
+int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
+                     int order, const double *sigma, TO *out, hipStream_t s) {
+    if (!truncated_in_scope(D, M, N, L, order)) return SK_ERR_UNSUPPORTED;
+    if (fd != trunc_fd(D) || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M) return SK_ERR_BAD_ARG;
+    TruncParams prm;
+    prm.Xr = Xr; prm.Yt = Yt; prm.out = out;
+    prm.A = A; prm.B = B;
+    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
+    prm.order = trunc_order(L, order);
+    prm.out_f32 = sizeof(TO) == 4;
+    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = m <= L ? sigma[m] : 0.0;
+    const int RC = prm.order == 1 ? 2 : 1;
+    const int lanes = (M + RC - 1) / RC;
+    int logW = 0;
+    while ((1 << logW) < lanes) ++logW;
+    prm.logW = logW;
+    const int G = WAVE >> logW;
+    prm.n_pos = (A + G - 1) / G * B;
+    int64_t blocks = (int64_t)device_cu_count() * 8;
+    if (blocks > prm.n_pos) blocks = prm.n_pos;
+    const size_t lds = sizeof(double) * (size_t)fd * Ncp;
+    if (RC == 2) SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
+    else SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
+    return check_launch();
+}
+
+template int launch_truncated<double>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
+                                      double *, hipStream_t);
+template int launch_truncated<float>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
+                                     float *, hipStream_t);
+
+}  // namespace sk

@@ -187,6 +187,9 @@ def gated(g, be):
         X, Y = walk(g, 3, 33, 5, dt), walk(g, 4, 20, 5, dt)
         sk.compute_Gram_prefixes(X, Y); sk.compute_kernel_prefixes(X, Y[:3])
     sigkernel_amd.SigKernel(LIN(), 1).compute_Gram_prefixes(walk(g, 3, 20, 12, f64), walk(g, 4, 17, 12, f64))
+    # truncated_sig_kernel: both instances of k_trunc_sig (order 1, two rows per lane; the general order), direct and on (y, x), each output dtype
+    for dt, (M, N, L, order) in itertools.product((f64, f32), ((100, 40, 6, 1), (50, 30, 5, -1), (40, 30, 4, 2), (200, 60, 4, 3))):
+        sigkernel_amd.truncated_sig_kernel(0.3 * torch.randn(5, M, 6, generator=g).to(dt).cuda(), 0.3 * torch.randn(7, N, 6, generator=g).to(dt).cuda(), L, order=order)
     # an exported entry point the host layer has no call of any more (the one-launch loss route carries its weights from the forward)
     be.loss_weights(5, 7, torch.ones((), dtype=f64).cuda(), torch.device("cuda"))
 
