@@ -429,6 +429,26 @@ int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream);
 int sk_solve_prefix_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, float *out, int64_t ldo, void *queue, void *stream);
+/* A SLICE of the prefix grid alone -- the same sweep of the same kernel, storing only the nodes of the slice, so a call is not bound by
+ * pairs x (Mc + 1) x (Nc + 1) stores nor by that much memory.  nodes:
+ *   SK_NODES_DIAGONAL  out[p ldo + t] = k_sig(x[:t+1], y[:t+1]),  1 <= t <= min(Mc, Nc);   ldo >= min(Mc, Nc) + 1
+ *   SK_NODES_LAST_ROW  out[p ldo + n] = k_sig(x, y[:n+1]),        1 <= n <= Nc;            ldo >= Nc + 1
+ *   SK_NODES_LAST_COL  out[p ldo + m] = k_sig(x[:m+1], y),        1 <= m <= Mc;            ldo >= Mc + 1
+ *   SK_NODES_ALL       the call above (out, ldo as there).
+ * Element 0 of every slice -- exactly 1 -- is NOT written: it is the caller's fill.  Nothing else outside those elements is written.
+ * Every element is bit for bit the node sk_solve_prefix_* stores there.  Other arguments, scope and errors: as sk_solve_prefix_*. */
+#define SK_NODES_ALL 0
+#define SK_NODES_DIAGONAL 1
+#define SK_NODES_LAST_ROW 2
+#define SK_NODES_LAST_COL 3
+int sk_solve_prefix_nodes_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                     int dyadic, int scheme, int nodes, double *out, int64_t ldo, void *queue, void *stream);
+int sk_solve_prefix_nodes_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                     int dyadic, int scheme, int nodes, float *out, int64_t ldo, void *queue, void *stream);
+int sk_solve_prefix_nodes_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                  int dyadic, int scheme, double inv_sigma, int nodes, double *out, int64_t ldo, void *queue, void *stream);
+int sk_solve_prefix_nodes_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                  int dyadic, int scheme, double inv_sigma, int nodes, float *out, int64_t ldo, void *queue, void *stream);
 /* The truncated signature kernel of Kiraly and Oberhauser as ONE sweep per pair (replaces truncated_sig_kernel, transformers.py:201-236:
  * six-dimensional numpy arrays shifted by a spline filter): out[a][b] = sigma[0] + sum_{m = 1 .. num_levels} sigma[m] * (sum of level m's
  * planes over the step grid of (x_a, y_b)); the rows of the paths are used as STEPS (no differencing); order = num_levels (or < 1) is the

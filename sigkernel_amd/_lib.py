@@ -25,6 +25,13 @@ FLAG_EXACT = 1
 FLAG_SIMPLE = 2
 FLAG_FAST_ONLY = 4
 FLAG_EDGES_GIVEN = 8
+# the nodes of the prefix grid a call keeps (SK_NODES_* of include/sigkernel_amd.h)
+PREFIX_NODES = {"all": 0, "diagonal": 1, "last_row": 2, "last_col": 3}
+
+
+def prefix_nodes_len(nodes, M, N):
+    """length of a slice of the (M, N) prefix grid: the diagonal, the last row (one node per prefix of y), the last column"""
+    return {"diagonal": min(M, N), "last_row": N, "last_col": M}[nodes]
 
 _lib = None
 
@@ -72,6 +79,10 @@ SIGNATURES = {
     "sk_solve_prefix_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _i64, _vp, _vp]),
+    "sk_solve_prefix_nodes_linear_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
+    "sk_solve_prefix_nodes_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
+    "sk_solve_prefix_nodes_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _vp, _i64, _vp, _vp]),
+    "sk_solve_prefix_nodes_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _vp, _i64, _vp, _vp]),
     "sk_truncated_gram_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_truncated_gram_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_prep_pair_f64": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
@@ -522,22 +533,29 @@ class HipBackend:
         _check(rc, "sk_solve_fwd_rbf")
         return (out, None) if keep_edges else out
 
-    def solve_prefix_fused(self, kind, param, X, Y, dyadic, naive, gram, out=None):
+    def solve_prefix_fused(self, kind, param, X, Y, dyadic, naive, gram, out=None, nodes="all"):
         """The grid of prefix kernels of every pair in ONE fused sweep (sk_solve_prefix_{linear,rbf}_*, csrc/sk_wave_prefix.hip):
         out[..., m, n] = k_sig(x[:m+1], y[:n+1]) -- (A, B, M, N) for gram, (A, M, N) paired -- in the dtype of X; nothing else of size
         pairs x M x N exists.  kind 0: param = the linear kernel's scale; kind 1: param = sigma.  Row 0 (the ones of the one-point prefix
         of x: N contiguous elements per pair) is filled here; column 0 comes from the kernel, inside the lines it writes anyway.  `out`: write into this tensor instead (a slice of a larger one is fine as long as every
-        pair's (M, N) grid is dense and the pairs are evenly spaced).  Returns None outside the kernel's scope
+        pair's (M, N) grid is dense and the pairs are evenly spaced).
+        nodes = "diagonal" / "last_row" / "last_col": the same sweep storing only that slice of every grid (sk_solve_prefix_nodes_*) --
+        (..., min(M, N)) / (..., N) / (..., M), element 0 (exactly 1) filled here -- and NOTHING of size pairs x M x N exists at all.
+        Returns None outside the kernel's scope
         (sk_route_query(SK_OP_PREFIX) != FUSED) -- the caller takes static_increments + solve_fwd(want_grid=True)."""
         _dev(X, "X")
         _dev(Y, "Y")
+        if nodes not in PREFIX_NODES:
+            raise ValueError("nodes must be one of %s, not %r" % (", ".join(repr(n) for n in PREFIX_NODES), nodes))
         A, M, D = X.shape
         B, N = Y.shape[0], Y.shape[1]
         Mc, Nc = M - 1, N - 1
         if Mc < 1 or Nc < 1 or (kind == 1 and not float(param) > 0) or \
                 self.route(OP_PREFIX, kind, D, M, N, dyadic, naive, X.element_size()) != ROUTE_FUSED:
             return None
-        shape = (A, B, M, N) if gram else (A, M, N)
+        mode = PREFIX_NODES[nodes]
+        tail = (M, N) if mode == 0 else (prefix_nodes_len(nodes, M, N),)
+        shape = ((A, B) if gram else (A,)) + tail
         if out is None:
             out = torch.empty(shape, dtype=X.dtype, device=X.device)
         if tuple(out.shape) != shape or out.dtype != X.dtype or out.device != X.device:
@@ -545,31 +563,38 @@ class HipBackend:
         if A == 0 or (gram and B == 0):
             return out
         ldo = out.stride(1) if gram else out.stride(0)
-        if out.stride(-1) != 1 or out.stride(-2) != N or ldo < M * N or (gram and A > 1 and out.stride(0) != B * ldo):
-            raise ValueError("out: every pair's (M, N) grid must be dense and the pairs evenly spaced")
+        if mode == 0:
+            if out.stride(-1) != 1 or out.stride(-2) != N or ldo < M * N or (gram and A > 1 and out.stride(0) != B * ldo):
+                raise ValueError("out: every pair's (M, N) grid must be dense and the pairs evenly spaced")
+        elif out.stride(-1) != 1 or ldo < tail[0] or (gram and A > 1 and out.stride(0) != B * ldo):
+            raise ValueError("out: every pair's slice must be dense and the pairs evenly spaced")
         Mrows = _stage_rows(kind, M, gram)
         Ncp = ((Nc if kind == 0 else N) + 15) // 16 * 16
         dev = X.device
         scheme = SCHEME_NAIVE if naive else SCHEME_DEFAULT
         lib = load()
         pairs = A * B if gram else A
+        # (the full grid keeps its own entry points: the same call as before the slices existed)
+        which = ("sk_solve_prefix_" if mode == 0 else "sk_solve_prefix_nodes_") + ("linear_" if kind == 0 else "rbf_") + _suffix(X)
+        sel = () if mode == 0 else (mode,)
         with _device(dev):
             if kind == 0:
                 # staged exactly as solve_fwd_fused_linear stages them: the last node is that call's value bit for bit
                 kappa = float(lib.sk_linear_prescale(int(dyadic)))
                 dXr, dYt = _prep_pair(X, Y, True, kappa * float(param) ** 2, Mrows, Ncp)
-                fn = getattr(lib, "sk_solve_prefix_linear_" + _suffix(X))
-                rc = fn(_ptr(dXr), _ptr(dYt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, _ptr(out), ldo,
-                        _ptr(_queue(dev, pairs)), _stream(X))
+                rc = getattr(lib, which)(_ptr(dXr), _ptr(dYt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, *sel,
+                                         _ptr(out), ldo, _ptr(_queue(dev, pairs)), _stream(X))
             else:
                 Xr, Yt = _prep_pair(X, Y, False, 1.0, Mrows, Ncp)
-                fn = getattr(lib, "sk_solve_prefix_rbf_" + _suffix(X))
-                rc = fn(_ptr(Xr), _ptr(Yt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, 1.0 / float(param),
-                        _ptr(out), ldo, _ptr(_queue(dev, pairs)), _stream(X))
+                rc = getattr(lib, which)(_ptr(Xr), _ptr(Yt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme,
+                                         1.0 / float(param), *sel, _ptr(out), ldo, _ptr(_queue(dev, pairs)), _stream(X))
         if rc == 2:
             return None
         _check(rc, "sk_solve_prefix")
-        out[..., 0, :] = 1      # the one-point prefix of x: the kernel stores rows m >= 1 (with their column 0)
+        if mode == 0:
+            out[..., 0, :] = 1      # the one-point prefix of x: the kernel stores rows m >= 1 (with their column 0)
+        else:
+            out[..., 0] = 1         # k of two one-point prefixes / of one against a whole path: the kernel stores elements >= 1
         return out
 
     def truncated_gram(self, X, Y, num_levels, sigma, order):

@@ -140,14 +140,19 @@ int solve_fwd_sym(int kind, const double *Xr, const double *Xt, const int *pair_
 // the prefix grid of every pair (sk_wave_prefix.hip); argument checks before any HIP call
 template <typename TO>
 int solve_prefix(int kind, const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
-                 int scheme, double inv_sigma, TO *out, int64_t ldo, void *queue, void *stream) {
+                 int scheme, double inv_sigma, TO *out, int64_t ldo, void *queue, void *stream, int nodes = SK_NODES_ALL) {
     if (D < 1 || !Xr || !Yt || !out || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
     if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
     if (kind == 1 && (!(inv_sigma > 0.0) || !(inv_sigma < 1e300))) return SK_ERR_BAD_ARG;
-    if (ldo < ((int64_t)Mc + 1) * ((int64_t)Nc + 1)) return SK_ERR_BAD_ARG;
+    if (nodes != SK_NODES_ALL && nodes != SK_NODES_DIAGONAL && nodes != SK_NODES_LAST_ROW && nodes != SK_NODES_LAST_COL) return SK_ERR_BAD_ARG;
+    // elements of one pair: the grid, or the slice of it
+    const int64_t need = nodes == SK_NODES_ALL ? ((int64_t)Mc + 1) * ((int64_t)Nc + 1)
+                         : nodes == SK_NODES_DIAGONAL ? (int64_t)(Mc < Nc ? Mc : Nc) + 1
+                         : nodes == SK_NODES_LAST_ROW ? (int64_t)Nc + 1 : (int64_t)Mc + 1;
+    if (ldo < need) return SK_ERR_BAD_ARG;
     if (A == 0) return SK_OK;
     const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
-    return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, ldo, queue, (hipStream_t)stream);
+    return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, ldo, queue, (hipStream_t)stream, nodes);
 }
 
 // the truncated signature kernel's Gram matrix (sk_truncated.hip); argument checks before any HIP call
@@ -463,6 +468,23 @@ int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64
 int sk_solve_prefix_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, float *out, int64_t ldo, void *queue, void *stream) {
     return solve_prefix<float>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, queue, stream);
+}
+
+int sk_solve_prefix_nodes_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                     int dyadic, int scheme, int nodes, double *out, int64_t ldo, void *queue, void *stream) {
+    return solve_prefix<double>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, out, ldo, queue, stream, nodes);
+}
+int sk_solve_prefix_nodes_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                     int dyadic, int scheme, int nodes, float *out, int64_t ldo, void *queue, void *stream) {
+    return solve_prefix<float>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, out, ldo, queue, stream, nodes);
+}
+int sk_solve_prefix_nodes_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                  int dyadic, int scheme, double inv_sigma, int nodes, double *out, int64_t ldo, void *queue, void *stream) {
+    return solve_prefix<double>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, queue, stream, nodes);
+}
+int sk_solve_prefix_nodes_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                  int dyadic, int scheme, double inv_sigma, int nodes, float *out, int64_t ldo, void *queue, void *stream) {
+    return solve_prefix<float>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, queue, stream, nodes);
 }
 
 size_t sk_solve_fwd_static_workspace_bytes(int kind, int64_t P, int Mc, int Nc, int dyadic, int D) {

@@ -26,6 +26,17 @@
 // masked per lane.  Column 0 of rows >= 1 is written here (inside lines the kernel writes anyway); row 0 -- N contiguous ones per
 // pair -- is the host's fill.
 //
+// SLICES (prm.slice, a launch-time wave-uniform value like the stencil and the output dtype: no instance more).  Most callers want a
+// thin slice of the grid, and the full grid is what binds the kernel to its stores (and to the card's memory), so three more store
+// modes keep only the nodes of a slice, out + p ldo + index with ldo = the slice's length:
+//   1  DIAGONAL     out[p][t] = k(x[:t+1], y[:t+1]), t < min(M, N): the nodes whose row lam RC + k + 1 equals their column 2 uk + q + 1
+//   2  LAST ROW     out[p][n] = k(x, y[:n+1]),       n < N:         row Mc, i.e. one row of one lane of the pair
+//   3  LAST COLUMN  out[p][m] = k(x[:m+1], y),       m < M:         column Nc, i.e. one macro-step of every lane
+// One-element stores straight from the registers, direct (where the block is finished), under the same masks as the full grid's
+// (padding rows, padding columns, stream positions without a pair); element 0 -- exactly 1 in all three -- is the host's fill.  The
+// sweep is the same code: every stored value is bit for bit the node the full grid holds there.  The slice modes branch around the
+// full grid's store block (one scalar branch per macro-step), so that block and its registers are as they were.
+//
 // Scope: kind 0 / 1, dim <= 8, one band per pair -- rows <= 64 RC with RC = 4 / 2 / 1 at dyadic 0 / 1 / 2, rows = M - 1 linear and
 // M rbf; rbf at dyadic 0 sweeps two rows per lane (rows <= 128: the four-row form with 8 staged dims spills) -- dyadic <= 2, any N.
 // PAIR ORDER, rings, producers: see sk_wave_fused.hip, whose comments are not repeated here.
@@ -44,13 +55,15 @@ constexpr int x_window(int kind, int rc) { return (kind == 0 && rc == 4) ? 4 : 8
 struct PrefixParams {
     const double *dXr;   // [A][Mrows][8]: linear: kappa s^2 (x[p+1]-x[p]); rbf: x[p]  (sk_prep_pair_*, as sk_solve_fwd_{linear,rbf}_*)
     const double *dYt;   // [Bn][8][Ncp]: linear: y[q+1]-y[q]; rbf: y[q]; dimension-major
-    void *out;           // pair p: (Mc + 1) x (Nc + 1) nodes at out + p ldo, row pitch Nc + 1; row 0 and column 0 are not written here
+    void *out;           // pair p: (Mc + 1) x (Nc + 1) nodes at out + p ldo, row pitch Nc + 1; row 0 is not written here
+                         // (slice != 0: the slice's min(Mc, Nc) + 1 / Nc + 1 / Mc + 1 elements at out + p ldo; element 0 is not written here)
     int64_t ldo;         // elements between the grids of consecutive pairs
     int64_t P, B;        // B > 0: Gram, pair p = (p / B, p % B); B == 0: paired, pair p = (p, p)
     int Mrows, Ncp;
     int Mc, Nc, NUp, logL;
     int kind, naive, f32;   // static kernel (0 linear, 1 rbf), first-order stencil, nodes stored as float
     int defer, wide;        // the store scheme (see THE STORE above): stores issued behind the window's DMA wait; shifted two-column pieces
+    int slice;              // SK_NODES_*: 0 the full grid; 1 / 2 / 3: only the diagonal / the last row / the last column (see SLICES above)
     int u_f, lam_f;      // unit / lane of the last node (they end the wave's last pair)
     double inv_sigma;    // RBF: G = exp(-|x - y|^2 * inv_sigma)
     WaveGroup wg;
@@ -310,8 +323,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
     // ---- the store: node (1, 1) of this lane's rows in the grid of the pair its SWEEP is in (nullptr: no such pair, or only padding
     // rows), set where the sweep enters a pair; o_rows of the lane's RC rows exist
     const int64_t pitch = (int64_t)prm.Nc + 1;
+    // (NOT clamped to RC: every use compares it with a k < RC, and the last-row store finds the lane of row Mc by 1 <= o_rows <= RC)
     int o_rows = prm.Mc - lam * RC;
-    o_rows = o_rows > RC ? RC : o_rows;
     char *o_ptr = nullptr;      // (bytes: the element is a double or, prm.f32, a float)
     const int esz = prm.f32 ? 4 : 8;
     int n_cols = prm.Nc;
@@ -321,6 +334,64 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
 #pragma unroll
     for (int k = 0; k < RC; ++k) prev[k] = 1.0;
     const bool wide = prm.wide != 0, defer = prm.defer != 0;
+    // a slice of the grid (prm.slice != 0): o_ptr is element 1 + lam RC of the pair's slice (diagonal, last column: element k from there
+    // belongs to the lane's row k) or element 1 (last row: element 2 uk + q from there belongs to node column q of the step).
+    // REGISTERS: k_fwd_prefix<1, 2, 0> has one VGPR to spare below three waves per SIMD, and whatever is invariant per lane gets hoisted
+    // into a register of its own -- so nothing here forms one (no lam RC, no Nc - 1, no running pointer); the ISA is as the full grid's
+    // alone (tools/variants.py: 157 / 155 / 167 / 147 VGPRs, no scratch).
+    auto store_slice = [&](const double (&cand)[RC][CW], int uk) __attribute__((always_inline)) {
+        if (o_ptr == nullptr) return;
+        const int slice = prm.slice;
+        const int col = 2 * uk;
+        if (slice == 2) {
+            // last row: only the lane that holds row Mc has a row k with k + 1 == o_rows
+            if (o_rows <= RC) {
+                asm volatile("");
+                double v0 = cand[0][0], v1 = cand[0][1];
+#pragma unroll
+                for (int k = 1; k < RC; ++k) {
+                    v0 = k + 1 == o_rows ? cand[k][0] : v0;
+                    v1 = k + 1 == o_rows ? cand[k][1] : v1;
+                }
+                if (prm.f32) {
+                    float *const o = reinterpret_cast<float *>(o_ptr) + col;
+                    if (col < n_cols) o[0] = (float)v0;
+                    if (col + 1 < n_cols) o[1] = (float)v1;
+                } else {
+                    double *const o = reinterpret_cast<double *>(o_ptr) + col;
+                    if (col < n_cols) o[0] = v0;
+                    if (col + 1 < n_cols) o[1] = v1;
+                }
+            }
+        } else if (slice == 1) {
+            // diagonal: node (k, q) lies on it where col + q == lam RC + k.  The lane's first row is re-derived from the lane number in
+            // every step (behind an opaque zero, or it would be hoisted): no register is held for it across the sweep
+            int z = 0;
+            asm volatile("" : "+s"(z));
+            const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z));
+            const int d = col - (ln & ((1 << prm.logL) - 1)) * RC;
+#pragma unroll
+            for (int k = 0; k < RC; ++k)
+#pragma unroll
+                for (int q = 0; q < CW; ++q)
+                    if (d == k - q && k < o_rows && col + q < n_cols) {
+                        if (prm.f32) reinterpret_cast<float *>(o_ptr)[k] = (float)cand[k][q];
+                        else reinterpret_cast<double *>(o_ptr)[k] = cand[k][q];
+                    }
+        } else {
+            // last column: grid column Nc = node column Nc - 1 of the sweep
+#pragma unroll
+            for (int q = 0; q < CW; ++q)
+                if (col + (q + 1) == n_cols) {
+#pragma unroll
+                    for (int k = 0; k < RC; ++k)
+                        if (k < o_rows) {
+                            if (prm.f32) reinterpret_cast<float *>(o_ptr)[k] = (float)cand[k][q];
+                            else reinterpret_cast<double *>(o_ptr)[k] = cand[k][q];
+                        }
+                }
+        }
+    };
     // the nodes of one macro-step (uk: the sweep's unit, before the step counter moves on)
     auto store_nodes = [&](const double (&cand)[RC][CW], int uk) __attribute__((always_inline)) {
         if (o_ptr != nullptr) {
@@ -406,8 +477,11 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
                 const unsigned Bu = (unsigned)prm.B, qa = pair_u / Bu, a = qa * (unsigned)G + (unsigned)grp;
                 pair_u = a < (unsigned)sA ? a * Bu + (pair_u - qa * Bu) : NOPAIR;
             }
+            // (a slice: see store_slice -- the same address arithmetic with a pitch of 1 or 0 in place of the grid's, all scalar)
+            const int sl = prm.slice;
+            const int64_t o_pitch = sl == 0 ? pitch : sl == 2 ? 0 : 1, o_first = sl == 0 || sl == 2 ? 1 : 0;
             o_ptr = (pair_u != NOPAIR && o_rows > 0)
-                        ? static_cast<char *>(prm.out) + ((int64_t)pair_u * prm.ldo + (int64_t)(1 + lam * RC) * pitch + 1) * esz
+                        ? static_cast<char *>(prm.out) + ((int64_t)pair_u * prm.ldo + (int64_t)(1 + lam * RC) * o_pitch + o_first) * esz
                         : nullptr;
         }
 
@@ -511,7 +585,12 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
         // they are issued behind it (end of the loop body) and have a whole window to land.
         int uk_now = tm + c_kr;
         uk_now -= uk_now >= NUp ? NUp : 0;
-        if (!defer) store_nodes(cand, uk_now);
+        if (prm.slice != 0) {      // (the launcher clears defer and wide then: nothing of the full grid's block runs)
+            asm volatile("");   // a real branch around the full grid's stores
+            store_slice(cand, uk_now);
+        } else if (!defer) {
+            store_nodes(cand, uk_now);
+        }
 
         // -- advance: the y units of the NEXT macro-step and the x rows of a lane that starts a pair in it, handed over by the single
         // LDS wait at the top of the next step
@@ -617,11 +696,13 @@ bool prefix_in_scope(int kind, int D, int Mc, int dyadic) {
 }
 
 // KIND 0: dXr [A][Mrows][8] / dYt [Bn][8][Ncp] are path differences; KIND 1: the same layouts hold the path points.
+// nodes: 0 the full grid (ldo >= (Mc + 1) (Nc + 1)); 1 / 2 / 3 the diagonal / last row / last column alone (ldo >= its length).
 // SK_ERR_UNSUPPORTED outside the kernel's scope.
 template <typename TO>
 int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s) {
+                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s, int nodes) {
     const int DY = g.dyadic;
+    if (nodes < 0 || nodes > 3) return SK_ERR_BAD_ARG;
     if (!prefix_in_scope(kind, D, g.Mc, DY)) return SK_ERR_UNSUPPORTED;
     // linear: one unit = two increment columns.  RBF: one unit = two NODE columns, and the sweep of a pair's last unit reads one node
     // column of the following unit, which therefore has to exist as padding inside the pair's stream; likewise the lanes of a pair
@@ -660,8 +741,10 @@ int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A,
     // store scheme: SK_PREFIX_STORE = 1 direct, 2 deferred, 3 deferred + two-column pieces (where the grid allows them); 0: the default
     const int mode = knobs().prefix_store > 0 ? knobs().prefix_store : PREFIX_STORE_DEFAULT;
     const bool can_wide = ((g.Nc + 1) & 1) == 0 && (ldo & 1) == 0 && ((uintptr_t)out % (2 * sizeof(TO))) == 0;
-    prm.defer = mode >= 2;
-    prm.wide = mode >= 3 && can_wide;
+    prm.slice = nodes;
+    // (a slice is stored direct, one element at a time: the deferred scheme and the two-column pieces belong to the full grid)
+    prm.defer = nodes == 0 && mode >= 2;
+    prm.wide = nodes == 0 && mode >= 3 && can_wide;
     // (shared-y: the kernel rebuilds the pair index a B + b from a position in 32 bits)
     if (B > 0 && A * B >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;
     prm.queue = (unsigned long long *)queue;
@@ -677,8 +760,8 @@ int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A,
 }
 
 template int launch_fwd_prefix<double>(int, const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double, double *,
-                                       int64_t, void *, hipStream_t);
+                                       int64_t, void *, hipStream_t, int);
 template int launch_fwd_prefix<float>(int, const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double, float *,
-                                      int64_t, void *, hipStream_t);
+                                      int64_t, void *, hipStream_t, int);
 
 }  // namespace sk

@@ -988,20 +988,31 @@ def _loss_launch_ok(be, static_kernel, Xd, Yd, dyadic, naive, need_grad, with_yy
 _LOSS_LAUNCH_FREE_BYTES = None    # "loss_launch_free_bytes": below this the one-launch loss route does not ask the device for its free memory
 
 
-def _prefix_grid(be, static_kernel, Xd, Yd, dyadic, naive, gram, workspace_bytes):
+def _prefix_nodes(grid, nodes):
+    """the slice `nodes` of prefix grids (..., M, N): their diagonal (..., min(M, N)), last row (..., N) or last column (..., M)"""
+    if nodes == "diagonal":
+        return torch.diagonal(grid, dim1=-2, dim2=-1)
+    return grid[..., -1, :] if nodes == "last_row" else grid[..., :, -1]
+
+
+def _prefix_grid(be, static_kernel, Xd, Yd, dyadic, naive, gram, workspace_bytes, nodes="all"):
     """out[..., m, n] = k_sig(x[:m+1], y[:n+1]) for every pair: (A, B, M, N) for gram, (A, M, N) paired.  The fused prefix kernel where the
     library says so (sk_route_query(SK_OP_PREFIX): no transient memory), else the existing pieces -- increments, the streaming
-    solver's full grid, its coarse nodes -- over row tiles that keep increments + fine grid within the budget."""
+    solver's full grid, its coarse nodes -- over row tiles that keep increments + fine grid within the budget.
+    nodes = "diagonal" / "last_row" / "last_col": only that slice of every grid, (..., min(M, N)) / (..., N) / (..., M) -- stored alone by
+    the fused kernel, taken from each row tile's grid elsewhere: nothing of size pairs x M x N is allocated beyond a tile."""
     A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
     B = Yd.shape[0] if gram else 1
-    shape = (A, Yd.shape[0], M, N) if gram else (A, M, N)
+    tail = (M, N) if nodes == "all" else (_lib.prefix_nodes_len(nodes, M, N),)
+    shape = ((A, Yd.shape[0]) if gram else (A,)) + tail
     if M < 2 or N < 2 or A == 0 or B == 0:      # one-point paths: every prefix kernel is 1; empty batches: empty results
         return torch.ones(shape, dtype=Xd.dtype, device=Xd.device)
     fused = _fused_static(static_kernel, gram)
     if fused is not None and hasattr(be, "solve_prefix_fused") and not routes.no_fused_prefix and \
             not (fused[0] == 1 and routes.no_fused_rbf):
         # (the back-end asks sk_route_query(SK_OP_PREFIX) and returns None where the library names the streamed route)
-        out = be.solve_prefix_fused(fused[0], fused[1], Xd.contiguous(), Yd.contiguous(), dyadic, naive, gram)
+        more = {} if nodes == "all" else {"nodes": nodes}
+        out = be.solve_prefix_fused(fused[0], fused[1], Xd.contiguous(), Yd.contiguous(), dyadic, naive, gram, **more)
         if out is not None:
             return out
     out = torch.empty(shape, dtype=Xd.dtype, device=Xd.device)
@@ -1011,7 +1022,7 @@ def _prefix_grid(be, static_kernel, Xd, Yd, dyadic, naive, gram, workspace_bytes
     for a0, a1 in _tiles(A, per_row, _budget(Xd.device, workspace_bytes)):
         inc = _increments(be, static_kernel, Xd[a0:a1], Yd if gram else Yd[a0:a1], gram=gram)
         _, grid, _ = be.solve_fwd(inc, dyadic, naive, want_grid=True)
-        out[a0:a1] = grid[..., ::r, ::r]
+        out[a0:a1] = grid[..., ::r, ::r] if nodes == "all" else _prefix_nodes(grid[..., ::r, ::r], nodes)
         del inc, grid
     return out
 
@@ -1071,10 +1082,12 @@ class SigKernel:
             return _SigKernel.forward(_NoGradCtx(), X, Y, self.static_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes)
         return _SigKernel.apply(X, Y, self.static_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes)
 
-    def _prefixes(self, X, Y, gram, max_batch):
+    def _prefixes(self, X, Y, gram, max_batch, nodes="all"):
+        if nodes not in _lib.PREFIX_NODES:
+            raise ValueError("nodes must be one of %s, not %r" % (", ".join(repr(n) for n in _lib.PREFIX_NODES), nodes))
         f = self._on_features()
         if f is not None:
-            return f[0]._prefixes(f[1](X), f[1](Y), gram, max_batch)
+            return f[0]._prefixes(f[1](X), f[1](Y), gram, max_batch, nodes)
         _check_inputs(X, Y, paired=not gram)
         if self.process_group is not None:
             raise NotImplementedError("prefix grids are not sharded over a process group: every rank would have to gather an "
@@ -1083,21 +1096,47 @@ class SigKernel:
             raise NotImplementedError("compute_Gram_prefixes / compute_kernel_prefixes are forward only: the prefix grid has no "
                                       "gradient.  Call them under torch.no_grad() or on detached paths")
         return _prefix_grid(_lib.get_backend(), self.static_kernel, X.detach(), Y.detach(), self.dyadic_order, self._naive_solver, gram,
-                            self.workspace_bytes)
+                            self.workspace_bytes, nodes)
 
-    def compute_Gram_prefixes(self, X, Y, max_batch=100):
+    def compute_Gram_prefixes(self, X, Y, max_batch=100, nodes="all"):
         """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim) -> (batch_X, batch_Y, len_x, len_y): out[a, b, m, n] =
         k(X^a restricted to its first m + 1 points, Y^b restricted to its first n + 1 points) -- the coarse nodes of the PDE grid the
         solver sweeps anyway (node (m << dyadic_order, n << dyadic_order) of the reference's solver grids), all in one sweep.  Row
         m = 0 and column n = 0 are exactly 1; out[..., -1, -1] is ``compute_Gram(X, Y)``.  Forward only: no ``grad_fn``, and paths that
         require grad raise outside ``torch.no_grad()``.  Batches of unequal length: pad every path at its end with anything and gather
-        node (len_a - 1, len_b - 1).  ``max_batch`` is accepted and ignored, as elsewhere."""
-        return self._prefixes(X, Y, True, max_batch)
+        node (len_a - 1, len_b - 1).  ``max_batch`` is accepted and ignored, as elsewhere.
 
-    def compute_kernel_prefixes(self, X, Y, max_batch=100):
+        ``nodes`` keeps a slice of every grid instead of the grid -- the same sweep, the same values bit for bit, but neither the
+        stores nor the memory of batch_X x batch_Y x len_x x len_y elements:
+          "diagonal"  (batch_X, batch_Y, min(len_x, len_y)):  out[a, b, t] = k(X^a[:t+1], Y^b[:t+1]), a kernel as a function of time
+          "last_row"  (batch_X, batch_Y, len_y):              out[a, b, n] = k(X^a, Y^b[:n+1]), a stream Y^b against complete paths
+          "last_col"  (batch_X, batch_Y, len_x):              out[a, b, m] = k(X^a[:m+1], Y^b)
+        Element 0 is exactly 1; the last element of "last_row" / "last_col" (of "diagonal" when len_x == len_y) is ``compute_Gram(X, Y)``.
+        Any other string raises ``ValueError``."""
+        return self._prefixes(X, Y, True, max_batch, nodes)
+
+    def compute_kernel_prefixes(self, X, Y, max_batch=100, nodes="all"):
         """X (batch, len_x, dim), Y (batch, len_y, dim) -> (batch, len_x, len_y): the paired form of ``compute_Gram_prefixes``;
-        out[..., -1, -1] is ``compute_kernel(X, Y)``."""
-        return self._prefixes(X, Y, False, max_batch)
+        out[..., -1, -1] is ``compute_kernel(X, Y)``.  ``nodes``: as there, without the batch_Y axis."""
+        return self._prefixes(X, Y, False, max_batch, nodes)
+
+    def compute_mmd_prefixes(self, X, Y, max_batch=100):
+        """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim) -> (min(len_x, len_y),): value t is ``compute_mmd(X[:, :t+1], Y[:, :t+1])``
+        -- the unbiased MMD^2 of the two samples as a function of time (sequential two-sample tests, change detection) -- from three
+        ``nodes="diagonal"`` sweeps (K_XX, K_YY, K_XY) and the reductions of ``compute_mmd`` over the pair axes; value 0 is 0 (every
+        kernel of one-point paths is 1).  Forward only, like the prefix methods; nothing of size pairs x len_x x len_y is allocated."""
+        if _wants_grad(X, Y):
+            raise NotImplementedError("compute_mmd_prefixes is forward only: the prefix grid has no gradient.  Call it under "
+                                      "torch.no_grad() or on detached paths")
+        T = min(X.shape[1], Y.shape[1])
+        K_XX = self.compute_Gram_prefixes(X, X, max_batch, nodes="diagonal")[..., :T]
+        K_YY = self.compute_Gram_prefixes(Y, Y, max_batch, nodes="diagonal")[..., :T]
+        K_XY = self.compute_Gram_prefixes(X, Y, max_batch, nodes="diagonal")
+        A, B = K_XX.shape[0], K_YY.shape[0]
+        # compute_mmd's estimator per t: the means of K_XX and K_YY without their diagonals (pairs a != a'), minus twice the mean of K_XY
+        K_XX_m = (torch.sum(K_XX, dim=(0, 1)) - torch.sum(torch.diagonal(K_XX, dim1=0, dim2=1), dim=-1)) / (A * (A - 1.))
+        K_YY_m = (torch.sum(K_YY, dim=(0, 1)) - torch.sum(torch.diagonal(K_YY, dim1=0, dim2=1), dim=-1)) / (B * (B - 1.))
+        return K_XX_m + K_YY_m - 2. * torch.mean(K_XY, dim=(0, 1))
 
     def compute_kernel_and_derivatives_Gram(self, X, Y, gamma, max_batch=100):
         """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim), gamma (batch_X, len_x, dim) -> three (batch_X, batch_Y)

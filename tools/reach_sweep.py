@@ -180,13 +180,17 @@ def gated(g, be):
         sk = sigkernel_amd.SigKernel(RBF(0.8), d)
         X, Y = walk(g, 3, 256, D, f64), walk(g, 4, 200, D, f64)
         sk.compute_Gram(X, Y); sk.compute_kernel(X, walk(g, 3, 200, D, f64))
-    # prefix grids: every instance of the fused prefix kernel (kind x dyadic order x stencil x output dtype), Gram and paired, and the
-    # route everything else takes (increments + the streaming solver's grid)
+    # prefix grids: every instance of the fused prefix kernel (kind x dyadic order x stencil x output dtype), Gram and paired, in each of
+    # its four store modes (the full grid, its diagonal, last row, last column), and the route everything else takes (increments + the
+    # streaming solver's grid, the slice taken from it)
     for kname, d, naive, dt in itertools.product(("linear", "rbf"), (0, 1, 2), (False, True), (f64, f32)):
         sk = sigkernel_amd.SigKernel(RBF(0.9) if kname == "rbf" else LIN(), d, _naive_solver=naive)
         X, Y = walk(g, 3, 33, 5, dt), walk(g, 4, 20, 5, dt)
         sk.compute_Gram_prefixes(X, Y); sk.compute_kernel_prefixes(X, Y[:3])
+        for nodes in ("diagonal", "last_row", "last_col"):      # the slice store modes of the same instances
+            sk.compute_Gram_prefixes(X, Y, nodes=nodes); sk.compute_kernel_prefixes(X, Y[:3], nodes=nodes)
     sigkernel_amd.SigKernel(LIN(), 1).compute_Gram_prefixes(walk(g, 3, 20, 12, f64), walk(g, 4, 17, 12, f64))
+    sigkernel_amd.SigKernel(LIN(), 1).compute_Gram_prefixes(walk(g, 3, 20, 12, f64), walk(g, 4, 17, 12, f64), nodes="diagonal")
     # truncated_sig_kernel: both instances of k_trunc_sig (order 1, two rows per lane; the general order), direct and on (y, x), each output dtype
     for dt, (M, N, L, order) in itertools.product((f64, f32), ((100, 40, 6, 1), (50, 30, 5, -1), (40, 30, 4, 2), (200, 60, 4, 3))):
         sigkernel_amd.truncated_sig_kernel(0.3 * torch.randn(5, M, 6, generator=g).to(dt).cuda(), 0.3 * torch.randn(7, N, 6, generator=g).to(dt).cuda(), L, order=order)
