@@ -163,7 +163,9 @@ __global__ __launch_bounds__(4 * WAVE) __attribute__((amdgpu_waves_per_eu((FD ==
         yslab = ((s0 % NSLAB) + NSLAB) % NSLAB;
         ypar = s0 & 1;
     }
-    // ---- the wave's pairs: positions 0 .. per-1 are pairs wave_id per + i ----------------------------------------------------------
+    // ---- the wave's pairs: the one-draw stream of sk_wave_fused_mb.hip.  A COPY, here and in the linear kernel below: as shared
+    // functions 14 of this file's instances changed, e.g. k_adj_fused_rbf_mb<0, 2, 16, 0> 291 -> 289 VGPRs, 2220 -> 2233 instructions
+    // and <2, 1, 16, 0> 253 -> 249 VGPRs
     constexpr unsigned NOPAIR = 0xffffffffu;
     const unsigned P32 = (unsigned)prm.P;
     const int C0 = prm.C0;
@@ -1206,15 +1208,10 @@ int launch_amb(AdjMbParams prm, const AmbPlan &pl, void *ws, size_t ws_bytes, hi
         if constexpr (KIND == 0) return k_adj_fused_linear_mb<DY, RC, FD>;
         else return k_adj_fused_rbf_mb<DY, RC, FD, Y32>;
     }();
-    static const int vgprs = [&] {
-        hipFuncAttributes attr;
-        return hipFuncGetAttributes(&attr, (const void *)kern) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : 256;
-    }();
+    static const int vgprs = variant_vgprs(kern, 256);
     // resident waves per CU: whole workgroups of wpb waves by LDS, by registers, at most two per SIMD
     const int wpb0 = wave_group(pl.lds_bytes, 1 << 20, knobs().adjmb_wpb).wpb;
-    int wpc = (int)((160 * 1024) / (pl.lds_bytes * wpb0)) * wpb0;
-    const int by_regs = 4 * (512 / ((vgprs + 7) & ~7));
-    if (wpc > by_regs) wpc = by_regs;
+    int wpc = waves_by_vgprs((int)((160 * 1024) / (pl.lds_bytes * wpb0)) * wpb0, vgprs);
     if (knobs().adjmb_wpc > 0 && wpc > knobs().adjmb_wpc) wpc = knobs().adjmb_wpc;
     if (wpc > 8) wpc = 8;
     if (wpc >= wpb0) wpc = wpc / wpb0 * wpb0;

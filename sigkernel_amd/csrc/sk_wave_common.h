@@ -418,6 +418,21 @@ __device__ __forceinline__ int64_t wave_slot(const WaveGroup &wg, char *lds_bloc
     return id < wg.n_waves ? id : -1;
 }
 
+// ---- resident waves of a kernel variant ------------------------------------------------------------------------------------------
+// Persistent waves must all be resident at once, so a variant's VGPR count caps the waves per SIMD (512 VGPRs per lane and SIMD: a
+// variant over 168 holds two waves per SIMD, not three).  The count is a property of the variant's code object, the same on every
+// gfx950 device: callers keep it in a `static const int`, initialised once, thread-safely, at the variant's first launch.
+template <class K>
+inline int variant_vgprs(K kern, int fallback) {
+    hipFuncAttributes attr;
+    return hipFuncGetAttributes(&attr, (const void *)kern) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : fallback;
+}
+inline int waves_by_vgprs(int waves_per_cu, int vgprs) {
+    const int by_regs = 4 * (512 / ((vgprs + 7) & ~7));
+    if (waves_per_cu > by_regs) waves_per_cu = by_regs;
+    return waves_per_cu < 1 ? 1 : waves_per_cu;
+}
+
 // ---- unequal shares for the waves that share a SIMD ---------------------------------------------------------------------
 // The SIMD arbiter favours the OLDEST resident wave: measured on the fused forward (3 four-wave workgroups per CU, equal
 // shares, profiles/r02_wave_placement.txt) the three waves of every SIMD finished after 2.8, 4.0 and 5.0 ms -- the SIMD ran

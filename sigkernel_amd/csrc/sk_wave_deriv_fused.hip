@@ -176,6 +176,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_deriv_fused(const DerivFusedParams
     }
     const int lam7 = lam & 7;
     // ---- the wave's stream of pairs (sk_wave_fused_mb.hip): C0 fixed, then one pair per draw from the launch's counter
+    // (a COPY: as shared functions all 24 instances changed, e.g. <0, 0, 8, 0, 0> 94 -> 96 SGPRs, 2155 -> 2157 instructions at 199 VGPRs)
     constexpr unsigned NOPAIR = 0xffffffffu;
     const unsigned P32 = (unsigned)prm.P;
     const int C0 = prm.C0;
@@ -668,14 +669,9 @@ DfPlan df_plan(int Mc, int Nc, int dyadic, int D) {
 template <int DY, int KIND, int FD, bool LDSB, bool SHIFT>
 int launch_df(DerivFusedParams prm, const DfPlan &pl, void *ws, size_t ws_bytes, hipStream_t s) {
     auto kern = k_deriv_fused<DY, KIND, FD, LDSB, SHIFT>;
-    static const int vgprs = [&] {
-        hipFuncAttributes attr;
-        return hipFuncGetAttributes(&attr, (const void *)kern) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : 256;
-    }();
+    static const int vgprs = variant_vgprs(kern, 256);
     const int wpb0 = wave_group(pl.lds_bytes, 1 << 20, knobs().derivf_wpb).wpb;
-    int wpc = (int)((160 * 1024) / (pl.lds_bytes * wpb0)) * wpb0;
-    const int by_regs = 4 * (512 / ((vgprs + 7) & ~7));
-    if (wpc > by_regs) wpc = by_regs;
+    int wpc = waves_by_vgprs((int)((160 * 1024) / (pl.lds_bytes * wpb0)) * wpb0, vgprs);
     if (knobs().derivf_wpc > 0 && wpc > knobs().derivf_wpc) wpc = knobs().derivf_wpc;
     if (wpc > 8) wpc = 8;
     if (wpc >= wpb0) wpc = wpc / wpb0 * wpb0;

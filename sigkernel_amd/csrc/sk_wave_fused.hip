@@ -33,18 +33,13 @@
 // instruction (a broadcast).  Per-pair arithmetic is untouched: results are bit-identical in either order.  With the x windows of
 // four lanes (x_window) the headline shape (L = 32, G = 2, four rows per lane, 8 dims) takes 6 KB + 4 KB of LDS per wave instead
 // of 12 + 8, which is what lets a third wave per SIMD be resident.
-#include "sk_wave_common.h"
+#include "sk_pair_stream.h"
 #include <algorithm>
 
 namespace sk {
 namespace {
 
 constexpr int FD = 8;              // dims carried (inputs are zero-padded to 8)
-constexpr int y_slab_pitch(int nd) { return nd * 128; }   // ND dimension rows of 8 units (the four-dimension variants stage and keep
-                                                          // dims 0..3 only); no padding (parity swizzle, see above)
-constexpr int X_SLOTS = 2;   // the window being consumed + the one in flight
-constexpr int x_row_bytes(int nd) { return nd == 4 ? 32 : 64; }
-
 struct FusedParams {
     const double *dXr;   // [A][Mrows][8]: kappa s^2 (x[p+1]-x[p]), kappa = 4^-d / sqrt(12) (sk_linear_prescale); zero rows/dims beyond Mc / D
     const double *dYt;   // [Bn][8][Ncp]: y[q+1]-y[q], dimension-major, zero columns/dims beyond Nc / D
@@ -85,44 +80,8 @@ struct FusedParams {
     // Consulted in the prologue, the producers and the (rarely taken) store branch, never in the step loop.
     int shy_A;
 };
-// lanes per x window: 8 (one window per y slab period), or 4 where four lanes' rows fill a whole 1 KiB LDS-DMA instruction anyway (the
-// linear four-row form with 8 dims and no edges: the headline's) -- half the x ring for the same number of DMA instructions, the
-// window bookkeeping every fourth step instead of every eighth
-constexpr int x_window(int kind, int nd, int rc, bool edges) { return (kind == 0 && nd == 8 && rc == 4 && !edges) ? 4 : 8; }
-
 template <int N>
 __device__ __forceinline__ void lds_read_units(d2_t (&v)[N], unsigned addr);
-// y units of a macro-step: even dimensions at a_even + {0, 256, 512, 768}, odd ones at a_odd + the same; the two addresses
-// differ by +-128 (parity swizzle of the slabs).
-// The reads carry no wait: they are issued at the end of a macro-step for the next one, so that their round trip
-// overlaps this wave's own block sweep.  `t` is written by the LDS and read by nothing until lds_dims_wait hands it
-// over (outputs tied to the temporaries' registers; tools/check_async_hazards.py lints the ISA for early uses).
-__device__ __forceinline__ void lds_read_dims_issue(d2_t (&t)[8], unsigned a_even, unsigned a_odd) {
-    asm volatile("ds_read_b128 %0, %8\n\t"
-                 "ds_read_b128 %1, %9\n\t"
-                 "ds_read_b128 %2, %8 offset:256\n\t"
-                 "ds_read_b128 %3, %9 offset:256\n\t"
-                 "ds_read_b128 %4, %8 offset:512\n\t"
-                 "ds_read_b128 %5, %9 offset:512\n\t"
-                 "ds_read_b128 %6, %8 offset:768\n\t"
-                 "ds_read_b128 %7, %9 offset:768"
-                 : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7])
-                 : "v"(a_even), "v"(a_odd)
-                 : "memory");
-}
-// dims 0..3 only (ND = 4)
-__device__ __forceinline__ void lds_read_dims_issue(d2_t (&t)[4], unsigned a_even, unsigned a_odd) {
-    asm volatile("ds_read_b128 %0, %4\n\t"
-                 "ds_read_b128 %1, %5\n\t"
-                 "ds_read_b128 %2, %4 offset:256\n\t"
-                 "ds_read_b128 %3, %5 offset:256"
-                 : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])
-                 : "v"(a_even), "v"(a_odd)
-                 : "memory");
-}
-__device__ __forceinline__ void lds_dims_wait(d2_t (&v)[4], d2_t (&t)[4]) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]) : "0"(t[0]), "1"(t[1]), "2"(t[2]), "3"(t[3]) : "memory");
-}
 // the first 32 bytes of two consecutive 64-byte rows (ND = 4), one wait
 __device__ __forceinline__ void lds_read_half_rows(d2_t (&v)[4], unsigned a) {
     asm volatile("ds_read_b128 %0, %4\n\t"
@@ -132,12 +91,6 @@ __device__ __forceinline__ void lds_read_half_rows(d2_t (&v)[4], unsigned a) {
                  "s_waitcnt lgkmcnt(0)"
                  : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
                  : "v"(a)
-                 : "memory");
-}
-__device__ __forceinline__ void lds_dims_wait(d2_t (&v)[8], d2_t (&t)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]), "=v"(v[4]), "=v"(v[5]), "=v"(v[6]), "=v"(v[7])
-                 : "0"(t[0]), "1"(t[1]), "2"(t[2]), "3"(t[3]), "4"(t[4]), "5"(t[5]), "6"(t[6]), "7"(t[7])
                  : "memory");
 }
 // 128 contiguous bytes (two coarse rows of x differences), one wait
@@ -165,37 +118,6 @@ __device__ __forceinline__ void lds_read_units<4>(d2_t (&v)[4], unsigned a) {
                  : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
                  : "v"(a)
                  : "memory");
-}
-
-// x-row reloads straight into the row registers (read-write operands: under a divergent branch the inactive lanes keep theirs).
-// No wait inside: lds_rows_wait (or any later s_waitcnt lgkmcnt(0) that precedes the first use) hands the rows over.
-__device__ __forceinline__ void lds_rows_wait(d2_t (&r)[4]) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : : "memory");
-}
-__device__ __forceinline__ void lds_rows_wait(d2_t (&r)[2]) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[0]), "+v"(r[1]) : : "memory");
-}
-__device__ __forceinline__ void lds_load_line(d2_t (&r0)[4], d2_t (&r1)[4], unsigned a) {     // 128 contiguous bytes: two rows of 8 dims
-    asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:16\n\tds_read_b128 %2, %8 offset:32\n\tds_read_b128 %3, %8 offset:48\n\t"
-                 "ds_read_b128 %4, %8 offset:64\n\tds_read_b128 %5, %8 offset:80\n\tds_read_b128 %6, %8 offset:96\n\t"
-                 "ds_read_b128 %7, %8 offset:112"
-                 : "+v"(r0[0]), "+v"(r0[1]), "+v"(r0[2]), "+v"(r0[3]), "+v"(r1[0]), "+v"(r1[1]), "+v"(r1[2]), "+v"(r1[3])
-                 : "v"(a) : "memory");
-}
-__device__ __forceinline__ void lds_load_two_half_rows(d2_t (&r0)[2], d2_t (&r1)[2], unsigned a) {   // two consecutive 32-byte rows
-    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\tds_read_b128 %3, %4 offset:48"
-                 : "+v"(r0[0]), "+v"(r0[1]), "+v"(r1[0]), "+v"(r1[1]) : "v"(a) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lds_load_row(d2_t (&r)[N], unsigned a);
-template <>
-__device__ __forceinline__ void lds_load_row<4>(d2_t (&r)[4], unsigned a) {
-    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\tds_read_b128 %3, %4 offset:48"
-                 : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : "v"(a) : "memory");
-}
-template <>
-__device__ __forceinline__ void lds_load_row<2>(d2_t (&r)[2], unsigned a) {
-    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16" : "+v"(r[0]), "+v"(r[1]) : "v"(a) : "memory");
 }
 
 // RCX: coarse rows per lane when not the strip kernels' own (Tile<DY>::RC) -- 2 for the RBF kernel at dyadic 0 with 8 staged dims,
@@ -279,11 +201,14 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     int c_u0m1 = (c_u0 + NUp - 1) % NUp;                                        // tm of the step BEFORE the lane starts a pair
     asm volatile("" : "+v"(c_u0), "+v"(c_uk0), "+v"(c_out), "+v"(c_kq), "+v"(c_kr), "+v"(c_u0m1));
     unsigned a_e;   // the odd rows are at a_e ^ 128: wave slices and slabs are 256-byte aligned, a slab row is 128 bytes
-    // ---- the wave's stream of pairs: position i of lane group g is pair cb[k] + g size(k) + off, (k, off) = chunk and offset of i.
-    // Pair indices are 32-bit here (the launcher refuses P >= 2^31 - 2^20); NOPAIR marks "no such pair".
+    // ---- the wave's stream of pairs, dealt in chunks: chunk 0 of a wave is fixed (C0 pairs per lane group from pair cb0 on), the
+    // rest is drawn CQ = 2^logC pairs per lane group at a time from prm.queue (nullptr: chunk 0 is the whole share).  Position i of
+    // lane group g is pair cb[k] + g size(k) + off, (k, off) = chunk and offset of i; NOPAIR marks "no such pair".
+    // k_fwd_prefix carries a COPY of this stream: as shared by-reference functions (sk_pair_stream.h) all 81 instances here changed
+    // at equal VGPR counts, e.g. <double, 0, 0, 0, 0, 0, 8> 2333 -> 2298 instructions at 145 VGPRs and its edge-keeping twin
+    // 2967 -> 2911 at 176; as a struct of references the 41 instances without edges swapped the scalars of tm and x_rd_off.
     // (The chunk bases are wave-uniform, but the compiler cannot see that through the atomic: readfirstlane says so, or they
     // live in VGPRs and every producer call computes its addresses with vector instructions.)
-    constexpr unsigned NOPAIR = 0xffffffffu;
     const unsigned P32 = (unsigned)prm.P;
     // pairs from here on keep no edges (the loss layout's triangle); worked out where it is needed, not kept in a scalar register
     auto edge_pairs = [&]() __attribute__((always_inline)) -> unsigned {
@@ -382,23 +307,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // ---- producers (uniform control; per-lane source offsets) ------------------------------------------------
     // y slab s = virtual units [8s, 8s+8) of every lane group: dims k = lane/8, unit x = lane%8
     // The producers run once per 8 macro-steps with wave-uniform control.  Their cursors advance incrementally (no division
-    // by NUp), and the pair -> (a, b) split uses 32-bit arithmetic whenever the pair count allows: the 64-bit division
-    // sequence is ~150 scalar instructions, and there are G of them per call.
-    // (the pairs of the triangular layouts -- symmetric Gram, loss layout -- come from a table [P][2] of int32 (a, b) that sk_prep_cat_*
-    // writes right BEHIND the staged columns: found from dYt, B and Ncp, which the producers hold anyway.  The triangle arithmetic
-    // inside this kernel -- a square root and two correction loops per look-up, inlined four times -- sat in the scalar registers of
-    // EVERY launch: 25 v_readlane / v_writelane in the headline variant against 17 without it, profiles/r05_ab_r04_vs_r05.txt)
-    auto split_ab = [&](int64_t p, bool want_b) __attribute__((always_inline)) -> int64_t {
-        if (prm.B <= 0) return p;
-        if (prm.tri) {
-            const int *tab = reinterpret_cast<const int *>(prm.dYt + prm.B * (int64_t)FD * prm.Ncp);
-            return (int64_t)tab[2 * p + (want_b ? 1 : 0)];
-        }
-        // (32-bit: the launcher refuses P >= 2^31 - 2^20, and B <= P in a Gram launch -- the 64-bit division sequence is ~150 scalar
-        // instructions, and it used to be inlined here twice for a case that cannot occur)
-        if (want_b) return (int64_t)((uint32_t)p % (uint32_t)prm.B);
-        return (int64_t)((uint32_t)p / (uint32_t)prm.B);
-    };
+    // by NUp); the pair -> (a, b) split and its tables of the triangular layouts: pair_split (sk_pair_stream.h).
+    auto split_ab = [&](int64_t p, bool want_b) __attribute__((always_inline)) -> int64_t { return pair_split<true, FD>(prm, p, want_b); };
     auto split_b = [&](int64_t p) -> int64_t { return split_ab(p, true); };
     auto split_a = [&](int64_t p) -> int64_t { return split_ab(p, false); };
     int y_pi = 0, y_u0 = 0, y_slot = 0, y_par = 0;   // next y slab: pair-in-group, first unit (NUp % 8 == 0: no straddling),
@@ -471,7 +381,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             for (int k = 0; k < RC; k += 2) lds_load_two_half_rows(dxq[k], dxq[k + 1], xa + k * (unsigned)XROW);
         } else {
 #pragma unroll
-            for (int k = 0; k < RC; ++k) lds_load_row<ND / 2>(dxq[k], xa + k * (unsigned)XROW);
+            for (int k = 0; k < RC; ++k) lds_load_row(dxq[k], xa + k * (unsigned)XROW);
         }
     };
     // RBF: node values of this lane's rows at the columns of units uk, uk + 1, uk + 2 (the last two filled this step), and
@@ -926,18 +836,10 @@ int launch_fused_nd(FusedParams prm, const FusedPlan &pl, hipStream_t s) {
     // (512 VGPRs per lane and SIMD; a variant over 168 holds two waves per SIMD, not three)
     // (a property of this variant's code object, the same on every gfx950 device: an immutable constant initialised once,
     // thread-safely, at the variant's first launch -- not mutable library state)
-    static const int vgprs = [&] {
-        hipFuncAttributes attr;
-        return hipFuncGetAttributes(&attr, (const void *)kern) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : 128;
-    }();
-    int waves_per_cu = pl.waves_per_cu;
-    const int by_regs = 4 * (512 / ((vgprs + 7) & ~7));
-    if (waves_per_cu > by_regs) waves_per_cu = by_regs;
-    if (waves_per_cu < 1) waves_per_cu = 1;
-    int64_t max_waves = (int64_t)device_cu_count() * waves_per_cu;
-    int64_t waves = (pl.P + pl.G - 1) / pl.G;
-    if (waves > max_waves) waves = max_waves;
-    int64_t per = (pl.P + waves * pl.G - 1) / (waves * pl.G);      // the equal share, pairs per lane group
+    static const int vgprs = variant_vgprs(kern, 128);
+    int waves_per_cu = waves_by_vgprs(pl.waves_per_cu, vgprs);
+    int64_t waves, per;
+    even_share(pl.P, pl.G, (int64_t)device_cu_count() * waves_per_cu, waves, per);
     if (per < 8 && waves_per_cu >= 8) {
         // A launch of a few pairs per lane group (no queue, see below): whole pairs do not divide evenly, every wave pays the
         // skew's fill (L - 1 + lag macro-steps) once, and fewer resident waves run faster each.  Take the resident waves per
@@ -966,44 +868,21 @@ int launch_fused_nd(FusedParams prm, const FusedPlan &pl, hipStream_t s) {
             const double cost = all * (double)on_simd * rate[on_simd] + (longest - all) * (double)big_on_simd * rate[big_on_simd > 0 ? big_on_simd : 1];
             if (best_q == 0 || cost < best * 0.98) { best = cost; best_q = q; }
         }
-        if (best_q && knobs().fused_wpc <= 0) {
-            waves_per_cu = 4 * best_q;
-            max_waves = (int64_t)device_cu_count() * waves_per_cu;
-            waves = (pl.P + pl.G - 1) / pl.G;
-            if (waves > max_waves) waves = max_waves;
-            per = (pl.P + waves * pl.G - 1) / (waves * pl.G);
-        }
+        if (best_q && knobs().fused_wpc <= 0) waves_per_cu = 4 * best_q;
     }
-    if (per > 0x1fffffff / pl.NUp) return SK_ERR_UNSUPPORTED;
-    // drawn chunks: small, but never so small that more than three of them are in flight between the producers' frontier and
-    // the last lane of the sweep (the kernel keeps a ring of four chunk bases)
-    if (pl.P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;           // (pair indices are 32-bit inside the kernel)
-    const int span = (pl.L - 1 + pl.lag + 24) / pl.NUp + 2;
-    int logC = 0;
-    while ((span >> logC) + 1 > 3) ++logC;
     const int pct = knobs().fused_q_static > 0 ? (knobs().fused_q_static > 100 ? 100 : knobs().fused_q_static)
                                                 : (int)cost_by_name(KIND == 1 ? "fused_static_share_rbf" : "fused_static_share_linear");
-    // ... and not smaller than needed either: ~24 draws per lane group balance a launch to a per cent or two, while every
-    // chunk costs each lane one look-up of its first pair (the variants that keep edges do that in the macro-step path)
-    while ((per * (100 - pct) / 100) >> (logC + 1) >= 24 && logC < 8) ++logC;
-    if (prm.queue && waves == max_waves && per >= (8 << logC) && pct < 100) {
-        // the launch fills the chip: `pct` per cent of the equal share is dealt out up front, the rest is drawn from the counter
-        prm.C0 = (int)(per * pct / 100);
-        prm.n_big = 0;
-        prm.logC = logC;
-        prm.q_first = waves * pl.G * (int64_t)prm.C0;
+    StreamPlan sp;
+    if (const int rc = plan_pair_stream(pl.P, pl.G, pl.NUp, pl.L, pl.lag, waves_per_cu, device_cu_count(), pct, prm.queue != nullptr, sp))
+        return rc;
+    const int64_t max_waves = (int64_t)device_cu_count() * waves_per_cu;
+    waves = sp.waves;
+    per = sp.per;
+    prm.C0 = sp.C0; prm.n_big = sp.n_big; prm.logC = sp.logC; prm.q_first = sp.q_first;
+    if (sp.queue) {
         if (hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
     } else {
-        // as even as whole pairs allow: every lane group takes floor(P / groups) pairs and the first n_big waves one more
-        // (128 x 128 symmetric pairs: 8256 = 4096 groups x 2 + 64 -- an equal share of 3 would run a third fewer waves
-        // for a third more macro-steps each)
-        const int64_t base = pl.P / (waves * pl.G), rem = pl.P - base * waves * pl.G;
         prm.queue = nullptr;
-        prm.C0 = (int)base;
-        prm.n_big = (int)((rem + pl.G - 1) / pl.G);
-        if (base == 0) waves = prm.n_big;                          // no more waves than the pairs need
-        prm.logC = logC;      // (the chunks after the first are all empty here, but the ring must not wrap onto the first)
-        prm.q_first = pl.P;
         // A launch that fills the chip with a dozen pairs per wave and more, but too few for the queue (a 64-row shard of the
         // headline Gram: 10.7 pairs per wave): shares by wave age rank, sized so that the waves of a SIMD finish together --
         // (share + the skew's fill) proportional to the measured issue shares of the ranks (SK_FUSED_RANK_W overrides them,
@@ -1124,41 +1003,29 @@ int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B,
     const bool four_dim = !g.naive && sizeof(TO) == 8 && D <= 4;
     const bool rbf0_two_rows = KIND == 1 && DY == 0 && !four_dim;
     if (rbf0_two_rows && strip_edges && (g.naive || sizeof(TO) != 8)) return SK_ERR_UNSUPPORTED;
-    // linear: one unit = two increment columns.  RBF: one unit = two NODE columns, and the sweep of a pair's last unit
-    // reads one node column of the following unit, which therefore has to exist as padding inside the pair's stream;
-    // likewise the lanes of a pair must cover M node rows, not M - 1 increment rows
-    const int NU = KIND == 1 ? (g.Nc + 2) / 2 : (g.Nc + 1) / 2;
-    const int rows = KIND == 1 ? g.Mc + 1 : g.Mc;
-    const int NUp = (NU + LINE_UNITS - 1) / LINE_UNITS * LINE_UNITS;
-    if (Ncp < NUp * 2 || (Ncp & 1)) return SK_ERR_UNSUPPORTED;
     // rows per lane: the strip kernels' own or twice that (fused_rcx, above -- the same rule the variant dispatch applies)
     const int nd_v = fused_nd(D, !g.naive && sizeof(TO) == 8);
     const int rcx = fused_rcx(KIND, DY, nd_v, strip_edges != nullptr, !g.naive && sizeof(TO) == 8);
     const int RC = rcx ? rcx : (DY == 0 ? 4 : DY == 1 ? 2 : 1);
     const bool doubled = rcx == 2 * (DY == 0 ? 4 : DY == 1 ? 2 : 1);
-    int logL = 3;
-    while (logL < 6 && (RC << logL) < rows) ++logL;
+    int logL_fixed = 0;
     if (rbf0_two_rows && strip_edges) {
         // the edges are read in the strip layout, whose padded rows (K constant along the zero increments of the padding) must all
         // be WRITTEN: this variant's lanes have to cover them -- twice the strip kernels' lanes
         const Strip st = strip_geom(rbf_edge_geom(g), 8);
         if (!st.ok || st.nb != 1 || st.logL > 5) return SK_ERR_UNSUPPORTED;
-        logL = st.logL + 1;
+        logL_fixed = st.logL + 1;
     }
-    const int L = 1 << logL;
-    if (L * RC < rows) return SK_ERR_UNSUPPORTED;   // more than one band per pair
-    if (Mrows < L * RC) return SK_ERR_UNSUPPORTED;
-    const int G = WAVE / L;
-    const int JMAX = (L + NUp - 1) / NUp;
-    const int nd = (!g.naive && sizeof(TO) == 8 && D <= 4) ? 4 : 8;   // the variant launch_fused_e picks
-    // shared-y pair order (FusedParams::shy_A): a plain Gram without edges and two or more lane groups per wave -- one y ring per wave
-    const bool shy = B > 0 && tri == 0 && !strip_edges && G >= 2 && A > 0 && A <= 0x7fffffff && g.P == A * B;
-    const int GY = shy ? 1 : G;
-    const int xw = x_window(KIND, nd, RC, strip_edges != nullptr);
-    const size_t lds_bytes = (size_t)GY * (((L >> 3) + 2) * y_slab_pitch(nd)) +
-                             (size_t)G * (X_SLOTS * JMAX * RC * xw * x_row_bytes(nd));   // (a multiple of 256: the y reads rely on 256-byte aligned slices)
-    const int64_t n_pos = shy ? (A + G - 1) / G * B : g.P;      // stream positions: pairs, or (shared-y) pairs of one lane group
-    if (lds_bytes > 160 * 1024) return SK_ERR_UNSUPPORTED;
+    const int nd = nd_v;   // the variant launch_fused_e picks
+    OneBandGeom og;
+    OneBandShape sh{};
+    sh.kind = KIND, sh.Mc = g.Mc, sh.Nc = g.Nc, sh.Mrows = Mrows, sh.Ncp = Ncp, sh.RC = RC, sh.nd = nd;
+    sh.edges = strip_edges != nullptr, sh.A = A, sh.B = B, sh.P = g.P, sh.tri = tri, sh.logL_fixed = logL_fixed;
+    if (const int rc = one_band_geometry(sh, og)) return rc;
+    const int NUp = og.NUp, logL = og.logL, L = og.L;
+    const bool shy = og.shy;
+    const size_t lds_bytes = og.lds_bytes;
+    const int64_t n_pos = og.n_pos;
 
     int waves_per_cu = (int)((160 * 1024) / lds_bytes);
     const int wpc_env = knobs().fused_wpc;
@@ -1173,7 +1040,7 @@ int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B,
     if (wpc_env > 0) waves_per_cu = waves_per_cu < wpc_env ? waves_per_cu : wpc_env;
     else if (waves_per_cu > 4) waves_per_cu &= ~3;   // whole four-wave workgroups
     if (waves_per_cu < 1) waves_per_cu = 1;
-    const FusedPlan pl{n_pos, GY, NUp, L, KIND == 1 ? 2 : 0, lds_bytes, waves_per_cu, rcx};
+    const FusedPlan pl{n_pos, og.GY, NUp, L, KIND == 1 ? 2 : 0, lds_bytes, waves_per_cu, rcx};
 
     FusedParams prm;
     prm.dXr = dXr; prm.dYt = dYt; prm.out = out; prm.edges = strip_edges; prm.P = n_pos; prm.B = B;

@@ -258,6 +258,9 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused_mb(const FusedMbParams p
     // ---- the wave's stream of pairs: positions 0 .. C0-1 are pairs wave_id C0 + i; every later position is one pair drawn from the
     // launch's counter (a pair is nb NUp >= 160 macro-steps long, the lanes' skew 63: at most two pairs are in flight, plus
     // the producers' look-ahead -- a ring of four).  Pair indices are 32-bit; NOPAIR = none.
+    // k_deriv_fused and the multi-band adjoints carry COPIES of this one-draw stream: as shared by-reference functions
+    // (sk_pair_stream.h) all 72 instances here changed, e.g. <double, 0, 0, 0, 16, 0, 4, 1> 238 -> 237 VGPRs, 2983 -> 2977
+    // instructions and <double, 0, 0, 0, 16, 0, 4, 0> 92 -> 90 SGPRs, 1705 -> 1694 instructions.
     constexpr unsigned NOPAIR = 0xffffffffu;
     const unsigned P32 = (unsigned)prm.P;
     const int C0 = prm.C0;
@@ -828,13 +831,8 @@ int launch_mb_one(FusedMbParams prm, int64_t P, size_t lds_bytes, int waves_per_
     auto kern = k_fwd_fused_mb<TO, DY, Y32, KIND, FD, EDGES, RCX, SPLIT>;
     // (a property of this variant's code object, the same on every gfx950 device: an immutable constant initialised once,
     // thread-safely, at the variant's first launch -- not mutable library state)
-    static const int vgprs = [&] {
-        hipFuncAttributes attr;
-        return hipFuncGetAttributes(&attr, (const void *)kern) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : 256;
-    }();
-    const int by_regs = 4 * (512 / ((vgprs + 7) & ~7));
-    if (waves_per_cu > by_regs) waves_per_cu = by_regs;
-    if (waves_per_cu < 1) waves_per_cu = 1;
+    static const int vgprs = variant_vgprs(kern, 256);
+    waves_per_cu = waves_by_vgprs(waves_per_cu, vgprs);
     const int64_t max_waves = (int64_t)device_cu_count() * waves_per_cu;
     int64_t waves = P < max_waves ? P : max_waves;
     if (P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;            // (pair indices are 32-bit inside the kernel)

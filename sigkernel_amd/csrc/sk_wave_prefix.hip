@@ -3,8 +3,10 @@
 //
 // The sweep is k_fwd_fused's without edges: the same staged arrays (sk_prep_pair_*), the same rings (y slabs and x windows by
 // LDS-DMA), the same increment formation and the same cell update in the same order, so node (M - 1, N - 1) of a pair is
-// bit for bit what sk_solve_fwd_{linear,rbf}_* return.  It is a copy and not more template parameters of that kernel because
+// bit for bit what sk_solve_fwd_{linear,rbf}_* return.  The STEP LOOP is a copy and not more template parameters of that kernel because
 // k_fwd_fused sits at its vector and scalar register limits; this one carries a per-lane output pointer and a column cursor more.
+// What surrounds the loop is shared with it (sk_pair_stream.h): the LDS read helpers, the pair -> (a, b) split, and on the host the
+// launch plan, the VGPR query and the geometry.  The chunked pair stream is a second copy as well (see there for why).
 // Always 8 staged dims, never the full-wave DPP form (lane 0 selects its 1.0 instead), no triangular pair tables; the stencil, the
 // output dtype and -- at dyadic 1 and 2 -- the static kernel are launch-time values: FOUR instances (the build's budget, tests/test_abi.py).
 //
@@ -40,17 +42,15 @@
 // Scope: kind 0 / 1, dim <= 8, one band per pair -- rows <= 64 RC with RC = 4 / 2 / 1 at dyadic 0 / 1 / 2, rows = M - 1 linear and
 // M rbf; rbf at dyadic 0 sweeps two rows per lane (rows <= 128: the four-row form with 8 staged dims spills) -- dyadic <= 2, any N.
 // PAIR ORDER, rings, producers: see sk_wave_fused.hip, whose comments are not repeated here.
-#include "sk_wave_common.h"
+#include "sk_pair_stream.h"
 #include <algorithm>
 
 namespace sk {
 namespace {
 
 constexpr int FD = 8, ND = 8;      // dims carried (inputs are zero-padded to 8)
-constexpr int Y_SLAB_PITCH = ND * 128;   // 8 dimension rows of 8 units; odd slabs swap each pair of rows (sk_wave_fused.hip)
-constexpr int X_SLOTS = 2, XROW = 64;
-// lanes per x window, as in k_fwd_fused without edges
-constexpr int x_window(int kind, int rc) { return (kind == 0 && rc == 4) ? 4 : 8; }
+constexpr int Y_SLAB_PITCH = y_slab_pitch(ND);   // 8 dimension rows of 8 units; odd slabs swap each pair of rows (sk_wave_fused.hip)
+constexpr int XROW = x_row_bytes(ND);
 
 struct PrefixParams {
     const double *dXr;   // [A][Mrows][8]: linear: kappa s^2 (x[p+1]-x[p]); rbf: x[p]  (sk_prep_pair_*, as sk_solve_fwd_{linear,rbf}_*)
@@ -67,52 +67,14 @@ struct PrefixParams {
     int u_f, lam_f;      // unit / lane of the last node (they end the wave's last pair)
     double inv_sigma;    // RBF: G = exp(-|x - y|^2 * inv_sigma)
     WaveGroup wg;
-    // the stream of pairs: chunk 0 of every wave is fixed (C0 pairs per lane group), the rest drawn 2^logC at a time from `queue`
-    // (sk_wave_fused.hip: FusedParams); queue == nullptr: the first n_big waves take C0 + 1 pairs per lane group
+    // the stream of pairs (sk_wave_fused.hip; the plan: plan_pair_stream): chunk 0 of every wave is fixed (C0 pairs per lane group), the
+    // rest drawn 2^logC at a time from `queue`; queue == nullptr: the first n_big waves take C0 + 1 pairs per lane group
     unsigned long long *queue;
     int64_t q_first;
     int C0, logC, n_big;
     int shy_A;           // > 0: SHARED-Y pair order (a Gram launch with G >= 2 lane groups): position q of lane group g is pair
                          // a = G (q / B) + g, b = q % B; P then counts positions, ceil(A / G) B
 };
-
-// y units of a macro-step: even dimensions at a_even + {0, 256, 512, 768}, odd ones at a_odd + the same.  No wait inside: issued at
-// the end of a macro-step for the next one; lds_dims_wait hands `t` over (tools/check_async_hazards.py lints the ISA for early uses)
-__device__ __forceinline__ void lds_read_dims_issue(d2_t (&t)[8], unsigned a_even, unsigned a_odd) {
-    asm volatile("ds_read_b128 %0, %8\n\t"
-                 "ds_read_b128 %1, %9\n\t"
-                 "ds_read_b128 %2, %8 offset:256\n\t"
-                 "ds_read_b128 %3, %9 offset:256\n\t"
-                 "ds_read_b128 %4, %8 offset:512\n\t"
-                 "ds_read_b128 %5, %9 offset:512\n\t"
-                 "ds_read_b128 %6, %8 offset:768\n\t"
-                 "ds_read_b128 %7, %9 offset:768"
-                 : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7])
-                 : "v"(a_even), "v"(a_odd)
-                 : "memory");
-}
-__device__ __forceinline__ void lds_dims_wait(d2_t (&v)[8], d2_t (&t)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]), "=v"(v[4]), "=v"(v[5]), "=v"(v[6]), "=v"(v[7])
-                 : "0"(t[0]), "1"(t[1]), "2"(t[2]), "3"(t[3]), "4"(t[4]), "5"(t[5]), "6"(t[6]), "7"(t[7])
-                 : "memory");
-}
-// x-row reloads straight into the row registers (read-write operands: under a divergent branch the inactive lanes keep theirs).
-// No wait inside: lds_rows_wait (or any later s_waitcnt lgkmcnt(0) that precedes the first use) hands the rows over.
-__device__ __forceinline__ void lds_rows_wait(d2_t (&r)[4]) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : : "memory");
-}
-__device__ __forceinline__ void lds_load_line(d2_t (&r0)[4], d2_t (&r1)[4], unsigned a) {     // 128 contiguous bytes: two rows of 8 dims
-    asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:16\n\tds_read_b128 %2, %8 offset:32\n\tds_read_b128 %3, %8 offset:48\n\t"
-                 "ds_read_b128 %4, %8 offset:64\n\tds_read_b128 %5, %8 offset:80\n\tds_read_b128 %6, %8 offset:96\n\t"
-                 "ds_read_b128 %7, %8 offset:112"
-                 : "+v"(r0[0]), "+v"(r0[1]), "+v"(r0[2]), "+v"(r0[3]), "+v"(r1[0]), "+v"(r1[1]), "+v"(r1[2]), "+v"(r1[3])
-                 : "v"(a) : "memory");
-}
-__device__ __forceinline__ void lds_load_row(d2_t (&r)[4], unsigned a) {
-    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\tds_read_b128 %3, %4 offset:48"
-                 : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]) : "v"(a) : "memory");
-}
 
 // RCX: coarse rows per lane when not the strip kernels' own (Tile<DY>::RC) -- 2 for the RBF kernel at dyadic 0, whose four-row form
 // with 8 staged dims spills
@@ -126,7 +88,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
     const int LAG = RBF ? 2 : 0;   // macro-steps by which the block sweep trails the node evaluation (sk_wave_fused.hip)
     constexpr int CW = 2;
     constexpr int RC = RCX ? RCX : Tile<DY>::RC, R = RC << DY, S = CW << DY, r = 1 << DY;
-    constexpr int XW = x_window(KIND, RC);   // lanes (= macro-steps) per x window: four only for the linear four-row form (dyadic 0)
+    constexpr int XW = x_window(KIND, ND, RC, false);   // lanes (= macro-steps) per x window: four only for the linear four-row form (dyadic 0)
     constexpr int XSLAB = RC * XW * XROW;    // XW lanes x RC rows
     extern __shared__ __attribute__((aligned(16))) char lds_block[];
     char *lds;
@@ -167,9 +129,10 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
     int c_u0m1 = (c_u0 + NUp - 1) % NUp;                                        // tm of the step BEFORE the lane starts a pair
     asm volatile("" : "+v"(c_u0), "+v"(c_uk0), "+v"(c_kq), "+v"(c_kr), "+v"(c_u0m1));
     unsigned a_e;   // the odd rows are at a_e ^ 128: wave slices and slabs are 256-byte aligned, a slab row is 128 bytes
-    // ---- the wave's stream of pairs: position i of lane group g is pair cb[k] + g size(k) + off, (k, off) = chunk and offset of i.
-    // Pair indices are 32-bit here (the launcher refuses P >= 2^31 - 2^20); NOPAIR marks "no such pair".
-    constexpr unsigned NOPAIR = 0xffffffffu;
+    // ---- the wave's stream of pairs: k_fwd_fused's chunked stream (the comments are there) with even shares or the queue, never
+    // rank shares.  A COPY: as shared by-reference functions (sk_pair_stream.h) all four instances changed -- 3213 / 2804 / 2987 /
+    // 2697 instructions became 3193 / 2759 / 2959 / 2669 and <1, 2, 0> went from 167 to 165 VGPRs (157 / 155 / 147 stayed); as a
+    // struct with the state by value 157 -> 159, 155 -> 157, 147 -> 148 VGPRs.
     const unsigned P32 = (unsigned)prm.P;
     const int w32 = __builtin_amdgcn_readfirstlane((int)wave_id);
     const int c0_ = prm.C0 + (w32 < prm.n_big ? 1 : 0);
@@ -237,11 +200,6 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
 
     // ---- producers (uniform control; per-lane source offsets): y slab s = virtual units [8s, 8s+8) of every lane group, dims
     // k = lane/8, unit x = lane%8; x windows for the lanes that start a pair during macro-steps [t0, t0+XW)
-    auto split_ab = [&](int64_t p, bool want_b) __attribute__((always_inline)) -> int64_t {
-        if (prm.B <= 0) return p;
-        if (want_b) return (int64_t)((uint32_t)p % (uint32_t)prm.B);
-        return (int64_t)((uint32_t)p / (uint32_t)prm.B);
-    };
     int y_pi = 0, y_u0 = 0, y_slot = 0, y_par = 0;   // next y slab: pair-in-group, first unit, ring slot, parity of the virtual slab number
     auto issue_y = [&]() __attribute__((always_inline)) {
         ensure(y_pi);
@@ -249,7 +207,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
         for (int g = 0; g < gy; ++g) {
             const unsigned sp = stream_pair(g, y_pi);
             const int64_t p = sp == NOPAIR ? 0 : (int64_t)sp;   // past the end: fetch something valid, never consumed
-            const int64_t b = split_ab(p, true);
+            const int64_t b = pair_split<false, FD>(prm, p, true);
             const int krow = (lane >> 3) ^ ((y_par + g) & 1);   // odd slabs (per group): dimension rows swapped in pairs
             const double *src = prm.dYt + ((b * FD + krow) * (int64_t)prm.Ncp + (int64_t)(y_u0 + (lane & 7)) * 2);
             __builtin_amdgcn_global_load_lds(src, (lds_void *)(lds + g * y_bytes + y_slot * Y_SLAB_PITCH), 16, 0, 0);
@@ -271,7 +229,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
             for (int g = 0; g < G; ++g) {
                 const unsigned sp = stream_pair(g, pi);
                 const int64_t p = sp == NOPAIR ? 0 : (int64_t)sp;
-                int64_t a = split_ab(p, false);
+                int64_t a = pair_split<false, FD>(prm, p, false);
                 a = a * gm + gs * g;
                 if (a >= a_lim) a = 0;
                 const char *src = reinterpret_cast<const char *>(prm.dXr + (a * prm.Mrows + (int64_t)lamj * RC) * FD);
@@ -639,45 +597,16 @@ template <int DY, int KIND>
 int launch_prefix_v(PrefixParams prm, const PrefixPlan &pl, hipStream_t s) {
     constexpr int RCX = (KIND == 1 && DY == 0) ? 2 : 0;
     auto kern = k_fwd_prefix<DY, KIND, RCX>;
-    // persistent waves: all of them must be resident at once, so the variant's VGPR count caps the waves per SIMD
-    static const int vgprs = [&] {
-        hipFuncAttributes attr;
-        return hipFuncGetAttributes(&attr, (const void *)kern) == hipSuccess && attr.numRegs > 0 ? attr.numRegs : 128;
-    }();
-    int waves_per_cu = pl.waves_per_cu;
-    const int by_regs = 4 * (512 / ((vgprs + 7) & ~7));
-    if (waves_per_cu > by_regs) waves_per_cu = by_regs;
-    if (waves_per_cu < 1) waves_per_cu = 1;
-    const int64_t max_waves = (int64_t)device_cu_count() * waves_per_cu;
-    int64_t waves = (pl.P + pl.G - 1) / pl.G;
-    if (waves > max_waves) waves = max_waves;
-    const int64_t per = (pl.P + waves * pl.G - 1) / (waves * pl.G);      // the equal share, pairs per lane group
-    if (per > 0x1fffffff / pl.NUp) return SK_ERR_UNSUPPORTED;
-    if (pl.P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;           // (pair indices are 32-bit inside the kernel)
-    // drawn chunks: never so small that more than three of them are in flight between the producers' frontier and the last lane of
-    // the sweep (the kernel keeps a ring of four chunk bases), and ~24 draws per lane group (sk_wave_fused.hip)
-    const int span = (pl.L - 1 + pl.lag + 24) / pl.NUp + 2;
-    int logC = 0;
-    while ((span >> logC) + 1 > 3) ++logC;
+    static const int vgprs = variant_vgprs(kern, 128);
     const int pct = (int)cost_by_name(prm.kind == 1 ? "fused_static_share_rbf" : "fused_static_share_linear");
-    while ((per * (100 - pct) / 100) >> (logC + 1) >= 24 && logC < 8) ++logC;
-    if (prm.queue && waves == max_waves && per >= (8 << logC) && pct < 100) {
-        // the launch fills the chip: `pct` per cent of the equal share is dealt out up front, the rest is drawn from the counter
-        prm.C0 = (int)(per * pct / 100);
-        prm.n_big = 0;
-        prm.logC = logC;
-        prm.q_first = waves * pl.G * (int64_t)prm.C0;
-        if (hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
-    } else {
-        // as even as whole pairs allow: every lane group takes floor(P / groups) pairs and the first n_big waves one more
-        const int64_t base = pl.P / (waves * pl.G), rem = pl.P - base * waves * pl.G;
-        prm.queue = nullptr;
-        prm.C0 = (int)base;
-        prm.n_big = (int)((rem + pl.G - 1) / pl.G);
-        if (base == 0) waves = prm.n_big;                          // no more waves than the pairs need
-        prm.logC = logC;      // (the chunks after the first are all empty here, but the ring must not wrap onto the first)
-        prm.q_first = pl.P;
-    }
+    StreamPlan sp;
+    if (const int rc = plan_pair_stream(pl.P, pl.G, pl.NUp, pl.L, pl.lag, waves_by_vgprs(pl.waves_per_cu, vgprs), device_cu_count(), pct,
+                                        prm.queue != nullptr, sp))
+        return rc;
+    const int64_t waves = sp.waves;
+    prm.C0 = sp.C0; prm.n_big = sp.n_big; prm.logC = sp.logC; prm.q_first = sp.q_first;
+    if (!sp.queue) prm.queue = nullptr;
+    else if (hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
     prm.wg = wave_group(pl.lds_bytes, waves, knobs().fused_wpb);
     const size_t lds_block = wave_group_lds(prm.wg);
     if (lds_block > 64 * 1024)
@@ -704,34 +633,21 @@ int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A,
     const int DY = g.dyadic;
     if (nodes < 0 || nodes > 3) return SK_ERR_BAD_ARG;
     if (!prefix_in_scope(kind, D, g.Mc, DY)) return SK_ERR_UNSUPPORTED;
-    // linear: one unit = two increment columns.  RBF: one unit = two NODE columns, and the sweep of a pair's last unit reads one node
-    // column of the following unit, which therefore has to exist as padding inside the pair's stream; likewise the lanes of a pair
-    // must cover M node rows, not M - 1 increment rows
-    const int NU = kind == 1 ? (g.Nc + 2) / 2 : (g.Nc + 1) / 2;
-    const int rows = kind == 1 ? g.Mc + 1 : g.Mc;
-    const int NUp = (NU + LINE_UNITS - 1) / LINE_UNITS * LINE_UNITS;
-    if (Ncp < NUp * 2 || (Ncp & 1)) return SK_ERR_UNSUPPORTED;
     const int RC = prefix_rc(kind, DY);
-    int logL = 3;
-    while (logL < 6 && (RC << logL) < rows) ++logL;
-    const int L = 1 << logL;
-    if (L * RC < rows) return SK_ERR_UNSUPPORTED;   // more than one band per pair
-    if (Mrows < L * RC) return SK_ERR_UNSUPPORTED;
-    const int G = WAVE / L;
-    const int JMAX = (L + NUp - 1) / NUp;
-    // shared-y pair order: a Gram launch with two or more lane groups per wave -- one y ring per wave
-    const bool shy = B > 0 && G >= 2 && A > 0 && A <= 0x7fffffff && g.P == A * B;
-    const int GY = shy ? 1 : G;
-    const int xw = x_window(kind, RC);
-    const size_t lds_bytes = (size_t)GY * (((L >> 3) + 2) * Y_SLAB_PITCH) + (size_t)G * (X_SLOTS * JMAX * RC * xw * XROW);   // (a multiple of 256)
-    const int64_t n_pos = shy ? (A + G - 1) / G * B : g.P;      // stream positions: pairs, or (shared-y) pairs of one lane group
-    if (lds_bytes > 160 * 1024) return SK_ERR_UNSUPPORTED;
+    OneBandGeom og;
+    OneBandShape sh{};   // (no edges, no triangular layouts, never a lane count of the caller's)
+    sh.kind = kind, sh.Mc = g.Mc, sh.Nc = g.Nc, sh.Mrows = Mrows, sh.Ncp = Ncp, sh.RC = RC, sh.nd = ND, sh.A = A, sh.B = B, sh.P = g.P;
+    if (const int rc = one_band_geometry(sh, og)) return rc;
+    const int NUp = og.NUp, logL = og.logL, L = og.L;
+    const bool shy = og.shy;
+    const size_t lds_bytes = og.lds_bytes;
+    const int64_t n_pos = og.n_pos;
     int waves_per_cu = (int)((160 * 1024) / lds_bytes);
     const int cap = DY == 0 ? 8 : 12;      // as the forward without stores (sk_wave_fused.hip)
     if (waves_per_cu > cap) waves_per_cu = cap;
     if (waves_per_cu > 4) waves_per_cu &= ~3;   // whole four-wave workgroups
     if (waves_per_cu < 1) waves_per_cu = 1;
-    const PrefixPlan pl{n_pos, GY, NUp, L, kind == 1 ? 2 : 0, lds_bytes, waves_per_cu};
+    const PrefixPlan pl{n_pos, og.GY, NUp, L, kind == 1 ? 2 : 0, lds_bytes, waves_per_cu};
 
     PrefixParams prm;
     prm.dXr = dXr; prm.dYt = dYt; prm.out = out; prm.ldo = ldo; prm.P = n_pos; prm.B = B;
