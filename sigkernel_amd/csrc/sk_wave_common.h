@@ -37,6 +37,46 @@ __device__ __forceinline__ double dpp_shr1_one(double v) {
     return __hiloint2double(hi, lo);
 }
 
+// v[i] = 1.0 in the lanes of `lanes`, every other lane keeps its value: S moves under a temporary EXEC instead of 2 S selects.
+// ALL 64 lanes must be active where this is called (the top level of a persistent wave's step loop): EXEC is set back to all ones,
+// not saved -- a saved copy would take a scalar register pair the step loops do not have.
+// (The neighbour exchange itself cannot run under that mask: a DPP move whose SOURCE lane is disabled by EXEC does not write its
+// destination on gfx9 -- there is no fetch-inactive control before gfx10 -- so lane 1 of a lane group would lose lane 0's value.)
+template <int S>
+__device__ __forceinline__ void set_one_in_lanes(double (&v)[S], unsigned long long lanes) {
+    static_assert(S == 2 || S == 4 || S == 8, "one v_mov_b64 per value");
+    if constexpr (S == 2) {
+        asm volatile("s_mov_b64 exec, %2\n\t"
+                     "v_mov_b64 %0, 1.0\n\t"
+                     "v_mov_b64 %1, 1.0\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(v[0]), "+v"(v[1])
+                     : "s"(lanes));
+    } else if constexpr (S == 4) {
+        asm volatile("s_mov_b64 exec, %4\n\t"
+                     "v_mov_b64 %0, 1.0\n\t"
+                     "v_mov_b64 %1, 1.0\n\t"
+                     "v_mov_b64 %2, 1.0\n\t"
+                     "v_mov_b64 %3, 1.0\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3])
+                     : "s"(lanes));
+    } else {
+        asm volatile("s_mov_b64 exec, %8\n\t"
+                     "v_mov_b64 %0, 1.0\n\t"
+                     "v_mov_b64 %1, 1.0\n\t"
+                     "v_mov_b64 %2, 1.0\n\t"
+                     "v_mov_b64 %3, 1.0\n\t"
+                     "v_mov_b64 %4, 1.0\n\t"
+                     "v_mov_b64 %5, 1.0\n\t"
+                     "v_mov_b64 %6, 1.0\n\t"
+                     "v_mov_b64 %7, 1.0\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7])
+                     : "s"(lanes));
+    }
+}
+
 __device__ __forceinline__ double dpp_shl1(double v, double fill) {
     // lane l receives lane l+1's value; lane 63 keeps `fill`
     int lo = __double2loint(v), hi = __double2hiint(v);

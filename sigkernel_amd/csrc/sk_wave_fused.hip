@@ -200,6 +200,12 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     int c_kq = floor_div(-lam - LAG, NUp), c_kr = (-lam - LAG) - c_kq * NUp;   // t - lam - LAG = (tq + c_kq) NUp + tm + c_kr
     int c_u0m1 = (c_u0 + NUp - 1) % NUp;                                        // tm of the step BEFORE the lane starts a pair
     asm volatile("" : "+v"(c_u0), "+v"(c_uk0), "+v"(c_out), "+v"(c_kq), "+v"(c_kr), "+v"(c_u0m1));
+    // The linear sweep without edges resets a lane's K state (left, corner) at the END of the step before the lane starts a pair, in the
+    // block that fetches its x rows (fetch_next): one exec-masked block per step instead of two.  Nothing reads the state in between.
+    // Not with one lane group per wave (corner is taken from ktop at the top of the step there), not for RBF (the sweep trails the
+    // reload by LAG steps), not with the per-lane cursors: those keep their two blocks and the step's order as they were (the
+    // full-wave RBF instance of 512 x 512 pairs of 64 points at dyadic 2 measured 0.4 % slower with the reordered counter alone).
+    constexpr bool RESET_AT_END = !CUR && !RBF && !FULLWAVE && !MID;
     unsigned a_e;   // the odd rows are at a_e ^ 128: wave slices and slabs are 256-byte aligned, a slab row is 128 bytes
     // ---- the wave's stream of pairs, dealt in chunks: chunk 0 of a wave is fixed (C0 pairs per lane group from pair cb0 on), the
     // rest is drawn CQ = 2^logC pairs per lane group at a time from prm.queue (nullptr: chunk 0 is the whole share).  Position i of
@@ -291,7 +297,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             have += 1;
         }
     };
-    const bool is_top = lam == 0;
+    const unsigned long long top_lanes = __builtin_amdgcn_ballot_w64(lam == 0);   // the first lane of every lane group (all lanes are active)
     const unsigned my_y = lds0 + (shy ? 0u : (unsigned)grp * y_bytes);
     const unsigned y_lim = my_y + y_bytes;
     const unsigned ring_bytes = FULLWAVE ? (unsigned)(((WAVE >> 3) + 2) * Y_SLAB_PITCH) : y_bytes;   // = y_bytes, as a literal when L = 64
@@ -495,6 +501,19 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         }
     }
     if (AHEAD) read_y();
+    // RESET_AT_END: the top row of the NEXT step's block is taken at the end of a step, before the pair-start reset -- bot[S-1] and
+    // left[R-1] are one value and stay one register that way (taken at the top of the step it would need a copy per step)
+    double top[S];
+#pragma unroll
+    for (int i = 0; i < S; ++i) top[i] = 1.0;
+    auto take_top = [&]() __attribute__((always_inline)) {
+        // Every lane takes its neighbour's value (lane 0 a zero: no `old` operand to keep or set up), then the first lane of every
+        // lane group is set to 1.0 under an EXEC mask: S moves where the selects `lam == 0 ? 1.0 : shifted` were 2 S v_cndmask, and
+        // no register is held across the loop edge for lane 0's sake.
+#pragma unroll
+        for (int i = 0; i < S; ++i) top[i] = dpp_shr1_zero(bot[i]);
+        set_one_in_lanes(top, top_lanes);
+    };
     for (int t = 0; t < t_end; ++t) {
         if (EDGES) {   // the edge values of the previous macro-step, straight from the state registers
             double *const ep = e_ptr;
@@ -515,7 +534,6 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         }
 
         // -- top row of the block from the lane above
-        double top[S];
         if (FULLWAVE) {   // lane 0 keeps the 1.0 of the persistent `old` register ktop[i] (see sk_wave.hip)
             // corner = the previous step's last top value, taken before the DPP overwrites it.  (An opaque move: left to the
             // compiler, the copy is made three times over.)
@@ -525,27 +543,15 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
                 ktop[i] = dpp_shr1(bot[i], ktop[i]);
                 top[i] = ktop[i];
             }
-        } else {
-            // KTOP_KEPT: into the persistent ktop as well -- the DPP's `old` operand is then a register that is live anyway (a fresh 1.0
-            // per value is two moves per value and macro-step); the tops of the other lane groups are selected as before.  It costs 2 S
-            // VGPRs, so only the doubled-row variants take it: their LDS holds them to two waves per SIMD whatever the registers (one
-            // exception: linear with 8 dims and edges at dyadic 2 would drop from three waves to two)
-            constexpr bool KTOP_KEPT = RCX != 0 && RCX == 2 * Tile<DY>::RC && !(KIND == 0 && ND == 8 && DY == 2);
-#pragma unroll
-            for (int i = 0; i < S; ++i) {
-                if constexpr (KTOP_KEPT) {
-                    ktop[i] = dpp_shr1(bot[i], ktop[i]);
-                    top[i] = is_top ? 1.0 : ktop[i];
-                } else {
-                    const double sh = dpp_shr1(bot[i], 1.0);
-                    top[i] = is_top ? 1.0 : sh;
-                }
-            }
+        } else if constexpr (!RESET_AT_END) {
+            take_top();
         }
 
         // -- start of a pair: left boundary K[i][0] = 1, and this lane's x rows.  Without edges the rows were fetched during the
         // previous macro-step (below); the wait for the y units hands them over.
-        if constexpr (!CUR) {
+        if constexpr (RESET_AT_END) {
+            // (done at the end of the previous step, in fetch_next)
+        } else if constexpr (!CUR) {
             if (tm == (RBF ? c_uk0 : c_u0)) {
                 asm volatile("");   // a real branch: if-converted, the five moves become ten v_cndmask in every macro-step
                 corner = 1.0;
@@ -651,18 +657,25 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         auto fetch_next = [&]() {
             const bool turn = ((t + 1) & (XW - 1)) == 0;   // the next step opens an x window (and, every eighth step, a y slab for
             if (__builtin_expect(turn, 0)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // lane 0): their DMA was issued XW (8) steps ago
-            a_e += 16;
+            // (in place: as `a_e += 16` the sum lands in a second register and is copied back at the loop edge)
+            asm("v_add_u32 %0, 16, %0" : "+v"(a_e));
             if (((t + 1) & 7) == lam7) {   // next slab: the other parity, one slab less one row on, wrapping at the end of the ring
                 asm volatile("");          // (a real branch: if-converted, the update costs two more VALU instructions per step)
                 const unsigned e = (a_e + (unsigned)(Y_SLAB_PITCH - 128)) ^ 128u;
                 a_e = e - (e >= y_lim ? ring_bytes : 0u);
             }
             read_y();
-            if (tm == c_u0m1) {
+            // this lane starts a pair in the next step (RESET_AT_END: tm is the NEXT step's already -- see "advance" -- and c_u0m1 is dead)
+            if (RESET_AT_END ? tm == c_u0 : tm == c_u0m1) {
                 load_x_rows(my_x + (turn ? x_rd_off ^ (unsigned)(JMAX * XSLAB) : x_rd_off));
                 if constexpr (!INFLIGHT_X) {
 #pragma unroll
                     for (int k = 0; k < RC; ++k) lds_rows_wait(dxq[k]);
+                }
+                if constexpr (RESET_AT_END) {   // left boundary K[i][0] = 1 of the new pair
+                    corner = 1.0;
+#pragma unroll
+                    for (int i = 0; i < R; ++i) left[i] = 1.0;
                 }
             }
         };
@@ -715,7 +728,13 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             }
             bot[cc] = above;
         }
-        if (!FULLWAVE) corner = top[S - 1];
+        if constexpr (RESET_AT_END) {
+            // (an opaque move, as in the full-wave branch: left to the compiler, the copy is made twice over)
+            asm volatile("v_mov_b64 %0, %1" : "=v"(corner) : "v"(top[S - 1]));
+            take_top();   // for macro-step t + 1
+        } else if (!FULLWAVE) {
+            corner = top[S - 1];
+        }
 
         if (EDGES) {
             const bool pair_ok = ep_cur != nullptr;
@@ -766,9 +785,13 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
 
         // -- advance
         if constexpr (!CUR) {
-            if constexpr (!MID) fetch_next();
+            if constexpr (!MID && !RESET_AT_END) fetch_next();
             tm += 1;
             if (tm == NUp) { tm = 0; tq += 1; }
+            if constexpr (RESET_AT_END) {
+                asm volatile("" : "+s"(tq));   // stays a scalar counter (compared in the store branch only, it is kept per lane otherwise: two VALU per step)
+                fetch_next();
+            }
         }
         if (CUR && RBF) {
             uk += 1;
