@@ -4,7 +4,10 @@ examples/time_series_classification.py:94 and :189-202 (transform -> compute_Gra
 kernel='precomputed', hyper-parameters by cross-validated grid search), on synthetic two-class paths: the UCR/UEA data
 sets the reference downloads through tslearn are not available offline.
 
-    python examples/time_series_classification.py [--n-train 120] [--n-test 80] [--length 60]
+    python examples/time_series_classification.py [--n-train 120] [--n-test 80] [--length 60] [--ragged]
+
+--ragged: the variable-length variant -- every series is cut at a random length in [length / 2, length], the batch is padded by
+pad_paths and the Gram matrices come from compute_Gram_ragged.
 
 Class 0: Brownian paths with a slow sinusoidal drift; class 1: the same noise with the drift's frequency doubled.
 Runs on an MI355X (the Gram matrices come from the HIP kernels; there is no CPU fallback).
@@ -33,17 +36,22 @@ def make_dataset(n, length, seed, noise=0.35):
 
 
 def fit_signature_svc(x_train, y_train, device, sigmas=(0.25, 0.5, 1.0), at=True, ll=False, scale=0.1, dyadic_order=0,
-                      cv=5, dtype=torch.float64):
+                      cv=5, dtype=torch.float64, lens=None):
     """Grid search over the RBF sigma of the static kernel and the SVC's C, as the reference does
     (examples/time_series_classification.py:150-202).  Returns (best cv score, sigma, fitted GridSearchCV, train tensor)."""
     from sklearn.model_selection import GridSearchCV
     from sklearn.svm import SVC
+    if lens is not None and ll:
+        raise ValueError("lens count the points of the untransformed series: the lead-lag transform changes the length")
     x_train = x_train / np.abs(x_train).max()                                    # :88
     xt = sigkernel.transform(torch.tensor(x_train, dtype=dtype, device=device), at=at, ll=ll, scale=scale)   # :94
     best = (-1.0, None, None)
     for sigma in sigmas:
         signature_kernel = sigkernel.SigKernel(sigkernel.RBFKernel(sigma=sigma), dyadic_order=dyadic_order)     # :186-189
-        G_train = signature_kernel.compute_Gram(xt, xt, sym=True).cpu().numpy()                                # :192
+        if lens is None:
+            G_train = signature_kernel.compute_Gram(xt, xt, sym=True).cpu().numpy()                            # :192
+        else:       # series of unequal length, padded at their ends
+            G_train = signature_kernel.compute_Gram_ragged(xt, xt, lens, lens, sym=True).cpu().numpy()
         svc = SVC(kernel="precomputed", decision_function_shape="ovo")                                         # :195
         model = GridSearchCV(estimator=svc, param_grid={"C": np.logspace(0, 4, 5)}, cv=cv, n_jobs=1)           # :196
         model.fit(G_train, y_train)                                                                            # :197
@@ -53,12 +61,31 @@ def fit_signature_svc(x_train, y_train, device, sigmas=(0.25, 0.5, 1.0), at=True
 
 
 def predict(model, sigma, xt_train, x_test, x_train_max, device, at=True, ll=False, scale=0.1, dyadic_order=0,
-            dtype=torch.float64):
+            dtype=torch.float64, lens_test=None, lens_train=None):
     """Test-vs-train Gram matrix and the SVC's predictions (examples/time_series_classification.py:262-281)."""
+    if lens_test is not None and ll:
+        raise ValueError("lens count the points of the untransformed series: the lead-lag transform changes the length")
     xs = sigkernel.transform(torch.tensor(x_test / x_train_max, dtype=dtype, device=device), at=at, ll=ll, scale=scale)
     signature_kernel = sigkernel.SigKernel(sigkernel.RBFKernel(sigma=sigma), dyadic_order=dyadic_order)
-    G_test = signature_kernel.compute_Gram(xs, xt_train, sym=False).cpu().numpy()
+    if lens_test is None:
+        G_test = signature_kernel.compute_Gram(xs, xt_train, sym=False).cpu().numpy()
+    else:
+        G_test = signature_kernel.compute_Gram_ragged(xs, xt_train, lens_test, lens_train).cpu().numpy()
     return model.predict(G_test)
+
+
+def cut_and_pad(x, seed):
+    """Cut every series of x (n, length, channels) at a random length in [length / 2, length] and pad the batch back to `length`
+    (pad_paths repeats the last point; the padding never reaches a result).  Returns the padded array and the lengths."""
+    if x.ndim != 3:
+        raise ValueError("x must have shape (n, length, channels)")
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(x.shape[1] // 2, x.shape[1] + 1, size=x.shape[0])
+    padded, lens_t = sigkernel.pad_paths([torch.tensor(x[i, :n]) for i, n in enumerate(lens)])
+    # train and test keep ONE padded length (the original): transform(at=True) adds time as linspace(0, 1, padded length), so its step
+    # -- part of every path's increments -- must be the same in both sets
+    tail = padded[:, -1:].expand(-1, x.shape[1] - padded.shape[1], -1)
+    return torch.cat((padded, tail), dim=1).numpy(), lens_t
 
 
 def main():
@@ -66,14 +93,22 @@ def main():
     ap.add_argument("--n-train", type=int, default=120)
     ap.add_argument("--n-test", type=int, default=80)
     ap.add_argument("--length", type=int, default=60)
+    ap.add_argument("--ragged", action="store_true", help="series of unequal length: pad_paths -> compute_Gram_ragged(sym=True) -> SVC")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("this example needs an MI355X (sigkernel_amd has no CPU path)")
     device = torch.device("cuda", 0)
     x_train, y_train = make_dataset(args.n_train, args.length, seed=0)
     x_test, y_test = make_dataset(args.n_test, args.length, seed=1)
-    score, sigma, model, xt = fit_signature_svc(x_train, y_train, device)
-    pred = predict(model, sigma, xt, x_test, np.abs(x_train).max(), device)
+    if args.ragged:
+        # (the transform -- time as a channel -- acts point by point, so it commutes with the padding)
+        x_train, len_train = cut_and_pad(x_train, seed=2)
+        x_test, len_test = cut_and_pad(x_test, seed=3)
+        score, sigma, model, xt = fit_signature_svc(x_train, y_train, device, lens=len_train)
+        pred = predict(model, sigma, xt, x_test, np.abs(x_train).max(), device, lens_test=len_test, lens_train=len_train)
+    else:
+        score, sigma, model, xt = fit_signature_svc(x_train, y_train, device)
+        pred = predict(model, sigma, xt, x_test, np.abs(x_train).max(), device)
     acc = float(np.mean(pred == y_test))
     print("signature PDE kernel + SVC: cv accuracy %.3f (sigma %.2f, C %g), test accuracy %.3f"
           % (score, sigma, model.best_params_["C"], acc))

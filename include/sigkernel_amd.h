@@ -449,6 +449,31 @@ int sk_solve_prefix_nodes_rbf_f64(const double *Xr, const double *Yt, int64_t A,
                                   int dyadic, int scheme, double inv_sigma, int nodes, double *out, int64_t ldo, void *queue, void *stream);
 int sk_solve_prefix_nodes_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                                   int dyadic, int scheme, double inv_sigma, int nodes, float *out, int64_t ldo, void *queue, void *stream);
+/* ONE NODE per pair: batches of paths of unequal length, padded at their ends to a common length (any finite values).  The same sweep
+ * of the same kernel over the padded pair, storing only
+ *     out[p] = k_sig(x_a[:len_x[a]], y_b[:len_y[b]])        (node (len_x[a] - 1, len_y[b] - 1) of pair p's grid, bit for bit)
+ * p = a B + b for a Gram launch (B > 0), p = a = b for a paired one (B == 0): A B resp. A elements, nothing else is written and nothing
+ * of size pairs x (Mc + 1) x (Nc + 1) exists.  A pair with len_x[a] == 1 or len_y[b] == 1 -- value exactly 1 -- is NOT written: the
+ * caller fills `out` with ones before the call.
+ *   out: aligned to its element size (4 / 8 bytes), as any float * / double * is: the kernel keeps a row number in the two low bits of
+ *   out + p.
+ *   len_x: A device int32 point counts; len_y: B of them (paired launch: A, indexed by the pair).  Both required (SK_ERR_BAD_ARG).
+ *   The lengths are NOT validated on the device: the caller guarantees 1 <= len_x[a] <= Mc + 1 and 1 <= len_y[b] <= Nc + 1.  A length
+ *   outside that range leaves the pair's element unwritten or holding another node of the pair; nothing is accessed out of bounds, the
+ *   only address formed is out + p.
+ * Other arguments, scope and errors: as sk_solve_prefix_*.  SK_NODES_AT names the kernel's store mode; sk_solve_prefix_nodes_* does not
+ * accept it (it has no length arguments). */
+#define SK_NODES_AT 4
+int sk_solve_prefix_at_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                  int dyadic, int scheme, const int *len_x, const int *len_y, double *out, void *queue, void *stream);
+int sk_solve_prefix_at_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                  int dyadic, int scheme, const int *len_x, const int *len_y, float *out, void *queue, void *stream);
+int sk_solve_prefix_at_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                               int dyadic, int scheme, double inv_sigma, const int *len_x, const int *len_y, double *out, void *queue,
+                               void *stream);
+int sk_solve_prefix_at_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                               int dyadic, int scheme, double inv_sigma, const int *len_x, const int *len_y, float *out, void *queue,
+                               void *stream);
 /* The truncated signature kernel of Kiraly and Oberhauser as ONE sweep per pair (replaces truncated_sig_kernel, transformers.py:201-236:
  * six-dimensional numpy arrays shifted by a spline filter): out[a][b] = sigma[0] + sum_{m = 1 .. num_levels} sigma[m] * (sum of level m's
  * planes over the step grid of (x_a, y_b)); the rows of the paths are used as STEPS (no differencing); order = num_levels (or < 1) is the

@@ -83,6 +83,10 @@ SIGNATURES = {
     "sk_solve_prefix_nodes_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_nodes_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_nodes_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _vp, _i64, _vp, _vp]),
+    "sk_solve_prefix_at_linear_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "sk_solve_prefix_at_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "sk_solve_prefix_at_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "sk_solve_prefix_at_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sk_truncated_gram_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_truncated_gram_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_prep_pair_f64": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
@@ -595,6 +599,50 @@ class HipBackend:
             out[..., 0, :] = 1      # the one-point prefix of x: the kernel stores rows m >= 1 (with their column 0)
         else:
             out[..., 0] = 1         # k of two one-point prefixes / of one against a whole path: the kernel stores elements >= 1
+        return out
+
+    def solve_prefix_at(self, kind, param, X, Y, len_x, len_y, dyadic, naive, gram):
+        """Batches of paths of unequal length in ONE fused sweep (sk_solve_prefix_at_{linear,rbf}_*, the prefix kernel's store mode
+        SK_NODES_AT): out[a, b] = k_sig(X[a, :len_x[a]], Y[b, :len_y[b]]) -- (A, B) for gram, (A,) paired -- in the dtype of X, every
+        value bit for bit node (len_x[a] - 1, len_y[b] - 1) of solve_prefix_fused's grid.  X (A, M, D) / Y (B, N, D) are padded at the
+        end to common lengths; len_x (A,) / len_y (B,): int32 tensors on the paths' device with 1 <= len <= M resp. N (the CALLER's
+        check: the kernel does not validate them).  `out` is filled with ones here: the kernel stores nothing for a pair with a
+        one-point path.  Staged as solve_prefix_fused stages; nothing of size pairs x M x N exists.  Returns None outside the kernel's
+        scope (sk_route_query(SK_OP_PREFIX) != FUSED) -- the caller tiles static_increments + solve_fwd(want_grid=True)."""
+        _dev(X, "X")
+        _dev(Y, "Y")
+        A, M, D = X.shape
+        B, N = Y.shape[0], Y.shape[1]
+        Mc, Nc = M - 1, N - 1
+        if Mc < 1 or Nc < 1 or (kind == 1 and not float(param) > 0) or \
+                self.route(OP_PREFIX, kind, D, M, N, dyadic, naive, X.element_size()) != ROUTE_FUSED:
+            return None
+        for name, t, n in (("len_x", len_x, A), ("len_y", len_y, B)):
+            if t.dtype != torch.int32 or t.device != X.device or tuple(t.shape) != (n,) or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous int32 tensor of shape (%d,) on %s" % (name, n, X.device))
+        out = torch.ones((A, B) if gram else (A,), dtype=X.dtype, device=X.device)
+        if A == 0 or (gram and B == 0):
+            return out
+        Mrows = _stage_rows(kind, M, gram)
+        Ncp = ((Nc if kind == 0 else N) + 15) // 16 * 16
+        dev = X.device
+        scheme = SCHEME_NAIVE if naive else SCHEME_DEFAULT
+        lib = load()
+        pairs = A * B if gram else A
+        fn = getattr(lib, "sk_solve_prefix_at_" + ("linear_" if kind == 0 else "rbf_") + _suffix(X))
+        with _device(dev):
+            if kind == 0:
+                kappa = float(lib.sk_linear_prescale(int(dyadic)))
+                dXr, dYt = _prep_pair(X, Y, True, kappa * float(param) ** 2, Mrows, Ncp)
+                rc = fn(_ptr(dXr), _ptr(dYt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, _ptr(len_x), _ptr(len_y),
+                        _ptr(out), _ptr(_queue(dev, pairs)), _stream(X))
+            else:
+                Xr, Yt = _prep_pair(X, Y, False, 1.0, Mrows, Ncp)
+                rc = fn(_ptr(Xr), _ptr(Yt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, 1.0 / float(param),
+                        _ptr(len_x), _ptr(len_y), _ptr(out), _ptr(_queue(dev, pairs)), _stream(X))
+        if rc == 2:
+            return None
+        _check(rc, "sk_solve_prefix_at")
         return out
 
     def truncated_gram(self, X, Y, num_levels, sigma, order):

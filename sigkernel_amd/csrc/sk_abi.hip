@@ -155,6 +155,19 @@ int solve_prefix(int kind, const double *Xr, const double *Yt, int64_t A, int64_
     return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, ldo, queue, (hipStream_t)stream, nodes);
 }
 
+// node (len_x[a] - 1, len_y[b] - 1) of every pair's prefix grid alone (sk_wave_prefix.hip, store mode SK_NODES_AT)
+template <typename TO>
+int solve_prefix_at(int kind, const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
+                    int scheme, double inv_sigma, const int *len_x, const int *len_y, TO *out, void *queue, void *stream) {
+    if (D < 1 || !Xr || !Yt || !out || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
+    if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
+    if (kind == 1 && (!(inv_sigma > 0.0) || !(inv_sigma < 1e300))) return SK_ERR_BAD_ARG;
+    if (!len_x || !len_y) return SK_ERR_BAD_ARG;
+    if (A == 0) return SK_OK;
+    const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
+    return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, 1, queue, (hipStream_t)stream, SK_NODES_AT, len_x, len_y);
+}
+
 // the truncated signature kernel's Gram matrix (sk_truncated.hip); argument checks before any HIP call
 template <typename TO>
 int truncated_gram(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
@@ -485,6 +498,25 @@ int sk_solve_prefix_nodes_rbf_f64(const double *Xr, const double *Yt, int64_t A,
 int sk_solve_prefix_nodes_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                                   int dyadic, int scheme, double inv_sigma, int nodes, float *out, int64_t ldo, void *queue, void *stream) {
     return solve_prefix<float>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, queue, stream, nodes);
+}
+
+int sk_solve_prefix_at_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                  int dyadic, int scheme, const int *len_x, const int *len_y, double *out, void *queue, void *stream) {
+    return solve_prefix_at<double>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, len_x, len_y, out, queue, stream);
+}
+int sk_solve_prefix_at_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                  int dyadic, int scheme, const int *len_x, const int *len_y, float *out, void *queue, void *stream) {
+    return solve_prefix_at<float>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, len_x, len_y, out, queue, stream);
+}
+int sk_solve_prefix_at_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                               int dyadic, int scheme, double inv_sigma, const int *len_x, const int *len_y, double *out, void *queue,
+                               void *stream) {
+    return solve_prefix_at<double>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, len_x, len_y, out, queue, stream);
+}
+int sk_solve_prefix_at_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                               int dyadic, int scheme, double inv_sigma, const int *len_x, const int *len_y, float *out, void *queue,
+                               void *stream) {
+    return solve_prefix_at<float>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, len_x, len_y, out, queue, stream);
 }
 
 size_t sk_solve_fwd_static_workspace_bytes(int kind, int64_t P, int Mc, int Nc, int dyadic, int D) {

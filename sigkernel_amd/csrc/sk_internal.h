@@ -179,9 +179,11 @@ int launch_fwd_fused_rbf(const double *Xr, const double *Yt, int64_t A, int64_t 
 // ---- sk_wave_prefix.hip: the one-band fused forward that stores every coarse node (prefix kernels) ----
 // kind 0: dXr / dYt as launch_fwd_fused_linear; kind 1: as launch_fwd_fused_rbf.  out: pair p's (Mc + 1) x (Nc + 1) grid at out + p ldo;
 // nodes = SK_NODES_DIAGONAL / _LAST_ROW / _LAST_COL: only that slice of it, min(Mc, Nc) + 1 / Nc + 1 / Mc + 1 elements at out + p ldo.
+// nodes = SK_NODES_AT: node (len_x[a] - 1, len_y[b] - 1) of pair (a, b) alone, at out + p; len_x / len_y: device int32, required.
 template <typename TO>
 int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s, int nodes = 0);
+                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s, int nodes = 0, const int *len_x = nullptr,
+                      const int *len_y = nullptr);
 bool prefix_in_scope(int kind, int D, int Mc, int dyadic);   // the kernel's scope = the SK_OP_PREFIX rule of sk_route_query
 
 // ---- sk_truncated.hip: the truncated signature kernel of Kiraly and Oberhauser, all levels in one sweep of the step grid ----

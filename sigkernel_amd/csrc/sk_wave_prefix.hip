@@ -38,6 +38,16 @@
 // (padding rows, padding columns, stream positions without a pair); element 0 -- exactly 1 in all three -- is the host's fill.  The
 // sweep is the same code: every stored value is bit for bit the node the full grid holds there.  The slice modes branch around the
 // full grid's store block (one scalar branch per macro-step), so that block and its registers are as they were.
+//   4  NODES AT     out[p] = k(x[:len_x[a]], y[:len_y[b]]): ONE node per pair, (len_x[a] - 1, len_y[b] - 1) of its grid -- batches of
+//      paths of unequal length, padded at the end to a common (M, N).  The wave sweeps the padded pair as ever; where the sweep enters a
+//      pair the lane loads the two lengths (two global loads in a block that runs once per pair and lane).  n_cols -- per launch Nc in
+//      every other mode -- becomes the pair's own len_y[b] - 1; the lane that holds row len_x[a] - 1 gets o_ptr = out + p with that row's
+//      k < RC in the pointer's two low bits (elements are 4 or 8 bytes and `out` is aligned to them), every other lane nullptr.  The
+//      store is the intersection of the last row's and the last column's conditions: that lane, row k, the node column with
+//      col + q + 1 == n_cols.  o_rows stays the launch's (a per-pair o_rows costs registers across the loop: profiles/r12_ragged.txt).
+//      A pair with a one-point path stores nothing (its value, exactly 1, is the host's fill of the whole of `out`); a length outside
+//      [1, padded length] stores nothing or another node of the pair, never elsewhere: the only address formed is out + p.  No
+//      per-lane state is added to the step loop.
 //
 // Scope: kind 0 / 1, dim <= 8, one band per pair -- rows <= 64 RC with RC = 4 / 2 / 1 at dyadic 0 / 1 / 2, rows = M - 1 linear and
 // M rbf; rbf at dyadic 0 sweeps two rows per lane (rows <= 128: the four-row form with 8 staged dims spills) -- dyadic <= 2, any N.
@@ -63,7 +73,9 @@ struct PrefixParams {
     int Mc, Nc, NUp, logL;
     int kind, naive, f32;   // static kernel (0 linear, 1 rbf), first-order stencil, nodes stored as float
     int defer, wide;        // the store scheme (see THE STORE above): stores issued behind the window's DMA wait; shifted two-column pieces
-    int slice;              // SK_NODES_*: 0 the full grid; 1 / 2 / 3: only the diagonal / the last row / the last column (see SLICES above)
+    int slice;              // SK_NODES_*: 0 the full grid; 1 / 2 / 3: only the diagonal / the last row / the last column; 4: one node per
+                            // pair, (len_x[a] - 1, len_y[b] - 1) (see SLICES above)
+    const int *len_x, *len_y;   // slice 4: points per path, [A] and [B] (paired launch: [A], indexed by the pair); nullptr otherwise
     int u_f, lam_f;      // unit / lane of the last node (they end the wave's last pair)
     double inv_sigma;    // RBF: G = exp(-|x - y|^2 * inv_sigma)
     WaveGroup wg;
@@ -125,9 +137,11 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
     const int lam7 = lam & 7;
     int tm = 0, tq = 0;
     int c_u0 = lam % NUp, c_uk0 = (lam + LAG) % NUp;
-    int c_kq = floor_div(-lam - LAG, NUp), c_kr = (-lam - LAG) - c_kq * NUp;   // t - lam - LAG = (tq + c_kq) NUp + tm + c_kr
+    // t - lam - LAG = (tq + c_kq) NUp + tm + c_kr with c_kr = (NUp - c_uk0) % NUp: the remainder is not held, tm + c_kr wrapped into
+    // [0, NUp) is tm - c_uk0 wrapped (a VGPR less across the loop: <1, 2, 0> sits AT the three-wave line, profiles/r12_ragged.txt)
+    int c_kq = floor_div(-lam - LAG, NUp);
     int c_u0m1 = (c_u0 + NUp - 1) % NUp;                                        // tm of the step BEFORE the lane starts a pair
-    asm volatile("" : "+v"(c_u0), "+v"(c_uk0), "+v"(c_kq), "+v"(c_kr), "+v"(c_u0m1));
+    asm volatile("" : "+v"(c_u0), "+v"(c_uk0), "+v"(c_kq), "+v"(c_u0m1));
     unsigned a_e;   // the odd rows are at a_e ^ 128: wave slices and slabs are 256-byte aligned, a slab row is 128 bytes
     // ---- the wave's stream of pairs: k_fwd_fused's chunked stream (the comments are there) with even shares or the queue, never
     // rank shares.  A COPY: as shared by-reference functions (sk_pair_stream.h) all four instances changed -- 3213 / 2804 / 2987 /
@@ -336,6 +350,24 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
                         if (prm.f32) reinterpret_cast<float *>(o_ptr)[k] = (float)cand[k][q];
                         else reinterpret_cast<double *>(o_ptr)[k] = cand[k][q];
                     }
+        } else if (slice == 4) {
+            // the pair's end node: only the lane that holds its row has a pointer, the row k in its low bits; both columns are selected
+            // before the column test (the select chain inside the test leaves <0, 0, 0> a private segment)
+            asm volatile("");
+            const int at = (int)(reinterpret_cast<uintptr_t>(o_ptr) & 3);
+            char *const o = reinterpret_cast<char *>(reinterpret_cast<uintptr_t>(o_ptr) & ~(uintptr_t)3);
+            double v0 = cand[0][0], v1 = cand[0][1];
+#pragma unroll
+            for (int k = 1; k < RC; ++k) {
+                v0 = k == at ? cand[k][0] : v0;
+                v1 = k == at ? cand[k][1] : v1;
+            }
+            const int dc = n_cols - col;
+            if (dc == 1 || dc == 2) {
+                const double v = dc == 2 ? v1 : v0;
+                if (prm.f32) *reinterpret_cast<float *>(o) = (float)v;
+                else *reinterpret_cast<double *>(o) = v;
+            }
         } else {
             // last column: grid column Nc = node column Nc - 1 of the sweep
 #pragma unroll
@@ -428,7 +460,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
             for (int i = 0; i < R; ++i) left[i] = 1.0;
 #pragma unroll
             for (int k = 0; k < RC; ++k) prev[k] = 1.0;
-            const int pv = tq + c_kq + (tm + c_kr >= NUp ? 1 : 0);
+            const int pv = tq + c_kq + (tm != 0 ? 1 : 0);   // (tm == c_uk0 here: tm + c_kr is 0 or NUp)
             unsigned pair_u = stream_pair(grp, pv);
             const int sA = shy_a();
             if (sA > 0 && pair_u != NOPAIR) {   // position -> this lane group's pair: a = G (q / B) + grp, b = q % B, out index a B + b
@@ -437,10 +469,30 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
             }
             // (a slice: see store_slice -- the same address arithmetic with a pitch of 1 or 0 in place of the grid's, all scalar)
             const int sl = prm.slice;
-            const int64_t o_pitch = sl == 0 ? pitch : sl == 2 ? 0 : 1, o_first = sl == 0 || sl == 2 ? 1 : 0;
+            // (slice 4: the pair's one element, ldo = 1)
+            const int64_t o_pitch = sl == 0 ? pitch : (sl == 2 || sl == 4) ? 0 : 1, o_first = sl == 0 || sl == 2 ? 1 : 0;
             o_ptr = (pair_u != NOPAIR && o_rows > 0)
                         ? static_cast<char *>(prm.out) + ((int64_t)pair_u * prm.ldo + (int64_t)(1 + lam * RC) * o_pitch + o_first) * esz
                         : nullptr;
+            if (sl == 4) {
+                // the pair's own end node in place of the launch's: out index a B + b (Gram, either pair order) or the pair (paired).
+                // The lane's first row is re-derived from the lane number behind an opaque zero, as the diagonal's store does: lam RC
+                // held for this block alone is a register across the loop
+                asm volatile("");
+                int lx = 0, ly = 0;
+                if (pair_u != NOPAIR) {
+                    unsigned a = pair_u, b = pair_u;
+                    if (prm.B > 0) { a = pair_u / (unsigned)prm.B; b = pair_u - a * (unsigned)prm.B; }
+                    lx = prm.len_x[a];
+                    ly = prm.len_y[b];
+                }
+                int z = 0;
+                asm volatile("" : "+s"(z));
+                const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z));
+                const int at_k = (lx - 2) - (ln & ((1 << prm.logL) - 1)) * RC;
+                n_cols = ly - 1;
+                o_ptr = (pair_u != NOPAIR && at_k >= 0 && at_k < RC) ? static_cast<char *>(prm.out) + ((int64_t)pair_u * esz + at_k) : nullptr;
+            }
         }
 
         // -- y differences of the two coarse columns of this macro-step, all 8 dims
@@ -541,8 +593,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
         // Stores count in vmcnt like the DMA, and loads and stores do not return in order among each other, so the window's DMA
         // wait below is vmcnt(0): stored HERE, the last step of a window pays its stores' whole round trip in that wait; DEFERRED,
         // they are issued behind it (end of the loop body) and have a whole window to land.
-        int uk_now = tm + c_kr;
-        uk_now -= uk_now >= NUp ? NUp : 0;
+        int uk_now = tm - c_uk0;
+        uk_now += uk_now < 0 ? NUp : 0;
         if (prm.slice != 0) {      // (the launcher clears defer and wide then: nothing of the full grid's block runs)
             asm volatile("");   // a real branch around the full grid's stores
             store_slice(cand, uk_now);
@@ -625,13 +677,17 @@ bool prefix_in_scope(int kind, int D, int Mc, int dyadic) {
 }
 
 // KIND 0: dXr [A][Mrows][8] / dYt [Bn][8][Ncp] are path differences; KIND 1: the same layouts hold the path points.
-// nodes: 0 the full grid (ldo >= (Mc + 1) (Nc + 1)); 1 / 2 / 3 the diagonal / last row / last column alone (ldo >= its length).
+// nodes: 0 the full grid (ldo >= (Mc + 1) (Nc + 1)); 1 / 2 / 3 the diagonal / last row / last column alone (ldo >= its length);
+// 4 (SK_NODES_AT): node (len_x[a] - 1, len_y[b] - 1) of every pair alone, out + p (ldo is not used), len_x [A] / len_y [B] (paired: [A])
+// device int32.  The wave sweeps the padded pair whatever the lengths: the plan is the padded shape's.
 // SK_ERR_UNSUPPORTED outside the kernel's scope.
 template <typename TO>
 int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s, int nodes) {
+                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s, int nodes, const int *len_x, const int *len_y) {
     const int DY = g.dyadic;
-    if (nodes < 0 || nodes > 3) return SK_ERR_BAD_ARG;
+    if (nodes < 0 || nodes > 4) return SK_ERR_BAD_ARG;
+    if (nodes == 4 && (!len_x || !len_y)) return SK_ERR_BAD_ARG;
+    if (nodes == 4) ldo = 1;
     if (!prefix_in_scope(kind, D, g.Mc, DY)) return SK_ERR_UNSUPPORTED;
     const int RC = prefix_rc(kind, DY);
     OneBandGeom og;
@@ -658,6 +714,8 @@ int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A,
     const int mode = knobs().prefix_store > 0 ? knobs().prefix_store : PREFIX_STORE_DEFAULT;
     const bool can_wide = ((g.Nc + 1) & 1) == 0 && (ldo & 1) == 0 && ((uintptr_t)out % (2 * sizeof(TO))) == 0;
     prm.slice = nodes;
+    prm.len_x = nodes == 4 ? len_x : nullptr;
+    prm.len_y = nodes == 4 ? len_y : nullptr;
     // (a slice is stored direct, one element at a time: the deferred scheme and the two-column pieces belong to the full grid)
     prm.defer = nodes == 0 && mode >= 2;
     prm.wide = nodes == 0 && mode >= 3 && can_wide;
@@ -676,8 +734,8 @@ int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A,
 }
 
 template int launch_fwd_prefix<double>(int, const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double, double *,
-                                       int64_t, void *, hipStream_t, int);
+                                       int64_t, void *, hipStream_t, int, const int *, const int *);
 template int launch_fwd_prefix<float>(int, const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double, float *,
-                                      int64_t, void *, hipStream_t, int);
+                                      int64_t, void *, hipStream_t, int, const int *, const int *);
 
 }  // namespace sk

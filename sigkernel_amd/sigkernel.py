@@ -19,7 +19,7 @@ from . import _lib
 from ._routes import routes
 from .static_kernels import LinearKernel, RBFKernel
 
-__all__ = ["SigKernel", "_SigKernel", "_SigKernelGram", "k_kgrad"]
+__all__ = ["SigKernel", "_SigKernel", "_SigKernelGram", "k_kgrad", "pad_paths"]
 
 _DEFAULT_WORKSPACE = 48 << 30  # bytes of transient HBM one call may use (288 GB part)
 
@@ -1027,6 +1027,91 @@ def _prefix_grid(be, static_kernel, Xd, Yd, dyadic, naive, gram, workspace_bytes
     return out
 
 
+def _prefix_at(be, static_kernel, Xd, Yd, lx, ly, dyadic, naive, gram, workspace_bytes):
+    """out[a, b] = k_sig(x_a[:lx[a]], y_b[:ly[b]]) -- (A, B) for gram, (A,) paired -- for paths padded at their ends to common lengths;
+    lx / ly: validated int32 lengths on the paths' device.  The fused prefix kernel storing ONE node per pair where the library says so
+    (sk_route_query(SK_OP_PREFIX); the same `routes` switches as _prefix_grid): nothing of size pairs x M x N exists.  Else the pieces
+    of _prefix_grid's fallback over row tiles within the budget -- increments, the streaming solver's full grid, its coarse nodes --
+    with the node of every pair gathered from a tile's grid before the tile is dropped."""
+    A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
+    B = Yd.shape[0] if gram else 1
+    shape = (A, Yd.shape[0]) if gram else (A,)
+    if M < 2 or N < 2 or A == 0 or B == 0:      # one-point paths: every kernel is 1; empty batches: empty results
+        return torch.ones(shape, dtype=Xd.dtype, device=Xd.device)
+    fused = _fused_static(static_kernel, gram)
+    if fused is not None and hasattr(be, "solve_prefix_at") and not routes.no_fused_prefix and \
+            not (fused[0] == 1 and routes.no_fused_rbf):
+        # (the back-end asks sk_route_query(SK_OP_PREFIX) and returns None where the library names the streamed route)
+        out = be.solve_prefix_at(fused[0], fused[1], Xd.contiguous(), Yd.contiguous(), lx, ly, dyadic, naive, gram)
+        if out is not None:
+            return out
+    out = torch.empty(shape, dtype=Xd.dtype, device=Xd.device)
+    r = 1 << dyadic
+    ix, iy = lx.long() - 1, ly.long() - 1
+    per_row = B * ((M - 1) * (N + 16) + (((M - 1) << dyadic) + 1) * (((N - 1) << dyadic) + 1)) * Xd.element_size()
+    for a0, a1 in _tiles(A, per_row, _budget(Xd.device, workspace_bytes)):
+        inc = _increments(be, static_kernel, Xd[a0:a1], Yd if gram else Yd[a0:a1], gram=gram)
+        _, grid, _ = be.solve_fwd(inc, dyadic, naive, want_grid=True)
+        coarse = grid[..., ::r, ::r]
+        rows = torch.arange(a1 - a0, device=Xd.device)
+        if gram:
+            out[a0:a1] = coarse[rows[:, None], torch.arange(B, device=Xd.device)[None, :], ix[a0:a1, None], iy[None, :]]
+        else:
+            out[a0:a1] = coarse[rows, ix[a0:a1], iy[a0:a1]]
+        del inc, grid, coarse
+    return out
+
+
+class _Lengths:
+    """Lengths that _lengths has checked: the int32 tensor on the paths' device and the host copy (one transfer, one check per call of a
+    public method, however many Gram matrices it takes)."""
+    __slots__ = ("dev", "host", "count", "padded")
+
+    def __init__(self, name, lens, count, padded, device):
+        self.count, self.padded = count, padded
+        self.dev, self.host = _lengths(name, lens, count, padded, device, True)
+
+
+def _lengths(name, lens, count, padded, device, with_host=False):
+    """The point counts of a ragged batch, checked ONCE on the host -- `count` integers in [1, padded] -- and returned as a contiguous
+    int32 tensor on `device`.  ValueError naming the argument otherwise.  A _Lengths (already checked) passes through."""
+    if isinstance(lens, _Lengths):
+        if lens.count != count or lens.padded != padded:
+            raise ValueError("%s: %d lengths checked against a padded length of %d do not fit %d paths of %d points"
+                             % (name, lens.count, lens.padded, count, padded))
+        return lens.dev
+    t = lens if torch.is_tensor(lens) else torch.as_tensor(list(lens))
+    if t.numel() == 0 and not torch.is_tensor(lens):
+        t = t.to(torch.int64)
+    if t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError("%s must hold integers (an integer tensor or a sequence of ints), not %s" % (name, t.dtype))
+    if t.dim() != 1 or t.shape[0] != count:
+        raise ValueError("%s must hold one length per path: expected shape (%d,), got %s" % (name, count, tuple(t.shape)))
+    host = t.detach().to("cpu", torch.int64)
+    if count and (int(host.min()) < 1 or int(host.max()) > padded):
+        raise ValueError("%s must lie in [1, %d] (the padded length), got values from %d to %d" % (name, padded, int(host.min()), int(host.max())))
+    dev = host.to(torch.int32).to(device).contiguous()
+    return (dev, host) if with_host else dev
+
+
+def pad_paths(paths):
+    """A list of (len_i, dim) tensors -> (X (batch, max len, dim), lens (batch,) int64): every path padded at its END by repeating its
+    last point, for ``SigKernel.compute_Gram_ragged`` / ``compute_kernel_ragged`` / ``compute_mmd_ragged`` (which never read the
+    padding: any finite values would do).  ``X[i, :lens[i]]`` is path i again."""
+    paths = list(paths)
+    if not paths:
+        raise ValueError("pad_paths needs at least one path")
+    for p in paths:
+        if not torch.is_tensor(p) or p.dim() != 2 or p.shape[0] < 1:
+            raise ValueError("every path must be a tensor of shape (length >= 1, dim)")
+        if p.shape[1] != paths[0].shape[1] or p.dtype != paths[0].dtype or p.device != paths[0].device:
+            raise ValueError("all paths must share dim, dtype and device")
+    lens = torch.tensor([p.shape[0] for p in paths], dtype=torch.int64)
+    L = int(lens.max())
+    X = torch.stack([torch.cat((p, p[-1:].expand(L - p.shape[0], -1))) for p in paths])
+    return X, lens
+
+
 class _NoGradCtx:
     """What the autograd Functions' forward needs of a context when no gradient can be asked for: the call skips
     torch.autograd.Function.apply (a quarter of the host time of a C1-sized call) and returns the same values."""
@@ -1137,6 +1222,61 @@ class SigKernel:
         K_XX_m = (torch.sum(K_XX, dim=(0, 1)) - torch.sum(torch.diagonal(K_XX, dim1=0, dim2=1), dim=-1)) / (A * (A - 1.))
         K_YY_m = (torch.sum(K_YY, dim=(0, 1)) - torch.sum(torch.diagonal(K_YY, dim1=0, dim2=1), dim=-1)) / (B * (B - 1.))
         return K_XX_m + K_YY_m - 2. * torch.mean(K_XY, dim=(0, 1))
+
+    def _ragged(self, X, Y, len_x, len_y, gram, what):
+        f = self._on_features()
+        if f is not None:
+            return f[0]._ragged(f[1](X), f[1](Y), len_x, len_y, gram, what)
+        _check_inputs(X, Y, paired=not gram)
+        if self.process_group is not None:
+            raise NotImplementedError("%s is not sharded over a process group; call it on a SigKernel without process_group" % what)
+        if _wants_grad(X, Y):
+            raise NotImplementedError("%s is forward only: gradients of ragged batches are not built.  Call it under torch.no_grad() "
+                                      "or on detached paths" % what)
+        lx = _lengths("len_x", len_x, X.shape[0], X.shape[1], X.device)
+        ly = _lengths("len_y", len_y, Y.shape[0], Y.shape[1], Y.device)
+        return _prefix_at(_lib.get_backend(), self.static_kernel, X.detach(), Y.detach(), lx, ly, self.dyadic_order, self._naive_solver,
+                          gram, self.workspace_bytes)
+
+    def compute_Gram_ragged(self, X, Y, len_x, len_y, sym=False, max_batch=100):
+        """Gram matrix of two batches of paths of UNEQUAL length: X (batch_X, Lx, dim), Y (batch_Y, Ly, dim) hold the paths padded at
+        their ends to common lengths (``pad_paths``; any finite padding), len_x (batch_X,) / len_y (batch_Y,) their point counts ->
+        (batch_X, batch_Y): out[a, b] = k(X^a[:len_x[a]], Y^b[:len_y[b]]) -- node (len_x[a] - 1, len_y[b] - 1) of
+        ``compute_Gram_prefixes``'s grid, bit for bit: one sweep of the padded pairs by the fused prefix kernel that stores that one node
+        per pair (dim <= 8, one band per pair; else gathered from row tiles of the streaming solver's grid within ``workspace_bytes``):
+        the (batch_X, batch_Y, Lx, Ly) tensor is never built.  A path of one point gives exactly 1.  The values past a path's length
+        never reach its result.  The lengths are integer tensors (any device) or sequences of ints, checked once on the host: a wrong
+        count, a non-integer dtype or a value outside [1, padded length] raises ``ValueError``.  ``sym=True`` requires ``Y is X`` and equal lengths; every pair is computed and the matrix then symmetrised
+        (K + K^T) / 2.  Forward only.  A sweep costs what the PADDED shape costs: sort or bucket by length first where lengths vary a
+        lot.  ``max_batch`` is accepted and ignored, as elsewhere."""
+        if sym:
+            if Y is not X:
+                raise ValueError("sym=True needs Y is X")
+            if len_y is not len_x and X.dim() >= 2:
+                len_x = _Lengths("len_x", len_x, X.shape[0], X.shape[1], X.device)
+                len_y = _Lengths("len_y", len_y, X.shape[0], X.shape[1], X.device)
+                if not torch.equal(len_x.host, len_y.host):
+                    raise ValueError("sym=True needs len_y equal to len_x")
+        K = self._ragged(X, Y, len_x, len_y, True, "compute_Gram_ragged")
+        return 0.5 * (K + K.transpose(0, 1)) if sym else K
+
+    def compute_kernel_ragged(self, X, Y, len_x, len_y, max_batch=100):
+        """The paired form of ``compute_Gram_ragged``: X (batch, Lx, dim), Y (batch, Ly, dim), len_x / len_y (batch,) -> (batch,):
+        out[i] = k(X^i[:len_x[i]], Y^i[:len_y[i]])."""
+        return self._ragged(X, Y, len_x, len_y, False, "compute_kernel_ragged")
+
+    def compute_mmd_ragged(self, X, len_x, Y, len_y, max_batch=100):
+        """``compute_mmd``'s unbiased MMD^2 estimator on two samples of paths of unequal length (padded as for
+        ``compute_Gram_ragged``): three ragged Gram matrices, K_XX and K_YY without their diagonals.  Forward only."""
+        if X.dim() >= 2 and Y.dim() >= 2:      # (a feature map keeps batch and length: axes 0 and 1)
+            len_x = _Lengths("len_x", len_x, X.shape[0], X.shape[1], X.device)
+            len_y = _Lengths("len_y", len_y, Y.shape[0], Y.shape[1], Y.device)
+        K_XX = self.compute_Gram_ragged(X, X, len_x, len_x, sym=True, max_batch=max_batch)
+        K_YY = self.compute_Gram_ragged(Y, Y, len_y, len_y, sym=True, max_batch=max_batch)
+        K_XY = self.compute_Gram_ragged(X, Y, len_x, len_y, sym=False, max_batch=max_batch)
+        K_XX_m = (torch.sum(K_XX) - torch.sum(torch.diag(K_XX))) / (K_XX.shape[0] * (K_XX.shape[0] - 1.))
+        K_YY_m = (torch.sum(K_YY) - torch.sum(torch.diag(K_YY))) / (K_YY.shape[0] * (K_YY.shape[0] - 1.))
+        return K_XX_m + K_YY_m - 2. * torch.mean(K_XY)
 
     def compute_kernel_and_derivatives_Gram(self, X, Y, gamma, max_batch=100):
         """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim), gamma (batch_X, len_x, dim) -> three (batch_X, batch_Y)
