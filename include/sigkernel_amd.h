@@ -485,6 +485,16 @@ int sk_truncated_gram_f64(const double *Xr, const double *Yt, int64_t A, int64_t
                           int num_levels, int order, const double *sigma, double *out, void *stream);
 int sk_truncated_gram_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                           int num_levels, int order, const double *sigma, float *out, void *stream);
+/* The same sweep on P PAIRS: out[p] = the truncated kernel of (x_p, y_p) -- what a normalised kernel k(x, y) / sqrt(k(x, x) k(y, y))
+ * needs of every path, without the P x P matrix around it.  A launch-time mode of the Gram kernel's instances: each lane group of a wave
+ * takes a pair of its own and keeps that pair's y block in LDS (the groups are widened until the blocks of a wave fit its 16 KB).
+ *   Xr [P][Mrows][fd] / Yt [P][fd][Ncp], sigma, order and the _f32 rule as above;  out [P].
+ * Forward only.  The scope is the Gram entry points': SK_ERR_UNSUPPORTED outside sk_route_query(SK_OP_TRUNCATED, ...) == SK_ROUTE_FUSED;
+ * for SK_ROUTE_FUSED_SWAP call it on (y, x): the recursion is symmetric, so the values need no transposing. */
+int sk_truncated_paired_f64(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
+                            int order, const double *sigma, double *out, void *stream);
+int sk_truncated_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
+                            int order, const double *sigma, float *out, void *stream);
 /* Symmetric Gram matrix of ONE path batch with the fused kernels above: only the A (A + 1) / 2 pairs on and above the diagonal are
  * solved (what the reference's CPU solver does for sym=True, cython_backend.pyx:74-97; its GPU path ignores `sym`), in ONE launch,
  * and each value is written to out[a][b] and out[b][a]: out [A][A] is exactly symmetric.  dXr / dXt (Xr / Xt): the row-major and

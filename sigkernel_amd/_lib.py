@@ -89,6 +89,8 @@ SIGNATURES = {
     "sk_solve_prefix_at_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sk_truncated_gram_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_truncated_gram_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "sk_truncated_paired_f64": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "sk_truncated_paired_f32": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_prep_pair_f64": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_prep_pair_f32": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_solve_fwd_static_workspace_bytes": (_sz, [_int, _i64, _int, _int, _int, _int]),
@@ -655,6 +657,17 @@ class HipBackend:
         if truncated.truncated_route(X.shape[2], X.shape[1], Y.shape[1], num_levels, order, X.element_size()) != ROUTE_FUSED:
             return None
         return truncated._truncated_hip(X, Y, int(num_levels), [float(v) for v in sigma], int(order))
+
+    def truncated_paired(self, X, Y, num_levels, sigma, order):
+        """The truncated signature kernel of the P pairs (X[p], Y[p]), (P,), by the same kernel in its paired mode (sk_truncated_paired_*): one
+        pair per lane group, nothing of size P x P.  None outside the kernel's scope, as truncated_gram: FUSED_SWAP is the caller's call on
+        (Y, X) -- the values need no transposing -- and STREAM its torch restatement."""
+        from . import truncated
+        _dev(X, "X")
+        _dev(Y, "Y")
+        if truncated.truncated_route(X.shape[2], X.shape[1], Y.shape[1], num_levels, order, X.element_size()) != ROUTE_FUSED:
+            return None
+        return truncated._truncated_hip(X, Y, int(num_levels), [float(v) for v in sigma], int(order), paired=True)
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):
         """The loss wrappers' forward in THREE launches (csrc/sk_loss.hip): [X; Y] staged in both layouts straight from the two

@@ -178,6 +178,16 @@ int truncated_gram(const double *Xr, const double *Yt, int64_t A, int64_t B, int
     return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream);
 }
 
+// ... and its paired values, the same kernel instances in their paired mode
+template <typename TO>
+int truncated_paired(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels, int order,
+                     const double *sigma, TO *out, void *stream) {
+    if (D < 1 || !Xr || !Yt || !out || !sigma || P < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D)
+        return SK_ERR_BAD_ARG;
+    if (P == 0) return SK_OK;
+    return launch_truncated<TO>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream, 1);
+}
+
 }  // namespace
 
 // ---- the one place that reads the environment: SK_* tuning knobs, parsed when the library is loaded ------------------------
@@ -473,6 +483,14 @@ int sk_truncated_gram_f64(const double *Xr, const double *Yt, int64_t A, int64_t
 int sk_truncated_gram_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                           int num_levels, int order, const double *sigma, float *out, void *stream) {
     return truncated_gram<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
+}
+int sk_truncated_paired_f64(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
+                            int order, const double *sigma, double *out, void *stream) {
+    return truncated_paired<double>(Xr, Yt, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
+}
+int sk_truncated_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
+                            int order, const double *sigma, float *out, void *stream) {
+    return truncated_paired<float>(Xr, Yt, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
 }
 int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream) {

@@ -21,6 +21,11 @@
 // b = q % B, so a wave stages one y block per position q.  Every pair of a launch costs exactly the same (one M, N, level count), so
 // the positions are dealt out statically (wave w takes q = w, w + waves, ...): a work counter would have nothing to even out.
 // Padding rows and columns have G = 0 and therefore contribute nothing; no lane is ever masked.
+// PAIRED mode (TruncParams::paired, launch-time and wave-uniform): a launch of P pairs (x_p, y_p), out[p].  Lane group g of position q
+// takes pair p = G q + g and needs ITS OWN y block, at ylds + g fd Ncp: the y blocks of consecutive pairs are consecutive in Yt, so the
+// wave stages those of its live groups as one run.  A lane's block never changes during a position, so the lane reads through a pointer
+// to it that is formed before the step loop: the loop issues the instructions it issues in Gram mode, where the pointer is ylds itself.
+// The launch widens the groups until G fd Ncp doubles fit the wave's 16 KB; lanes beyond the rows of x hold zero rows.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
 // order (1: one plane per level, or TR_OMAX) and the rows per lane.
 #include "sk_wave_common.h"
@@ -35,15 +40,16 @@ constexpr int TR_LDS_DOUBLES = 2048;  // y block of a wave: fd x Ncp doubles, 16
 struct TruncParams {
     const double *Xr;   // [A][Mrows][fd]
     const double *Yt;   // [B][fd][Ncp]
-    void *out;          // [A][B], double or float
+    void *out;          // [A][B], double or float; paired: [A]
     int64_t A, B, n_pos;
     int Mrows, Ncp, fd, M, N, L, order, logW, out_f32;
+    int paired;         // 0: the Gram matrix of A x B pairs; 1: the A = B pairs (x_p, y_p), one per lane group
     double sigma[TR_LMAX + 1];
 };
 
 template <int OM, int RC>
 __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
-    extern __shared__ __attribute__((aligned(16))) double ylds[];   // [fd][Ncp]
+    extern __shared__ __attribute__((aligned(16))) double ylds[];   // [fd][Ncp]; paired: [G][fd][Ncp], one block per lane group
     constexpr int O1 = OM > 1 ? OM - 1 : 1;
     constexpr int NS = TR_LMAX - 1;      // levels that feed a next one
     const int lane = threadIdx.x;
@@ -52,14 +58,26 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     const int N = prm.N, Ncp = prm.Ncp, L = prm.L, ord = prm.order, fd = prm.fd;
     const bool wide = fd > 8;
     const int steps = N + W - 1;
+    const bool paired = prm.paired != 0;
     for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
-        const int64_t at = pos / prm.B, b = pos - at * prm.B;
-        const int64_t a = at * G + grp;
+        int64_t a, b;           // the lane group's row of Xr; the first y block the wave stages
+        int nblk = 1;           // ... and how many: one per live group in paired mode
+        if (paired) {
+            b = pos * G;
+            a = b + grp;
+            nblk = prm.A - b < G ? (int)(prm.A - b) : G;
+        } else {
+            const int64_t at = pos / prm.B;
+            b = pos - at * prm.B;
+            a = at * G + grp;
+        }
         const bool live = a < prm.A;
+        // the y block the lane reads: its group's (a dead group reads block 0, which is always staged)
+        const double *yl = ylds + ((paired && live) ? grp * fd * Ncp : 0);
         __syncthreads();
         {
             const double *yb = prm.Yt + b * (int64_t)fd * Ncp;
-            for (int k = lane; k < fd * Ncp; k += WAVE) ylds[k] = yb[k];
+            for (int k = lane; k < nblk * fd * Ncp; k += WAVE) ylds[k] = yb[k];
         }
         double xr[RC][16];
 #pragma unroll
@@ -111,12 +129,12 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
             // carries the values, so nothing that uses them can move above it -- the build's hazard lint holds this unit to that)
             double yv[16];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) yv[k] = ylds[k * Ncp + jc];
+            for (int k = 0; k < 8; ++k) yv[k] = yl[k * Ncp + jc];
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
             if (wide) {
 #pragma unroll
-                for (int k = 8; k < 16; ++k) yv[k] = ylds[k * Ncp + jc];
+                for (int k = 8; k < 16; ++k) yv[k] = yl[k * Ncp + jc];
                 asm volatile("s_waitcnt lgkmcnt(0)"
                              : "+v"(yv[8]), "+v"(yv[9]), "+v"(yv[10]), "+v"(yv[11]), "+v"(yv[12]), "+v"(yv[13]), "+v"(yv[14]), "+v"(yv[15]));
             } else {
@@ -202,8 +220,9 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
         for (int off = 1; off < W; off <<= 1) acc += __shfl_xor(acc, off, WAVE);
         if (lam == 0 && live) {
             const double v = prm.sigma[0] + acc;
-            if (prm.out_f32) reinterpret_cast<float *>(prm.out)[a * prm.B + b] = (float)v;
-            else reinterpret_cast<double *>(prm.out)[a * prm.B + b] = v;
+            const int64_t o = paired ? a : a * prm.B + b;
+            if (prm.out_f32) reinterpret_cast<float *>(prm.out)[o] = (float)v;
+            else reinterpret_cast<double *>(prm.out)[o] = v;
         }
     }
 }
@@ -224,36 +243,40 @@ bool truncated_in_scope(int D, int M, int N, int L, int order) {
     return (int64_t)trunc_fd(D) * ((N + 15) / 16 * 16) <= TR_LDS_DOUBLES;
 }
 
+// paired != 0: the A = B pairs (x_p, y_p), out [A]
 template <typename TO>
 int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
-                     int order, const double *sigma, TO *out, hipStream_t s) {
+                     int order, const double *sigma, TO *out, hipStream_t s, int paired) {
     if (!truncated_in_scope(D, M, N, L, order)) return SK_ERR_UNSUPPORTED;
-    if (fd != trunc_fd(D) || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M) return SK_ERR_BAD_ARG;
+    if (fd != trunc_fd(D) || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
     TruncParams prm;
     prm.Xr = Xr; prm.Yt = Yt; prm.out = out;
     prm.A = A; prm.B = B;
     prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
     prm.order = trunc_order(L, order);
     prm.out_f32 = sizeof(TO) == 4;
+    prm.paired = paired != 0;
     for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = m <= L ? sigma[m] : 0.0;
     const int RC = prm.order == 1 ? 2 : 1;
     const int lanes = (M + RC - 1) / RC;
     int logW = 0;
     while ((1 << logW) < lanes) ++logW;
+    // paired: every lane group of a wave keeps a y block of its own -- fewer, wider groups until they fit (one group always does)
+    while (paired && (int64_t)(WAVE >> logW) * fd * Ncp > TR_LDS_DOUBLES) ++logW;
     prm.logW = logW;
     const int G = WAVE >> logW;
-    prm.n_pos = (A + G - 1) / G * B;
+    prm.n_pos = paired ? (A + G - 1) / G : (A + G - 1) / G * B;
     int64_t blocks = (int64_t)device_cu_count() * 8;
     if (blocks > prm.n_pos) blocks = prm.n_pos;
-    const size_t lds = sizeof(double) * (size_t)fd * Ncp;
+    const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
     if (RC == 2) SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     else SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     return check_launch();
 }
 
 template int launch_truncated<double>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
-                                      double *, hipStream_t);
+                                      double *, hipStream_t, int);
 template int launch_truncated<float>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
-                                     float *, hipStream_t);
+                                     float *, hipStream_t, int);
 
 }  // namespace sk

@@ -9,7 +9,7 @@ array) and, additionally, a (batch, length, dim) tensor, which stays a tensor on
 import numpy as np
 import torch
 
-__all__ = ["add_time", "lead_lag", "transform", "AddTime", "LeadLag", "truncated_sig_kernel"]
+__all__ = ["add_time", "lead_lag", "transform", "AddTime", "LeadLag", "truncated_sig_kernel", "truncated_sig_kernel_paired"]
 
 try:    # the reference's classes are sklearn estimators (pipelines, get_params); without sklearn they are plain objects
     from sklearn.base import BaseEstimator, TransformerMixin
@@ -96,4 +96,10 @@ class LeadLag(_PathTransformer):
 def truncated_sig_kernel(X, Y, num_levels, sigma=1., order=-1, **kwargs):
     """The reference keeps ``truncated_sig_kernel`` with its transformers (transformers.py:201-236); here it lives in truncated.py."""
     from .truncated import truncated_sig_kernel as impl
+    return impl(X, Y, num_levels, sigma, order, **kwargs)
+
+
+def truncated_sig_kernel_paired(X, Y, num_levels, sigma=1., order=-1, **kwargs):
+    """``truncated_sig_kernel`` on the pairs (X[p], Y[p]); it lives in truncated.py too."""
+    from .truncated import truncated_sig_kernel_paired as impl
     return impl(X, Y, num_levels, sigma, order, **kwargs)

@@ -77,7 +77,7 @@ def inputs(spec):
         z = np.load(os.path.join(ROOT, "tests", "golden", "truncated.npz"))
         k = "c%02d_" % spec["fixture"]
         return {"X": torch.as_tensor(z[k + "X"]), "Y": torch.as_tensor(z[k + "Y"]), "sigma": torch.as_tensor(z[k + "sigma"])}
-    if op == "truncated":      # steps, not points
+    if op in ("truncated", "truncated_paired"):      # steps, not points
         return {"X": (0.3 * torch.randn(A, M, D, generator=g)).to(dt), "Y": (0.3 * torch.randn(B, N, D, generator=g)).to(dt)}
     X = (torch.cumsum(torch.randn(A, M, D, generator=g, dtype=f64), 1) / np.sqrt(M * D)).to(dt)
     Y = (torch.cumsum(torch.randn(B, N, D, generator=g, dtype=f64), 1) / np.sqrt(N * D)).to(dt)
@@ -135,6 +135,8 @@ def execute(spec, t=None):
     X, Y, A = dev["X"], dev["Y"], spec["A"]
     if op == "truncated":
         return {"value": sigkernel_amd.truncated_sig_kernel(X, Y, spec["L"], order=spec["order"])}
+    if op == "truncated_paired":      # the same instances in their paired mode: the pairs (X[p], Y[p])
+        return {"value": sigkernel_amd.truncated_sig_kernel_paired(X, Y[:A], spec["L"], order=spec["order"])}
     if op == "truncated_golden":
         sg = dev["sigma"]
         return {"value": sigkernel_amd.truncated_sig_kernel(X, Y, spec["L"], sigma=float(sg) if sg.dim() == 0 else sg.cpu(), order=spec["order"])}
@@ -290,6 +292,8 @@ def gated_items(combo, it):
         yield it("truncated", "none", None, dt, 0, False, 5, 7, M, N, 6, combo(), L=L, order=order)
     # an exported entry point the host layer has no call of any more (the one-launch loss route carries its weights from the forward)
     yield it("loss_weights", "none", None, f64, 0, False, 5, 7, 0, 0, 0, combo())
+    # truncated_sig_kernel_paired: the paired mode of k_trunc_sig's general instance (a launch-time mode: no instance of its own)
+    yield it("truncated_paired", "none", None, f64, 0, False, 5, 7, 40, 30, 6, combo(), L=4, order=2)
 
 
 def run(first=0, stride=1, check=0.0, verbose=True):
