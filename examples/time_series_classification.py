@@ -5,13 +5,15 @@ kernel='precomputed', hyper-parameters by cross-validated grid search), on synth
 sets the reference downloads through tslearn are not available offline.
 
     python examples/time_series_classification.py [--n-train 120] [--n-test 80] [--length 60] [--ragged]
-    python examples/time_series_classification.py --truncated [--normalize]
+    python examples/time_series_classification.py --truncated [--normalize | --robust]
 
 --ragged: the variable-length variant -- every series is cut at a random length in [length / 2, length], the batch is padded by
 pad_paths and the Gram matrices come from compute_Gram_ragged.
 
 --truncated: the truncated signature kernel of the transformed series' steps (truncated_sig_kernel, four levels) in place of the PDE
 kernel; --normalize divides it by sqrt(k(x, x) k(y, y)) (normalize=True: the A + B self-kernels come from one paired launch each).
+--robust: Chevyrev and Oberhauser's robust normalisation instead -- truncated_sig_kernel_levels (the level terms of one sweep) ->
+truncated_robust_scales (a scale per path from its paired self levels) -> truncated_from_levels (the kernel of the rescaled paths).
 
 Class 0: Brownian paths with a slow sinusoidal drift; class 1: the same noise with the drift's frequency doubled.
 Runs on an MI355X (the Gram matrices come from the HIP kernels; there is no CPU fallback).
@@ -78,15 +80,25 @@ def predict(model, sigma, xt_train, x_test, x_train_max, device, at=True, ll=Fal
     return model.predict(G_test)
 
 
-def truncated_svc(x_train, y_train, x_test, device, normalize, num_levels=4, cv=5):
+def robust_gram(X, Y, num_levels):
+    """The robustly normalised truncated kernel matrix of two step batches: levels -> scales -> truncated_from_levels, three sweeps."""
+    lam_x = sigkernel.truncated_robust_scales(sigkernel.truncated_sig_kernel_levels(X, X, num_levels, paired=True))
+    lam_y = lam_x if Y is X else sigkernel.truncated_robust_scales(sigkernel.truncated_sig_kernel_levels(Y, Y, num_levels, paired=True))
+    return sigkernel.truncated_from_levels(sigkernel.truncated_sig_kernel_levels(X, Y, num_levels), 1., lam_x, lam_y)
+
+
+def truncated_svc(x_train, y_train, x_test, device, normalize, num_levels=4, cv=5, robust=False):
     """The same pipeline with truncated_sig_kernel on the STEPS of the time-augmented series: (cv score, C, test predictions)."""
     from sklearn.model_selection import GridSearchCV
     from sklearn.svm import SVC
     top = np.abs(x_train).max()
     steps = [torch.diff(sigkernel.transform(torch.tensor(x / top, dtype=torch.float64, device=device), at=True, ll=False, scale=1.0), dim=1)
              for x in (x_train, x_test)]
-    G_train = sigkernel.truncated_sig_kernel(steps[0], steps[0], num_levels, normalize=normalize).cpu().numpy()
-    G_test = sigkernel.truncated_sig_kernel(steps[1], steps[0], num_levels, normalize=normalize).cpu().numpy()
+    if robust:
+        G_train, G_test = robust_gram(steps[0], steps[0], num_levels).cpu().numpy(), robust_gram(steps[1], steps[0], num_levels).cpu().numpy()
+    else:
+        G_train = sigkernel.truncated_sig_kernel(steps[0], steps[0], num_levels, normalize=normalize).cpu().numpy()
+        G_test = sigkernel.truncated_sig_kernel(steps[1], steps[0], num_levels, normalize=normalize).cpu().numpy()
     model = GridSearchCV(estimator=SVC(kernel="precomputed", decision_function_shape="ovo"), param_grid={"C": np.logspace(0, 4, 5)}, cv=cv, n_jobs=1)
     model.fit(G_train, y_train)
     return float(model.best_score_), model.best_params_["C"], model.predict(G_test)
@@ -114,18 +126,20 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="series of unequal length: pad_paths -> compute_Gram_ragged(sym=True) -> SVC")
     ap.add_argument("--truncated", action="store_true", help="truncated_sig_kernel of the series' steps instead of the PDE kernel")
     ap.add_argument("--normalize", action="store_true", help="with --truncated: k(x, y) / sqrt(k(x, x) k(y, y))")
+    ap.add_argument("--robust", action="store_true", help="with --truncated: the robust normalisation, from the level terms of one sweep")
     args = ap.parse_args()
-    if args.normalize and not args.truncated or args.truncated and args.ragged:
-        raise SystemExit("--normalize goes with --truncated, and --truncated takes series of one length")
+    if (args.normalize or args.robust) and not args.truncated or args.truncated and args.ragged or args.normalize and args.robust:
+        raise SystemExit("--normalize or --robust (one of them) goes with --truncated, and --truncated takes series of one length")
     if not torch.cuda.is_available():
         raise SystemExit("this example needs an MI355X (sigkernel_amd has no CPU path)")
     device = torch.device("cuda", 0)
     x_train, y_train = make_dataset(args.n_train, args.length, seed=0)
     x_test, y_test = make_dataset(args.n_test, args.length, seed=1)
     if args.truncated:
-        score, C, pred = truncated_svc(x_train, y_train, x_test, device, args.normalize)
+        score, C, pred = truncated_svc(x_train, y_train, x_test, device, args.normalize, robust=args.robust)
         acc = float(np.mean(pred == y_test))
-        print("truncated signature kernel%s + SVC: cv accuracy %.3f (C %g), test accuracy %.3f" % (" (normalised)" if args.normalize else "", score, C, acc))
+        how = " (normalised)" if args.normalize else " (robustly normalised)" if args.robust else ""
+        print("truncated signature kernel%s + SVC: cv accuracy %.3f (C %g), test accuracy %.3f" % (how, score, C, acc))
         return acc
     if args.ragged:
         # (the transform -- time as a channel -- acts point by point, so it commutes with the padding)

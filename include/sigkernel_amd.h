@@ -62,7 +62,8 @@ typedef enum sk_status {
 /* 340.  The number moves whenever an exported signature changes incompatibly: 310 -> 320 gave sk_solve_fwd_{linear,rbf}_sym_* their
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
- * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  A binding
+ * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -495,6 +496,24 @@ int sk_truncated_paired_f64(const double *Xr, const double *Yt, int64_t P, int M
                             int order, const double *sigma, double *out, void *stream);
 int sk_truncated_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
                             int order, const double *sigma, float *out, void *stream);
+/* The LEVEL TERMS of the truncated kernel, all of them from the one sweep: out[m][a][b] = k_m(x_a, y_b) = the sum of level m's planes over
+ * the step grid, m = 1 .. num_levels, and out[0] = 1, so that sk_truncated_gram_* with weights sigma is sum_m sigma[m] out[m] (replaces
+ * num_levels + 1 calls of truncated_sig_kernel, transformers.py:201-236, with unit-vector sigma: the reference has no per-level output).
+ * Every truncation 1 .. num_levels, every choice of level weights and every rescaling of the paths (k_m(c x, y) = c^m k_m(x, y)) is a
+ * weighted sum of these planes.  A launch-time mode of the Gram kernel's instances: the step loop is the plain launch's, the levels below
+ * the last are the row sums it keeps anyway, reduced per level after the loop; num_levels + 1 stores per pair.
+ *   Xr, Yt, order, the _f32 rule and the scope as sk_truncated_gram_*;  out [num_levels + 1][A][B], every plane a contiguous matrix. */
+int sk_truncated_levels_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                            int num_levels, int order, double *out, void *stream);
+int sk_truncated_levels_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                            int num_levels, int order, float *out, void *stream);
+/* ... and of the P PAIRS (x_p, y_p): out [num_levels + 1][P], the paired mode of sk_truncated_paired_* with the level output above
+ * (replaces num_levels + 1 calls of truncated_sig_kernel per pair with unit-vector sigma, transformers.py:201-236, keeping [0][0]).  With
+ * y = x these are the squared norms of the signature levels of every path: what a per-path rescaling is solved from. */
+int sk_truncated_levels_paired_f64(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                   int num_levels, int order, double *out, void *stream);
+int sk_truncated_levels_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                   int num_levels, int order, float *out, void *stream);
 /* Symmetric Gram matrix of ONE path batch with the fused kernels above: only the A (A + 1) / 2 pairs on and above the diagonal are
  * solved (what the reference's CPU solver does for sym=True, cython_backend.pyx:74-97; its GPU path ignores `sym`), in ONE launch,
  * and each value is written to out[a][b] and out[b][a]: out [A][A] is exactly symmetric.  dXr / dXt (Xr / Xt): the row-major and

@@ -91,6 +91,10 @@ SIGNATURES = {
     "sk_truncated_gram_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_truncated_paired_f64": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_truncated_paired_f32": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "sk_truncated_levels_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
+    "sk_truncated_levels_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
+    "sk_truncated_levels_paired_f64": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
+    "sk_truncated_levels_paired_f32": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
     "sk_prep_pair_f64": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_prep_pair_f32": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_solve_fwd_static_workspace_bytes": (_sz, [_int, _i64, _int, _int, _int, _int]),
@@ -668,6 +672,18 @@ class HipBackend:
         if truncated.truncated_route(X.shape[2], X.shape[1], Y.shape[1], num_levels, order, X.element_size()) != ROUTE_FUSED:
             return None
         return truncated._truncated_hip(X, Y, int(num_levels), [float(v) for v in sigma], int(order), paired=True)
+
+    def truncated_levels(self, X, Y, num_levels, order, paired=False):
+        """The level terms k_0 .. k_L of the truncated signature kernel from ONE sweep per pair (sk_truncated_levels_*, the levels mode of
+        k_trunc_sig): (num_levels + 1, A, B), or -- paired -- (num_levels + 1, P) of the pairs (X[p], Y[p]); plane 0 holds 1.  None outside
+        the kernel's scope, as truncated_gram: FUSED_SWAP is the caller's call on (Y, X), each level transposed, and STREAM its torch
+        restatement."""
+        from . import truncated
+        _dev(X, "X")
+        _dev(Y, "Y")
+        if truncated.truncated_route(X.shape[2], X.shape[1], Y.shape[1], num_levels, order, X.element_size()) != ROUTE_FUSED:
+            return None
+        return truncated._truncated_levels_hip(X, Y, int(num_levels), int(order), paired=paired)
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):
         """The loss wrappers' forward in THREE launches (csrc/sk_loss.hip): [X; Y] staged in both layouts straight from the two

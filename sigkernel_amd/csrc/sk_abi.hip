@@ -188,6 +188,17 @@ int truncated_paired(const double *Xr, const double *Yt, int64_t P, int Mrows, i
     return launch_truncated<TO>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream, 1);
 }
 
+// ... and the level terms of every pair, the same instances in their levels mode (paired != 0: P = A pairs, B ignored)
+template <typename TO>
+int truncated_levels(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
+                     int order, TO *out, void *stream, int paired) {
+    if (paired) B = A;
+    if (D < 1 || !Xr || !Yt || !out || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D)
+        return SK_ERR_BAD_ARG;
+    if (A == 0 || B == 0) return SK_OK;
+    return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, nullptr, out, (hipStream_t)stream, paired, 1);
+}
+
 }  // namespace
 
 // ---- the one place that reads the environment: SK_* tuning knobs, parsed when the library is loaded ------------------------
@@ -257,6 +268,7 @@ int device_cu_count() {
 
 extern "C" {
 
+// (340 still: sk_truncated_levels_{,paired_}{f64,f32} are additions, no exported signature changed)
 // 340: sk_static_increments_* serve any path dim (D > 32: k_static_wide_mfma); sk_static_adjoint_* kind 1 with D > 32 writes the first
 // pass H [P][M][ldh] of the rbf chain rule instead of dL/dX
 // 330 (round 6): sk_linear_adjoint_fused_f64 takes ypart / ypart_doubles / ycols_out (the second-argument sums, route FUSED_SWAP)
@@ -491,6 +503,22 @@ int sk_truncated_paired_f64(const double *Xr, const double *Yt, int64_t P, int M
 int sk_truncated_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
                             int order, const double *sigma, float *out, void *stream) {
     return truncated_paired<float>(Xr, Yt, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
+}
+int sk_truncated_levels_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                            int num_levels, int order, double *out, void *stream) {
+    return truncated_levels<double>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, out, stream, 0);
+}
+int sk_truncated_levels_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                            int num_levels, int order, float *out, void *stream) {
+    return truncated_levels<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, out, stream, 0);
+}
+int sk_truncated_levels_paired_f64(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                   int num_levels, int order, double *out, void *stream) {
+    return truncated_levels<double>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, out, stream, 1);
+}
+int sk_truncated_levels_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                   int num_levels, int order, float *out, void *stream) {
+    return truncated_levels<float>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, out, stream, 1);
 }
 int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream) {

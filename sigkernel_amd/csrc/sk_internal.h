@@ -188,11 +188,12 @@ bool prefix_in_scope(int kind, int D, int Mc, int dyadic);   // the kernel's sco
 
 // ---- sk_truncated.hip: the truncated signature kernel of Kiraly and Oberhauser, all levels in one sweep of the step grid ----
 // Xr [A][Mrows][fd] / Yt [B][fd][Ncp]: the path POINTS as sk_prep_pair_* stages them (fd = 8 up to dim 8, else 16); sigma: L + 1 host
-// values; out [A][B].  paired != 0 (a launch-time mode of the same instances): A = B pairs (x_p, y_p), out [A].  SK_ERR_UNSUPPORTED
-// outside truncated_in_scope, in either mode.
+// values; out [A][B].  paired != 0 (a launch-time mode of the same instances): A = B pairs (x_p, y_p), out [A].  levels != 0 (another):
+// the level terms k_0 .. k_L of every pair instead of their weighted sum, out [L + 1][A][B] / [L + 1][A]; sigma is not read.
+// SK_ERR_UNSUPPORTED outside truncated_in_scope, in every mode.
 template <typename TO>
 int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
-                     int order, const double *sigma, TO *out, hipStream_t s, int paired = 0);
+                     int order, const double *sigma, TO *out, hipStream_t s, int paired = 0, int levels = 0);
 bool truncated_in_scope(int D, int M, int N, int L, int order);   // the kernel's scope = the SK_OP_TRUNCATED rule of sk_route_query
 
 // ---- sk_loss.hip: the glue of the loss wrappers (compute_mmd / scoring rules) as single launches ----

@@ -26,6 +26,10 @@
 // wave stages those of its live groups as one run.  A lane's block never changes during a position, so the lane reads through a pointer
 // to it that is formed before the step loop: the loop issues the instructions it issues in Gram mode, where the pointer is ylds itself.
 // The launch widens the groups until G fd Ncp doubles fit the wave's 16 KB; lanes beyond the rows of x hold zero rows.
+// LEVELS mode (TruncParams::levels, launch-time and wave-uniform, in Gram and paired mode): the pair's level terms k_0 = 1, k_1, .., k_L
+// instead of their weighted sum, out[m][pair].  The step loop is the plain launch's, run with the weights (0, .., 0, 1): acc is then
+// level L, and the totals of the levels below are the running row sums rowS the loop keeps anyway.  The mode is an epilogue: a sum over
+// the lane's rows and the group's butterfly per level, and L + 1 stores per pair where the plain launch has one.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
 // order (1: one plane per level, or TR_OMAX) and the rows per lane.
 #include "sk_wave_common.h"
@@ -40,10 +44,11 @@ constexpr int TR_LDS_DOUBLES = 2048;  // y block of a wave: fd x Ncp doubles, 16
 struct TruncParams {
     const double *Xr;   // [A][Mrows][fd]
     const double *Yt;   // [B][fd][Ncp]
-    void *out;          // [A][B], double or float; paired: [A]
+    void *out;          // [A][B], double or float; paired: [A]; levels: [L + 1][A][B], paired [L + 1][A]
     int64_t A, B, n_pos;
     int Mrows, Ncp, fd, M, N, L, order, logW, out_f32;
     int paired;         // 0: the Gram matrix of A x B pairs; 1: the A = B pairs (x_p, y_p), one per lane group
+    int levels;         // 0: one weighted value per pair; 1: the pair's L + 1 level terms, one plane of `out` per level
     double sigma[TR_LMAX + 1];
 };
 
@@ -218,7 +223,34 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
         }
         // the pair's total: a butterfly over the lanes of the group, the same order on every call
         for (int off = 1; off < W; off <<= 1) acc += __shfl_xor(acc, off, WAVE);
-        if (lam == 0 && live) {
+        if (prm.levels) {
+            // LEVELS mode: the weights are (0, .., 0, 1), so acc is level L; the total of level s + 1 < L is what the rows' running
+            // sums rowS[.][s] hold after the last step.  The same butterfly per level, then plane m of the output takes level m.
+            const int64_t plane = paired ? prm.A : prm.A * prm.B;
+            const int64_t o = paired ? a : a * prm.B + b;
+            const bool st = lam == 0 && live;
+            if (st) {
+                if (prm.out_f32) {
+                    reinterpret_cast<float *>(prm.out)[o] = 1.0f;
+                    reinterpret_cast<float *>(prm.out)[L * plane + o] = (float)acc;
+                } else {
+                    reinterpret_cast<double *>(prm.out)[o] = 1.0;
+                    reinterpret_cast<double *>(prm.out)[L * plane + o] = acc;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (s < L - 1) {
+                    double v = rowS[0][s];
+#pragma unroll
+                    for (int r = 1; r < RC; ++r) v += rowS[r][s];
+                    for (int off = 1; off < W; off <<= 1) v += __shfl_xor(v, off, WAVE);
+                    if (st) {
+                        if (prm.out_f32) reinterpret_cast<float *>(prm.out)[(s + 1) * plane + o] = (float)v;
+                        else reinterpret_cast<double *>(prm.out)[(s + 1) * plane + o] = v;
+                    }
+                }
+        } else if (lam == 0 && live) {
             const double v = prm.sigma[0] + acc;
             const int64_t o = paired ? a : a * prm.B + b;
             if (prm.out_f32) reinterpret_cast<float *>(prm.out)[o] = (float)v;
@@ -243,10 +275,10 @@ bool truncated_in_scope(int D, int M, int N, int L, int order) {
     return (int64_t)trunc_fd(D) * ((N + 15) / 16 * 16) <= TR_LDS_DOUBLES;
 }
 
-// paired != 0: the A = B pairs (x_p, y_p), out [A]
+// paired != 0: the A = B pairs (x_p, y_p), out [A].  levels != 0: sigma is not read, out [L + 1][A][B] (paired: [L + 1][A])
 template <typename TO>
 int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
-                     int order, const double *sigma, TO *out, hipStream_t s, int paired) {
+                     int order, const double *sigma, TO *out, hipStream_t s, int paired, int levels) {
     if (!truncated_in_scope(D, M, N, L, order)) return SK_ERR_UNSUPPORTED;
     if (fd != trunc_fd(D) || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
     TruncParams prm;
@@ -256,7 +288,8 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
     prm.order = trunc_order(L, order);
     prm.out_f32 = sizeof(TO) == 4;
     prm.paired = paired != 0;
-    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = m <= L ? sigma[m] : 0.0;
+    prm.levels = levels != 0;
+    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = levels ? (m == L ? 1.0 : 0.0) : (m <= L ? sigma[m] : 0.0);
     const int RC = prm.order == 1 ? 2 : 1;
     const int lanes = (M + RC - 1) / RC;
     int logW = 0;
@@ -275,8 +308,8 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
 }
 
 template int launch_truncated<double>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
-                                      double *, hipStream_t, int);
+                                      double *, hipStream_t, int, int);
 template int launch_truncated<float>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
-                                     float *, hipStream_t, int);
+                                     float *, hipStream_t, int, int);
 
 }  // namespace sk

@@ -9,7 +9,8 @@ array) and, additionally, a (batch, length, dim) tensor, which stays a tensor on
 import numpy as np
 import torch
 
-__all__ = ["add_time", "lead_lag", "transform", "AddTime", "LeadLag", "truncated_sig_kernel", "truncated_sig_kernel_paired"]
+__all__ = ["add_time", "lead_lag", "transform", "AddTime", "LeadLag", "truncated_sig_kernel", "truncated_sig_kernel_paired",
+           "truncated_sig_kernel_levels", "truncated_from_levels", "truncated_robust_scales"]
 
 try:    # the reference's classes are sklearn estimators (pipelines, get_params); without sklearn they are plain objects
     from sklearn.base import BaseEstimator, TransformerMixin
@@ -103,3 +104,21 @@ def truncated_sig_kernel_paired(X, Y, num_levels, sigma=1., order=-1, **kwargs):
     """``truncated_sig_kernel`` on the pairs (X[p], Y[p]); it lives in truncated.py too."""
     from .truncated import truncated_sig_kernel_paired as impl
     return impl(X, Y, num_levels, sigma, order, **kwargs)
+
+
+def truncated_sig_kernel_levels(X, Y, num_levels, order=-1, **kwargs):
+    """The level terms of ``truncated_sig_kernel``, (num_levels + 1, A, B); it lives in truncated.py too."""
+    from .truncated import truncated_sig_kernel_levels as impl
+    return impl(X, Y, num_levels, order, **kwargs)
+
+
+def truncated_from_levels(levels, sigma=1., scale_x=None, scale_y=None):
+    """``sum_m sigma[m] (scale_x scale_y)^m levels[m]``: the truncated kernel from its level terms (truncated.py)."""
+    from .truncated import truncated_from_levels as impl
+    return impl(levels, sigma, scale_x, scale_y)
+
+
+def truncated_robust_scales(self_levels, C=4.0, a=1.0):
+    """The per-path scales of the robust normalisation from the paired self levels (truncated.py)."""
+    from .truncated import truncated_robust_scales as impl
+    return impl(self_levels, C, a)

@@ -22,6 +22,13 @@ Two routes, chosen by ``sk_route_query(SK_OP_TRUNCATED, ...)``:
 ``truncated_sig_kernel_paired`` is the same kernel on P pairs ``(X[p], Y[p])``: the same two routes (the HIP kernel in its paired mode, one
 pair per lane group; the torch restatement tiled over pairs), the same scope, and nothing of size P x P on either.  It is what
 ``truncated_sig_kernel(..., normalize=True)`` -- ``K[a, b] / sqrt(k(x_a, x_a) k(y_b, y_b))`` -- takes its two diagonals from.
+
+``truncated_sig_kernel_levels`` returns the level terms ``k_m = sum_{nodes, planes} R^m`` themselves, ``(L + 1, A, B)`` with ``k_0 = 1``: the
+sweep holds them all when it ends (the levels mode of ``k_trunc_sig``: an epilogue, no second sweep), and ``_truncated_levels_torch`` is the
+restatement that keeps each level's sum.  ``K`` is linear in them -- ``truncated_from_levels`` forms ``sum_m sigma[m] k_m`` for any weights,
+differentiably, and with per-path scales ``(lx[a] ly[b])^m`` in front, because ``k_m(c x, y) = c^m k_m(x, y)`` at every order: every
+truncation below L, every choice of weights and every rescaling of the paths is a re-weighting of ONE sweep's output.
+``truncated_robust_scales`` solves the scales of Chevyrev and Oberhauser's robust normalisation from the paired self levels.
 """
 import ctypes
 
@@ -30,7 +37,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["truncated_sig_kernel", "truncated_sig_kernel_paired"]
+__all__ = ["truncated_sig_kernel", "truncated_sig_kernel_paired", "truncated_sig_kernel_levels", "truncated_from_levels",
+           "truncated_robust_scales"]
 
 _DEFAULT_WORKSPACE = 1 << 30
 
@@ -91,6 +99,50 @@ def _truncated_block(X, Y, L, sig, order, paired=False):
     return K
 
 
+def _levels_block(X, Y, L, order, paired=False):
+    """_truncated_block keeping each level's sum: (L + 1, A, B) of all pairs, or -- paired -- (L + 1, P); plane 0 is the ones of level 0"""
+    G = torch.einsum("pid,pjd->pij", X, Y) if paired else torch.einsum("aid,bjd->abij", X, Y)
+    first = G.sum((-2, -1))
+    out = [torch.ones_like(first), first]
+    R = [[G]]
+    for m in range(1, L):
+        d = min(m + 1, order)
+        total = sum(sum(row) for row in R)
+        nxt = [[None] * d for _ in range(d)]
+        nxt[0][0] = G * _excl(_excl(total, -2), -1)
+        for q in range(1, d):
+            nxt[0][q] = G * _excl(sum(R[p][q - 1] for p in range(len(R))), -2) / (q + 1)
+            nxt[q][0] = G * _excl(sum(R[q - 1]), -1) / (q + 1)
+        for p in range(1, d):
+            for q in range(1, d):
+                nxt[p][q] = G * R[p - 1][q - 1] / ((p + 1) * (q + 1))
+        R = nxt
+        out.append(sum(sum(row) for row in R).sum((-2, -1)))
+    return torch.stack(out, 0)
+
+
+def _truncated_levels_torch(X, Y, num_levels, order=-1, paired=False, workspace_bytes=None):
+    """The level terms k_0 .. k_L in torch ops on the tensors' own device, differentiable: (L + 1, A, B), paired (L + 1, P).  The recursion
+    of _truncated_torch with each level's sum kept, tiled over rows of X (over pairs) by `workspace_bytes` exactly as it is."""
+    num_levels, order = _check_args(X, Y, num_levels, order)
+    if paired and X.shape[0] != Y.shape[0]:
+        raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
+    A, M = X.shape[0], X.shape[1]
+    B, N = Y.shape[0], Y.shape[1]
+    shape = (A,) if paired else (A, B)
+    if A == 0 or B == 0 or M == 0 or N == 0:
+        out = torch.zeros((num_levels + 1,) + shape, dtype=X.dtype, device=X.device)
+        out[0] = 1
+        return out
+    d = min(num_levels, order)
+    budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
+    per_row = (1 if paired else B) * M * N * X.element_size() * (2 * d * d + 6) * (num_levels if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad) else 1)
+    rows = int(max(1, min(A, budget // max(1, per_row))))
+    if paired:
+        return torch.cat([_levels_block(X[a:a + rows], Y[a:a + rows], num_levels, order, True) for a in range(0, A, rows)], 1)
+    return torch.cat([_levels_block(X[a:a + rows], Y, num_levels, order) for a in range(0, A, rows)], 1)
+
+
 def _truncated_torch(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=None):
     """The recursion in torch ops on the tensors' own device (any device: the tests drive it on the CPU), differentiable; (A, B)."""
     num_levels, order = _check_args(X, Y, num_levels, order)
@@ -146,6 +198,29 @@ def _truncated_hip(X, Y, num_levels, sig, order, paired=False):
     return out
 
 
+def _truncated_levels_hip(X, Y, num_levels, order, paired=False):
+    """(L + 1, A, B) -- paired: (L + 1, P) -- through k_trunc_sig in its levels mode (the body of HipBackend.truncated_levels, which has asked
+    sk_route_query).  X, Y contiguous on a HIP device."""
+    A, M, D = X.shape
+    B, N = Y.shape[0], Y.shape[1]
+    out = torch.empty((num_levels + 1,) + ((A,) if paired else (A, B)), dtype=X.dtype, device=X.device)
+    if A == 0 or B == 0:
+        return out
+    fd = 8 if D <= 8 else 16
+    Ncp = (N + 15) // 16 * 16
+    lib = _lib.load()
+    with _lib._device(X.device):
+        Xr, Yt = _lib._prep_pair(X, Y, False, 1.0, M, Ncp, fd)
+        if paired:
+            fn = getattr(lib, "sk_truncated_levels_paired_" + _lib._suffix(X))
+            rc = fn(_lib._ptr(Xr), _lib._ptr(Yt), A, M, M, N, Ncp, D, fd, num_levels, order, _lib._ptr(out), _lib._stream(X))
+        else:
+            fn = getattr(lib, "sk_truncated_levels_" + _lib._suffix(X))
+            rc = fn(_lib._ptr(Xr), _lib._ptr(Yt), A, B, M, M, N, Ncp, D, fd, num_levels, order, _lib._ptr(out), _lib._stream(X))
+    _lib._check(rc, "sk_truncated_levels_paired" if paired else "sk_truncated_levels")
+    return out
+
+
 def truncated_route(D, M, N, num_levels, order, elem_size):
     """ROUTE_FUSED / ROUTE_FUSED_SWAP / ROUTE_STREAM (= the torch restatement) for step counts M, N (sk_route_query, csrc/sk_route.hip)."""
     return int(_lib.load().sk_route_query(_lib.OP_TRUNCATED, int(order), int(D), int(M), int(N), int(num_levels), 0, int(elem_size), 0))
@@ -164,6 +239,21 @@ def _paired_hip(be, X, Y, num_levels, weights, order, budget):
             return None
         parts.append(k)
     return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+
+def _levels_paired_hip(be, X, Y, num_levels, order, budget):
+    """be.truncated_levels(paired=True) on as many pairs at a time as `budget` bytes of staging hold, as _paired_hip; None where it says None"""
+    P, M, D = X.shape
+    fd = 8 if D <= 8 else 16
+    per_pair = 8 * fd * (M + (Y.shape[1] + 15) // 16 * 16)
+    pairs = int(max(1, min(P, budget // per_pair)))
+    parts = []
+    for p in range(0, P, pairs):
+        k = be.truncated_levels(X[p:p + pairs], Y[p:p + pairs], num_levels, order, paired=True)
+        if k is None:
+            return None
+        parts.append(k)
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
 
 
 def _stage(X, Y):
@@ -254,3 +344,117 @@ def truncated_sig_kernel(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=N
         ky = kx if same else _normalizer(truncated_sig_kernel_paired(Y, Y, num_levels, sig, order, workspace_bytes), "Y")
         K = K / torch.sqrt(kx[:, None] * ky[None, :])
     return K.cpu().numpy() if as_numpy else K
+
+
+def truncated_sig_kernel_levels(X, Y, num_levels, order=-1, paired=False, workspace_bytes=None):
+    """The level terms of the truncated signature kernel: ``(num_levels + 1, A, B)`` with ``out[m, a, b] = k_m(X[a], Y[b])``, the sum of
+    level m's planes over the step grid, and ``out[0] = 1`` -- so ``truncated_sig_kernel(X, Y, L, sigma, order)`` is
+    ``sum_m sigma[m] * out[m]`` (truncated_from_levels).  ``paired=True``: ``(num_levels + 1, P)`` of the pairs ``(X[p], Y[p])``.  Every
+    level is a contiguous matrix.  X, Y, ``num_levels``, ``order``, the dtypes and numpy in / numpy out are those of truncated_sig_kernel.
+
+    Inside the HIP kernel's scope this is ONE launch of k_trunc_sig in its levels mode -- the sweep of the plain call plus an epilogue --
+    on (Y, X) with every level transposed when only the second batch fits the lanes.  Inputs that require grad and shapes outside the
+    scope take the differentiable torch restatement, tiled by ``workspace_bytes`` (default 1 GiB) as truncated_sig_kernel's; the paired HIP
+    route's staging is bounded by it as truncated_sig_kernel_paired's."""
+    X, Y, as_numpy = _stage(X, Y)
+    num_levels, order = _check_args(X, Y, num_levels, order)
+    if paired and X.shape[0] != Y.shape[0]:
+        raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
+    X, Y = X.contiguous(), Y.contiguous()
+    _lib._dev(X, "X")
+    _lib._dev(Y, "Y")
+    be = _lib.get_backend()
+    K = None
+    if not _needs_grad(X, Y, None) and min(X.shape[0], X.shape[1], Y.shape[0], Y.shape[1]) > 0 and hasattr(be, "truncated_levels"):
+        Xd, Yd = X.detach(), Y.detach()
+        if paired:
+            budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
+            K = _levels_paired_hip(be, Xd, Yd, num_levels, order, budget)
+            if K is None:       # SK_ROUTE_FUSED_SWAP: k_m(x, y) = k_m(y, x) at every order, nothing to transpose
+                K = _levels_paired_hip(be, Yd, Xd, num_levels, order, budget)
+        else:
+            K = be.truncated_levels(Xd, Yd, num_levels, order)
+            if K is None:       # SK_ROUTE_FUSED_SWAP: every level of (y, x) is the transpose of that level of (x, y)
+                Kt = be.truncated_levels(Yd, Xd, num_levels, order)
+                K = None if Kt is None else Kt.transpose(1, 2).contiguous()
+    if K is None:
+        K = _truncated_levels_torch(X, Y, num_levels, order, paired, workspace_bytes)
+    return K.cpu().numpy() if as_numpy else K
+
+
+def _scale_vector(scale, n, like, name):
+    s = scale if isinstance(scale, torch.Tensor) else torch.as_tensor(np.asarray(scale, dtype=np.float64))
+    s = s.to(dtype=like.dtype, device=like.device)
+    if s.dim() > 1 or (s.dim() == 1 and s.numel() not in (1, n)):
+        raise ValueError("%s must be a scalar or hold one value per path (%d), got shape %s" % (name, n, tuple(s.shape)))
+    return s.reshape(-1).expand(n) if s.numel() == 1 else s
+
+
+def truncated_from_levels(levels, sigma=1., scale_x=None, scale_y=None):
+    """``sum_m sigma[m] * (scale_x[:, None] * scale_y[None, :])**m * levels[m]`` for ``levels (L + 1, A, B)`` of
+    truncated_sig_kernel_levels -- the truncated kernel of the paths ``scale_x[a] X[a]`` and ``scale_y[b] Y[b]`` with weights ``sigma``
+    (a scalar or L + 1 values), without another sweep: level m is homogeneous of degree m in either path.  ``levels (L + 1, P)``: the
+    elementwise analogue, ``(scale_x * scale_y)**m``.  No scales: ``sum_m sigma[m] levels[m]``, which is truncated_sig_kernel.  Plain torch
+    ops on the tensors' device: differentiable in ``sigma``, the scales and ``levels``.  numpy levels give a numpy result."""
+    as_numpy = isinstance(levels, np.ndarray)
+    if as_numpy:
+        levels = torch.as_tensor(levels)
+    if not isinstance(levels, torch.Tensor) or levels.dim() not in (2, 3) or levels.shape[0] < 2:
+        raise ValueError("levels must have shape (num_levels + 1, A, B) or (num_levels + 1, P)")
+    L = levels.shape[0] - 1
+    sig = _sigma_vector(sigma, L, levels.dtype, levels.device)
+    w = sig.reshape((L + 1,) + (1,) * (levels.dim() - 1))
+    if scale_x is not None or scale_y is not None:
+        one = torch.ones((), dtype=levels.dtype, device=levels.device)
+        sx = _scale_vector(one if scale_x is None else scale_x, levels.shape[1], levels, "scale_x")
+        sy = _scale_vector(one if scale_y is None else scale_y, levels.shape[-1], levels, "scale_y")
+        lam = sx[:, None] * sy[None, :] if levels.dim() == 3 else sx * sy
+        w = w * torch.stack([lam ** m for m in range(L + 1)], 0)
+    K = (w * levels).sum(0)
+    return K.detach().cpu().numpy() if as_numpy else K
+
+
+def _psi(s, C, a):
+    """Chevyrev and Oberhauser's psi: s up to C, then C + C^(1+a) (C^-a - s^-a) / a -- increasing, bounded by C (1 + 1/a)"""
+    big = s.clamp_min(C)
+    return torch.where(s <= C, s, C + C ** (1 + a) * (C ** -a - big ** -a) / a)
+
+
+def truncated_robust_scales(self_levels, C=4.0, a=1.0):
+    """The per-path scales of the robust signature normalisation (Chevyrev and Oberhauser, "Signature moments to characterize laws of
+    stochastic processes", section 5) at truncation L.  ``self_levels = truncated_sig_kernel_levels(X, X, L, order, paired=True)``,
+    ``(L + 1, P)``: ``n_m = k_m(x, x)``, the squared norm of level m of the path's signature.  Returns ``lam (P,)`` in [0, 1] with
+
+        sum_m lam^(2m) n_m = psi(sum_m n_m),    psi(s) = s for s <= C,  C + C^(1+a) (C^-a - s^-a) / a beyond,
+
+    so that the rescaled path ``lam x`` has a self-kernel of at most ``C (1 + 1/a)``; ``truncated_from_levels(levels, sigma, lam_x, lam_y)``
+    is then the robustly normalised kernel.  Paths with ``s <= C`` get exactly 1.  The left side increases in lam from n_0 = 1 <= psi(s) to
+    s >= psi(s): 64 bisection steps on [0, 1] for all paths at once on the levels' device, no host read inside the loop.  A negative
+    ``n_m`` (orders below num_levels are not inner products of signature levels: nothing keeps k_m(x, x) from it) raises ValueError after
+    ONE flag read.  Not differentiated:
+    the scales are returned detached."""
+    as_numpy = isinstance(self_levels, np.ndarray)
+    n = torch.as_tensor(self_levels) if as_numpy else self_levels
+    if not isinstance(n, torch.Tensor) or n.dim() != 2 or n.shape[0] < 2:
+        raise ValueError("self_levels must have shape (num_levels + 1, P): truncated_sig_kernel_levels(X, X, L, order, paired=True)")
+    if not (C > 0 and a > 0):
+        raise ValueError("C and a must be positive, got C = %r, a = %r" % (C, a))
+    n, dtype = n.detach(), n.dtype
+    if bool((n < 0).any()):
+        raise ValueError("truncated_robust_scales needs k_m(x, x) >= 0 at every level, but a path's self level is negative (orders below "
+                         "num_levels can do that: use order = num_levels)")
+    n = n.double()
+    L = n.shape[0] - 1
+    s = n.sum(0)
+    target = _psi(s, float(C), float(a))
+    lo, hi = torch.zeros_like(s), torch.ones_like(s)
+    for _ in range(64):
+        mid = 0.5 * (lo + hi)
+        m2 = mid * mid
+        f = n[L]
+        for m in range(L - 1, -1, -1):      # Horner in lam^2
+            f = f * m2 + n[m]
+        below = f < target
+        lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
+    lam = torch.where(s <= C, torch.ones_like(s), 0.5 * (lo + hi)).to(dtype)
+    return lam.cpu().numpy() if as_numpy else lam
