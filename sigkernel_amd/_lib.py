@@ -377,6 +377,11 @@ def _prep_pair(X, Y, diff, scale_x, rows_x, rows_y, fd=8):
     return out_x, out_y
 
 
+def _truncated_staging(D, N):
+    """(fd, Ncp) of k_trunc_sig's staged paths: 8 or 16 doubles per step, the second batch's steps padded to a multiple of 16"""
+    return (8 if D <= 8 else 16), (N + 15) // 16 * 16
+
+
 class _WorstResidual:
     """The worst self-check residual of a fused-adjoint launch (NaN-propagating, as torch.max is), reduced only when somebody asks
     for it -- `float(r)` or `r.tensor()`: it is a diagnostic, and a backward pass should not pay a reduction kernel for it.  The
@@ -651,39 +656,41 @@ class HipBackend:
         _check(rc, "sk_solve_prefix_at")
         return out
 
-    def truncated_gram(self, X, Y, num_levels, sigma, order):
-        """The truncated signature kernel's (A, B) matrix in one sweep per pair (sk_truncated_gram_*, csrc/sk_truncated.hip): X (A, M, D) /
-        Y (B, N, D) hold steps, sigma num_levels + 1 host values.  None outside the kernel's scope (sk_route_query(SK_OP_TRUNCATED) !=
-        FUSED) -- the caller takes the torch restatement (truncated.py)."""
-        from . import truncated
+    def _truncated(self, X, Y, num_levels, order, paired, sigma):
+        """The one call of k_trunc_sig (sk_truncated_{gram,paired,levels,levels_paired}_*, csrc/sk_truncated.hip): X (A, M, D) / Y (B, N, D) hold
+        steps; sigma: num_levels + 1 host weights -> (A, B), paired (P,); None -> the level terms under a leading axis of num_levels + 1, plane 0
+        ones.  None outside the kernel's scope (sk_route_query(SK_OP_TRUNCATED) != FUSED): FUSED_SWAP is the caller's call on (Y, X) -- a Gram
+        result transposed, a paired one as it is -- and STREAM its torch restatement (truncated.py)."""
         _dev(X, "X")
         _dev(Y, "Y")
-        if truncated.truncated_route(X.shape[2], X.shape[1], Y.shape[1], num_levels, order, X.element_size()) != ROUTE_FUSED:
+        (A, M, D), (B, N), L = X.shape, Y.shape[:2], int(num_levels)
+        if self.route(OP_TRUNCATED, order, D, M, N, L, False, X.element_size()) != ROUTE_FUSED:
             return None
-        return truncated._truncated_hip(X, Y, int(num_levels), [float(v) for v in sigma], int(order))
+        batches = (A,) if paired else (A, B)
+        out = torch.empty(batches if sigma is not None else (L + 1,) + batches, dtype=X.dtype, device=X.device)
+        if A == 0 or B == 0:
+            return out
+        fd, Ncp = _truncated_staging(D, N)
+        name = "sk_truncated_" + (("paired" if paired else "gram") if sigma is not None else ("levels_paired" if paired else "levels"))
+        weights = () if sigma is None else ((ctypes.c_double * (L + 1))(*[float(v) for v in sigma]),)
+        with _device(X.device):
+            Xr, Yt = _prep_pair(X, Y, False, 1.0, M, Ncp, fd)
+            rc = getattr(load(), name + "_" + _suffix(X))(_ptr(Xr), _ptr(Yt), *batches, M, M, N, Ncp, D, fd, L, int(order), *weights,
+                                                          _ptr(out), _stream(X))
+        _check(rc, name)
+        return out
+
+    def truncated_gram(self, X, Y, num_levels, sigma, order):
+        """The truncated signature kernel's (A, B) matrix in one sweep per pair, or None: _truncated with sigma's num_levels + 1 host values."""
+        return self._truncated(X, Y, num_levels, order, False, sigma)
 
     def truncated_paired(self, X, Y, num_levels, sigma, order):
-        """The truncated signature kernel of the P pairs (X[p], Y[p]), (P,), by the same kernel in its paired mode (sk_truncated_paired_*): one
-        pair per lane group, nothing of size P x P.  None outside the kernel's scope, as truncated_gram: FUSED_SWAP is the caller's call on
-        (Y, X) -- the values need no transposing -- and STREAM its torch restatement."""
-        from . import truncated
-        _dev(X, "X")
-        _dev(Y, "Y")
-        if truncated.truncated_route(X.shape[2], X.shape[1], Y.shape[1], num_levels, order, X.element_size()) != ROUTE_FUSED:
-            return None
-        return truncated._truncated_hip(X, Y, int(num_levels), [float(v) for v in sigma], int(order), paired=True)
+        """... of the P pairs (X[p], Y[p]), (P,), by the same kernel in its paired mode: one pair per lane group, nothing of size P x P."""
+        return self._truncated(X, Y, num_levels, order, True, sigma)
 
     def truncated_levels(self, X, Y, num_levels, order, paired=False):
-        """The level terms k_0 .. k_L of the truncated signature kernel from ONE sweep per pair (sk_truncated_levels_*, the levels mode of
-        k_trunc_sig): (num_levels + 1, A, B), or -- paired -- (num_levels + 1, P) of the pairs (X[p], Y[p]); plane 0 holds 1.  None outside
-        the kernel's scope, as truncated_gram: FUSED_SWAP is the caller's call on (Y, X), each level transposed, and STREAM its torch
-        restatement."""
-        from . import truncated
-        _dev(X, "X")
-        _dev(Y, "Y")
-        if truncated.truncated_route(X.shape[2], X.shape[1], Y.shape[1], num_levels, order, X.element_size()) != ROUTE_FUSED:
-            return None
-        return truncated._truncated_levels_hip(X, Y, int(num_levels), int(order), paired=paired)
+        """The level terms k_0 .. k_L from ONE sweep per pair (the kernel's levels mode): (num_levels + 1, A, B), paired (num_levels + 1, P)."""
+        return self._truncated(X, Y, num_levels, order, bool(paired), None)
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):
         """The loss wrappers' forward in THREE launches (csrc/sk_loss.hip): [X; Y] staged in both layouts straight from the two

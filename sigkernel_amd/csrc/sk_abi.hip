@@ -168,35 +168,17 @@ int solve_prefix_at(int kind, const double *Xr, const double *Yt, int64_t A, int
     return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, 1, queue, (hipStream_t)stream, SK_NODES_AT, len_x, len_y);
 }
 
-// the truncated signature kernel's Gram matrix (sk_truncated.hip); argument checks before any HIP call
+// the truncated signature kernel (sk_truncated.hip), every mode of its one launch; argument checks before any HIP call.  paired != 0: the
+// A pairs (x_p, y_p), B ignored; levels != 0: the level terms of every pair, sigma not read -- and only then may it be null
 template <typename TO>
-int truncated_gram(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
-                   int order, const double *sigma, TO *out, void *stream) {
-    if (D < 1 || !Xr || !Yt || !out || !sigma || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D)
-        return SK_ERR_BAD_ARG;
-    if (A == 0 || B == 0) return SK_OK;
-    return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream);
-}
-
-// ... and its paired values, the same kernel instances in their paired mode
-template <typename TO>
-int truncated_paired(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels, int order,
-                     const double *sigma, TO *out, void *stream) {
-    if (D < 1 || !Xr || !Yt || !out || !sigma || P < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D)
-        return SK_ERR_BAD_ARG;
-    if (P == 0) return SK_OK;
-    return launch_truncated<TO>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream, 1);
-}
-
-// ... and the level terms of every pair, the same instances in their levels mode (paired != 0: P = A pairs, B ignored)
-template <typename TO>
-int truncated_levels(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
-                     int order, TO *out, void *stream, int paired) {
+int truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
+              int order, const double *sigma, TO *out, void *stream, int paired, int levels) {
     if (paired) B = A;
-    if (D < 1 || !Xr || !Yt || !out || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D)
+    if (D < 1 || !Xr || !Yt || !out || (!sigma && !levels) || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N ||
+        fd < D)
         return SK_ERR_BAD_ARG;
     if (A == 0 || B == 0) return SK_OK;
-    return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, nullptr, out, (hipStream_t)stream, paired, 1);
+    return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream, paired, levels);
 }
 
 }  // namespace
@@ -490,35 +472,35 @@ int sk_solve_prefix_linear_f32(const double *dXr, const double *dYt, int64_t A, 
 }
 int sk_truncated_gram_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                           int num_levels, int order, const double *sigma, double *out, void *stream) {
-    return truncated_gram<double>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
+    return truncated<double>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, 0, 0);
 }
 int sk_truncated_gram_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                           int num_levels, int order, const double *sigma, float *out, void *stream) {
-    return truncated_gram<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
+    return truncated<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, 0, 0);
 }
 int sk_truncated_paired_f64(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
                             int order, const double *sigma, double *out, void *stream) {
-    return truncated_paired<double>(Xr, Yt, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
+    return truncated<double>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, 1, 0);
 }
 int sk_truncated_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
                             int order, const double *sigma, float *out, void *stream) {
-    return truncated_paired<float>(Xr, Yt, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream);
+    return truncated<float>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, 1, 0);
 }
 int sk_truncated_levels_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                             int num_levels, int order, double *out, void *stream) {
-    return truncated_levels<double>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, out, stream, 0);
+    return truncated<double>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, nullptr, out, stream, 0, 1);
 }
 int sk_truncated_levels_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                             int num_levels, int order, float *out, void *stream) {
-    return truncated_levels<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, out, stream, 0);
+    return truncated<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, nullptr, out, stream, 0, 1);
 }
 int sk_truncated_levels_paired_f64(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
                                    int num_levels, int order, double *out, void *stream) {
-    return truncated_levels<double>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, out, stream, 1);
+    return truncated<double>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, nullptr, out, stream, 1, 1);
 }
 int sk_truncated_levels_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
                                    int num_levels, int order, float *out, void *stream) {
-    return truncated_levels<float>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, out, stream, 1);
+    return truncated<float>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, nullptr, out, stream, 1, 1);
 }
 int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream) {

@@ -29,9 +29,11 @@ restatement that keeps each level's sum.  ``K`` is linear in them -- ``truncated
 differentiably, and with per-path scales ``(lx[a] ly[b])^m`` in front, because ``k_m(c x, y) = c^m k_m(x, y)`` at every order: every
 truncation below L, every choice of weights and every rescaling of the paths is a re-weighting of ONE sweep's output.
 ``truncated_robust_scales`` solves the scales of Chevyrev and Oberhauser's robust normalisation from the paired self levels.
-"""
-import ctypes
 
+Each thing is stated once.  ``_level_sums`` is the recursion and ``_restatement`` its tiling, behind all three torch routes; the three public
+functions share ``_prepare`` (stage, check), ``_routed`` (try (X, Y), then (Y, X)) and ``_chunked`` (paired launches within the workspace);
+the ctypes call and the staging rule are the backend's (``_lib.HipBackend._truncated``, ``_lib._truncated_staging``).
+"""
 import numpy as np
 import torch
 
@@ -78,10 +80,11 @@ def _check_args(X, Y, num_levels, order):
     return num_levels, (num_levels if order < 1 else order)
 
 
-def _truncated_block(X, Y, L, sig, order, paired=False):
-    """(A, B) of all pairs, or -- paired -- (P,) of the pairs (X[p], Y[p]): everything below G works on its last two axes"""
+def _level_sums(X, Y, L, order, paired=False):
+    """THE recursion: yields k_1 .. k_L, each level's planes summed over the step grid -- (A, B) of all pairs, or -- paired -- (P,) of the
+    pairs (X[p], Y[p]): everything below G works on its last two axes"""
     G = torch.einsum("pid,pjd->pij", X, Y) if paired else torch.einsum("aid,bjd->abij", X, Y)
-    K = sig[0] + sig[1] * G.sum((-2, -1))
+    yield G.sum((-2, -1))
     R = [[G]]
     for m in range(1, L):
         d = min(m + 1, order)
@@ -95,130 +98,61 @@ def _truncated_block(X, Y, L, sig, order, paired=False):
             for q in range(1, d):
                 nxt[p][q] = G * R[p - 1][q - 1] / ((p + 1) * (q + 1))
         R = nxt
-        K = K + sig[m + 1] * sum(sum(row) for row in R).sum((-2, -1))
+        yield sum(sum(row) for row in R).sum((-2, -1))
+
+
+def _block(X, Y, L, order, paired, sig):
+    """one tile: the weighted value sig[0] + sum_m sig[m] k_m, folded level by level as the sums arrive; sig None: the sums themselves,
+    stacked under the ones of level 0"""
+    if sig is None:
+        out = list(_level_sums(X, Y, L, order, paired))
+        return torch.stack([torch.ones_like(out[0])] + out, 0)
+    K = sig[0]
+    for m, k in enumerate(_level_sums(X, Y, L, order, paired), 1):
+        K = K + sig[m] * k
     return K
 
 
-def _levels_block(X, Y, L, order, paired=False):
-    """_truncated_block keeping each level's sum: (L + 1, A, B) of all pairs, or -- paired -- (L + 1, P); plane 0 is the ones of level 0"""
-    G = torch.einsum("pid,pjd->pij", X, Y) if paired else torch.einsum("aid,bjd->abij", X, Y)
-    first = G.sum((-2, -1))
-    out = [torch.ones_like(first), first]
-    R = [[G]]
-    for m in range(1, L):
-        d = min(m + 1, order)
-        total = sum(sum(row) for row in R)
-        nxt = [[None] * d for _ in range(d)]
-        nxt[0][0] = G * _excl(_excl(total, -2), -1)
-        for q in range(1, d):
-            nxt[0][q] = G * _excl(sum(R[p][q - 1] for p in range(len(R))), -2) / (q + 1)
-            nxt[q][0] = G * _excl(sum(R[q - 1]), -1) / (q + 1)
-        for p in range(1, d):
-            for q in range(1, d):
-                nxt[p][q] = G * R[p - 1][q - 1] / ((p + 1) * (q + 1))
-        R = nxt
-        out.append(sum(sum(row) for row in R).sum((-2, -1)))
-    return torch.stack(out, 0)
-
-
-def _truncated_levels_torch(X, Y, num_levels, order=-1, paired=False, workspace_bytes=None):
-    """The level terms k_0 .. k_L in torch ops on the tensors' own device, differentiable: (L + 1, A, B), paired (L + 1, P).  The recursion
-    of _truncated_torch with each level's sum kept, tiled over rows of X (over pairs) by `workspace_bytes` exactly as it is."""
+def _restatement(X, Y, num_levels, sigma, order, paired, workspace_bytes):
+    """The three torch routes: check, empty case, and the recursion tiled over rows of X (over pairs) so that a tile's (2 d^2 + 6) arrays
+    of the step grid -- times the levels autograd keeps -- stay within `workspace_bytes`.  sigma None: the level terms, tiles joined along
+    axis 1 under the level axis; else the weighted value."""
     num_levels, order = _check_args(X, Y, num_levels, order)
     if paired and X.shape[0] != Y.shape[0]:
         raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
+    sig = None if sigma is None else _sigma_vector(sigma, num_levels, X.dtype, X.device)
     A, M = X.shape[0], X.shape[1]
     B, N = Y.shape[0], Y.shape[1]
     shape = (A,) if paired else (A, B)
     if A == 0 or B == 0 or M == 0 or N == 0:
+        if sig is not None:
+            return sig[0] * torch.ones(shape, dtype=X.dtype, device=X.device)
         out = torch.zeros((num_levels + 1,) + shape, dtype=X.dtype, device=X.device)
         out[0] = 1
         return out
     d = min(num_levels, order)
     budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
-    per_row = (1 if paired else B) * M * N * X.element_size() * (2 * d * d + 6) * (num_levels if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad) else 1)
+    kept = num_levels if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad) else 1
+    per_row = (1 if paired else B) * M * N * X.element_size() * (2 * d * d + 6) * kept
     rows = int(max(1, min(A, budget // max(1, per_row))))
-    if paired:
-        return torch.cat([_levels_block(X[a:a + rows], Y[a:a + rows], num_levels, order, True) for a in range(0, A, rows)], 1)
-    return torch.cat([_levels_block(X[a:a + rows], Y, num_levels, order) for a in range(0, A, rows)], 1)
+    return torch.cat([_block(X[a:a + rows], Y[a:a + rows] if paired else Y, num_levels, order, paired, sig) for a in range(0, A, rows)],
+                     1 if sig is None else 0)
+
+
+def _truncated_levels_torch(X, Y, num_levels, order=-1, paired=False, workspace_bytes=None):
+    """The level terms k_0 .. k_L in torch ops on the tensors' own device, differentiable: (L + 1, A, B), paired (L + 1, P).  The recursion
+    of _truncated_torch with each level's sum kept, tiled over rows of X (over pairs) by `workspace_bytes` exactly as it is."""
+    return _restatement(X, Y, num_levels, None, order, paired, workspace_bytes)
 
 
 def _truncated_torch(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=None):
     """The recursion in torch ops on the tensors' own device (any device: the tests drive it on the CPU), differentiable; (A, B)."""
-    num_levels, order = _check_args(X, Y, num_levels, order)
-    sig = _sigma_vector(sigma, num_levels, X.dtype, X.device)
-    A, M = X.shape[0], X.shape[1]
-    B, N = Y.shape[0], Y.shape[1]
-    if A == 0 or B == 0 or M == 0 or N == 0:
-        return sig[0] * torch.ones((A, B), dtype=X.dtype, device=X.device)
-    d = min(num_levels, order)
-    budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
-    per_row = B * M * N * X.element_size() * (2 * d * d + 6) * (num_levels if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad) else 1)
-    rows = int(max(1, min(A, budget // max(1, per_row))))
-    return torch.cat([_truncated_block(X[a:a + rows], Y, num_levels, sig, order) for a in range(0, A, rows)], 0)
+    return _restatement(X, Y, num_levels, sigma, order, False, workspace_bytes)
 
 
 def _truncated_paired_torch(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=None):
     """The recursion on the P pairs (X[p], Y[p]) in torch ops, differentiable; (P,).  Tiled over pairs: nothing of size P x P."""
-    num_levels, order = _check_args(X, Y, num_levels, order)
-    if X.shape[0] != Y.shape[0]:
-        raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
-    sig = _sigma_vector(sigma, num_levels, X.dtype, X.device)
-    P, M, N = X.shape[0], X.shape[1], Y.shape[1]
-    if P == 0 or M == 0 or N == 0:
-        return sig[0] * torch.ones((P,), dtype=X.dtype, device=X.device)
-    d = min(num_levels, order)
-    budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
-    per_pair = M * N * X.element_size() * (2 * d * d + 6) * (num_levels if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad) else 1)
-    pairs = int(max(1, min(P, budget // max(1, per_pair))))
-    return torch.cat([_truncated_block(X[p:p + pairs], Y[p:p + pairs], num_levels, sig, order, paired=True) for p in range(0, P, pairs)], 0)
-
-
-def _truncated_hip(X, Y, num_levels, sig, order, paired=False):
-    """(A, B) -- paired: (P,) -- through k_trunc_sig (the body of HipBackend.truncated_gram / truncated_paired, which have asked
-    sk_route_query).  X, Y contiguous on a HIP device."""
-    A, M, D = X.shape
-    B, N = Y.shape[0], Y.shape[1]
-    out = torch.empty((A,) if paired else (A, B), dtype=X.dtype, device=X.device)
-    if A == 0 or B == 0:
-        return out
-    fd = 8 if D <= 8 else 16
-    Ncp = (N + 15) // 16 * 16
-    lib = _lib.load()
-    sg = (ctypes.c_double * (num_levels + 1))(*[float(v) for v in sig])
-    with _lib._device(X.device):
-        Xr, Yt = _lib._prep_pair(X, Y, False, 1.0, M, Ncp, fd)
-        if paired:
-            fn = getattr(lib, "sk_truncated_paired_" + _lib._suffix(X))
-            rc = fn(_lib._ptr(Xr), _lib._ptr(Yt), A, M, M, N, Ncp, D, fd, num_levels, order, sg, _lib._ptr(out), _lib._stream(X))
-        else:
-            fn = getattr(lib, "sk_truncated_gram_" + _lib._suffix(X))
-            rc = fn(_lib._ptr(Xr), _lib._ptr(Yt), A, B, M, M, N, Ncp, D, fd, num_levels, order, sg, _lib._ptr(out), _lib._stream(X))
-    _lib._check(rc, "sk_truncated_paired" if paired else "sk_truncated_gram")
-    return out
-
-
-def _truncated_levels_hip(X, Y, num_levels, order, paired=False):
-    """(L + 1, A, B) -- paired: (L + 1, P) -- through k_trunc_sig in its levels mode (the body of HipBackend.truncated_levels, which has asked
-    sk_route_query).  X, Y contiguous on a HIP device."""
-    A, M, D = X.shape
-    B, N = Y.shape[0], Y.shape[1]
-    out = torch.empty((num_levels + 1,) + ((A,) if paired else (A, B)), dtype=X.dtype, device=X.device)
-    if A == 0 or B == 0:
-        return out
-    fd = 8 if D <= 8 else 16
-    Ncp = (N + 15) // 16 * 16
-    lib = _lib.load()
-    with _lib._device(X.device):
-        Xr, Yt = _lib._prep_pair(X, Y, False, 1.0, M, Ncp, fd)
-        if paired:
-            fn = getattr(lib, "sk_truncated_levels_paired_" + _lib._suffix(X))
-            rc = fn(_lib._ptr(Xr), _lib._ptr(Yt), A, M, M, N, Ncp, D, fd, num_levels, order, _lib._ptr(out), _lib._stream(X))
-        else:
-            fn = getattr(lib, "sk_truncated_levels_" + _lib._suffix(X))
-            rc = fn(_lib._ptr(Xr), _lib._ptr(Yt), A, B, M, M, N, Ncp, D, fd, num_levels, order, _lib._ptr(out), _lib._stream(X))
-    _lib._check(rc, "sk_truncated_levels_paired" if paired else "sk_truncated_levels")
-    return out
+    return _restatement(X, Y, num_levels, sigma, order, True, workspace_bytes)
 
 
 def truncated_route(D, M, N, num_levels, order, elem_size):
@@ -226,34 +160,35 @@ def truncated_route(D, M, N, num_levels, order, elem_size):
     return int(_lib.load().sk_route_query(_lib.OP_TRUNCATED, int(order), int(D), int(M), int(N), int(num_levels), 0, int(elem_size), 0))
 
 
-def _paired_hip(be, X, Y, num_levels, weights, order, budget):
-    """be.truncated_paired on as many pairs at a time as `budget` bytes of staging hold (all of them, usually); None where it says None"""
-    P, M, D = X.shape
-    fd = 8 if D <= 8 else 16
-    per_pair = 8 * fd * (M + (Y.shape[1] + 15) // 16 * 16)
-    pairs = int(max(1, min(P, budget // per_pair)))
-    parts = []
-    for p in range(0, P, pairs):
-        k = be.truncated_paired(X[p:p + pairs], Y[p:p + pairs], num_levels, weights, order)
-        if k is None:
-            return None
-        parts.append(k)
-    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+def _chunked(call, workspace_bytes, axis):
+    """`call(X, Y)` of a paired backend method, on as many pairs at a time as `workspace_bytes` of fp64 staging hold (all of them, usually)
+    and the parts joined along `axis`; None where `call` says None"""
+    budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
+
+    def run(X, Y):
+        P, M, D = X.shape
+        fd, Ncp = _lib._truncated_staging(D, Y.shape[1])
+        pairs = int(max(1, min(P, budget // (8 * fd * (M + Ncp)))))
+        parts = []
+        for p in range(0, P, pairs):
+            k = call(X[p:p + pairs], Y[p:p + pairs])
+            if k is None:
+                return None
+            parts.append(k)
+        return parts[0] if len(parts) == 1 else torch.cat(parts, axis)
+    return run
 
 
-def _levels_paired_hip(be, X, Y, num_levels, order, budget):
-    """be.truncated_levels(paired=True) on as many pairs at a time as `budget` bytes of staging hold, as _paired_hip; None where it says None"""
-    P, M, D = X.shape
-    fd = 8 if D <= 8 else 16
-    per_pair = 8 * fd * (M + (Y.shape[1] + 15) // 16 * 16)
-    pairs = int(max(1, min(P, budget // per_pair)))
-    parts = []
-    for p in range(0, P, pairs):
-        k = be.truncated_levels(X[p:p + pairs], Y[p:p + pairs], num_levels, order, paired=True)
-        if k is None:
-            return None
-        parts.append(k)
-    return parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+def _routed(call, X, Y, gram):
+    """`call(X, Y)`, or where it says None (SK_ROUTE_FUSED_SWAP: only the second batch fits the kernel's lanes) `call(Y, X)`: k_m(x, y) =
+    k_m(y, x) at every order, so a Gram result has its last two axes transposed back and a paired one is taken as it is.  None when both
+    decline."""
+    K = call(X, Y)
+    if K is None:
+        K = call(Y, X)
+        if K is not None and gram:
+            K = K.transpose(-2, -1).contiguous()
+    return K
 
 
 def _stage(X, Y):
@@ -269,6 +204,23 @@ def _needs_grad(X, Y, sigma):
     return torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad or (isinstance(sigma, torch.Tensor) and sigma.requires_grad))
 
 
+def _prepare(X, Y, num_levels, order, paired):
+    """the public functions' preamble -> (X, Y contiguous on a HIP device, num_levels, order as checked, numpy out?, the backend)"""
+    X, Y, as_numpy = _stage(X, Y)
+    num_levels, order = _check_args(X, Y, num_levels, order)
+    if paired and X.shape[0] != Y.shape[0]:
+        raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
+    X, Y = X.contiguous(), Y.contiguous()
+    _lib._dev(X, "X")
+    _lib._dev(Y, "Y")
+    return X, Y, num_levels, order, as_numpy, _lib.get_backend()
+
+
+def _hip_serves(be, method, X, Y, sigma):
+    """no gradient pending, no empty axis, and a backend that has `method` (the HIP kernel is forward only)"""
+    return not _needs_grad(X, Y, sigma) and min(X.shape[0], X.shape[1], Y.shape[0], Y.shape[1]) > 0 and hasattr(be, method)
+
+
 def truncated_sig_kernel_paired(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=None):
     """The truncated signature kernel of the pairs (X[p], Y[p]): X (P, M, D) and Y (P, N, D) hold STEPS, the result is (P,) with
     ``out[p] = truncated_sig_kernel(X[p:p+1], Y[p:p+1], ...)[0, 0]`` -- the diagonal of the matrix without the matrix.  ``num_levels``,
@@ -279,22 +231,13 @@ def truncated_sig_kernel_paired(X, Y, num_levels, sigma=1., order=-1, workspace_
     torch restatement.  Nothing of size P x P is built on either route, and ``workspace_bytes`` (default 1 GiB) bounds what is: the torch
     route is tiled over pairs by it, and the HIP route's fp64 staging of the paths (8 or 16 doubles per step) is too -- a batch whose
     staging exceeds it goes in several launches."""
-    X, Y, as_numpy = _stage(X, Y)
-    num_levels, order = _check_args(X, Y, num_levels, order)
-    if X.shape[0] != Y.shape[0]:
-        raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
-    X, Y = X.contiguous(), Y.contiguous()
-    _lib._dev(X, "X")
-    _lib._dev(Y, "Y")
+    X, Y, num_levels, order, as_numpy, be = _prepare(X, Y, num_levels, order, True)
     sig = _sigma_vector(sigma, num_levels, X.dtype, X.device)
-    be = _lib.get_backend()
     k = None
-    if not _needs_grad(X, Y, sigma) and min(X.shape[0], X.shape[1], Y.shape[1]) > 0 and hasattr(be, "truncated_paired"):
+    if _hip_serves(be, "truncated_paired", X, Y, sigma):
         weights = sig.detach().double().cpu().tolist()
-        budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
-        k = _paired_hip(be, X.detach(), Y.detach(), num_levels, weights, order, budget)
-        if k is None:       # SK_ROUTE_FUSED_SWAP: k(x, y) = k(y, x) at every order, so the same launch on (Y, X) and nothing to transpose
-            k = _paired_hip(be, Y.detach(), X.detach(), num_levels, weights, order, budget)
+        call = lambda x, y: be.truncated_paired(x, y, num_levels, weights, order)
+        k = _routed(_chunked(call, workspace_bytes, 0), X.detach(), Y.detach(), False)
     if k is None:
         k = _truncated_paired_torch(X, Y, num_levels, sig, order, workspace_bytes)
     return k.cpu().numpy() if as_numpy else k
@@ -322,21 +265,12 @@ def truncated_sig_kernel(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=N
     raises ValueError naming the argument; that check reads one flag per batch back from the device, so a normalised call synchronises
     with the host where the plain one does not.  With a gradient both parts take the torch route and autograd covers the quotient."""
     same = Y is X
-    X, Y, as_numpy = _stage(X, Y)
-    num_levels, order = _check_args(X, Y, num_levels, order)
-    X, Y = X.contiguous(), Y.contiguous()
-    _lib._dev(X, "X")
-    _lib._dev(Y, "Y")
+    X, Y, num_levels, order, as_numpy, be = _prepare(X, Y, num_levels, order, False)
     sig = _sigma_vector(sigma, num_levels, X.dtype, X.device)
-    needs_grad = _needs_grad(X, Y, sigma)
-    be = _lib.get_backend()
     K = None
-    if not needs_grad and min(X.shape[0], X.shape[1], Y.shape[0], Y.shape[1]) > 0 and hasattr(be, "truncated_gram"):
+    if _hip_serves(be, "truncated_gram", X, Y, sigma):
         weights = sig.detach().double().cpu().tolist()
-        K = be.truncated_gram(X.detach(), Y.detach(), num_levels, weights, order)
-        if K is None:       # SK_ROUTE_FUSED_SWAP: only the second batch fits the kernel's lanes -- K(x, y) = K(y, x)^T at every order
-            Kt = be.truncated_gram(Y.detach(), X.detach(), num_levels, weights, order)
-            K = None if Kt is None else Kt.t().contiguous()
+        K = _routed(lambda x, y: be.truncated_gram(x, y, num_levels, weights, order), X.detach(), Y.detach(), True)
     if K is None:
         K = _truncated_torch(X, Y, num_levels, sig, order, workspace_bytes)
     if normalize:
@@ -356,27 +290,11 @@ def truncated_sig_kernel_levels(X, Y, num_levels, order=-1, paired=False, worksp
     on (Y, X) with every level transposed when only the second batch fits the lanes.  Inputs that require grad and shapes outside the
     scope take the differentiable torch restatement, tiled by ``workspace_bytes`` (default 1 GiB) as truncated_sig_kernel's; the paired HIP
     route's staging is bounded by it as truncated_sig_kernel_paired's."""
-    X, Y, as_numpy = _stage(X, Y)
-    num_levels, order = _check_args(X, Y, num_levels, order)
-    if paired and X.shape[0] != Y.shape[0]:
-        raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
-    X, Y = X.contiguous(), Y.contiguous()
-    _lib._dev(X, "X")
-    _lib._dev(Y, "Y")
-    be = _lib.get_backend()
+    X, Y, num_levels, order, as_numpy, be = _prepare(X, Y, num_levels, order, paired)
     K = None
-    if not _needs_grad(X, Y, None) and min(X.shape[0], X.shape[1], Y.shape[0], Y.shape[1]) > 0 and hasattr(be, "truncated_levels"):
-        Xd, Yd = X.detach(), Y.detach()
-        if paired:
-            budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
-            K = _levels_paired_hip(be, Xd, Yd, num_levels, order, budget)
-            if K is None:       # SK_ROUTE_FUSED_SWAP: k_m(x, y) = k_m(y, x) at every order, nothing to transpose
-                K = _levels_paired_hip(be, Yd, Xd, num_levels, order, budget)
-        else:
-            K = be.truncated_levels(Xd, Yd, num_levels, order)
-            if K is None:       # SK_ROUTE_FUSED_SWAP: every level of (y, x) is the transpose of that level of (x, y)
-                Kt = be.truncated_levels(Yd, Xd, num_levels, order)
-                K = None if Kt is None else Kt.transpose(1, 2).contiguous()
+    if _hip_serves(be, "truncated_levels", X, Y, None):
+        call = lambda x, y: be.truncated_levels(x, y, num_levels, order, paired=paired)
+        K = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
     if K is None:
         K = _truncated_levels_torch(X, Y, num_levels, order, paired, workspace_bytes)
     return K.cpu().numpy() if as_numpy else K
