@@ -63,7 +63,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -116,6 +116,10 @@ const char *sk_cost_note(int which);
                                  order 1 with M <= 128 (two rows per lane) or order <= 4 with M <= 64 (one), and 8 (dim <= 8; else 16) x
                                  ceil16(N) <= 2048 (the y block of a wave in 16 KB of LDS); SK_ROUTE_FUSED_SWAP = the same on (y, x), the
                                  result transposed; SK_ROUTE_STREAM = the host layer's torch restatement (differentiable). */
+#define SK_OP_TRUNCATED_ADJOINT 5 /* the gradient of the truncated kernel's level terms with respect to the FIRST batch (kind, dyadic, M, N as
+                                 SK_OP_TRUNCATED): SK_ROUTE_FUSED = sk_truncated_adjoint: inside SK_OP_TRUNCATED's FUSED scope, order 1 (kind 1, or
+                                 num_levels 1), path dim <= 8, M <= 128; SK_ROUTE_STREAM otherwise = autograd of the host layer's torch
+                                 restatement.  Never swapped: the second batch's gradient is the same query on (N, M). */
 #define SK_ROUTE_STREAM 0
 #define SK_ROUTE_FUSED 1
 #define SK_ROUTE_FUSED_MB 2
@@ -514,6 +518,21 @@ int sk_truncated_levels_paired_f64(const double *Xr, const double *Yt, int64_t P
                                    int num_levels, int order, double *out, void *stream);
 int sk_truncated_levels_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
                                    int num_levels, int order, float *out, void *stream);
+/* The GRADIENT of the level terms with respect to the first batch, by the same kernel in its adjoint mode (no counterpart in the reference,
+ * whose truncated kernel is numpy): for weights w [num_levels][A][B] (device fp64; paired: [num_levels][P]) -- the upstream gradient of level
+ * m + 1 of every pair -- the chunks' parts of d / dX sum_pairs sum_m w[m][pair] k_{m+1}(pair) go to Tpart [n_chunks][A][M][8]; the caller
+ * adds the chunks (dX = sum over the first axis, the first D of the 8 columns).  Per pair one forward sweep that stores the num_levels - 1
+ * prefix factors of every node to `slab`, and one reverse sweep that reads them back; plain stores, no atomics: bit-reproducible.
+ *   sk_truncated_adjoint_plan  plan[0..2] = n_chunks, blocks, slab bytes of the shape, the slab within workspace_bytes (the block count is
+ *                              lowered until it fits); SK_ERR_UNSUPPORTED when one block's slab, (num_levels - 1) (N + W - 1) KB with W the
+ *                              lanes of a pair's group, does not.  Host only.
+ *   sk_truncated_adjoint       Xr, Yt, Mrows, Ncp, fd as sk_truncated_gram_* (fd = 8); n_chunks in 1 .. B (paired: 1), usually the plan's;
+ *                              slab / slab_bytes: device scratch, may be NULL / 0 at num_levels = 1.
+ * Scope: sk_route_query(SK_OP_TRUNCATED_ADJOINT, 1, D, M, N, num_levels, ...) == SK_ROUTE_FUSED -- order 1, D <= 8; else SK_ERR_UNSUPPORTED. */
+int sk_truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes, int64_t *plan);
+int sk_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                         int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
+                         int paired);
 /* Symmetric Gram matrix of ONE path batch with the fused kernels above: only the A (A + 1) / 2 pairs on and above the diagonal are
  * solved (what the reference's CPU solver does for sym=True, cython_backend.pyx:74-97; its GPU path ignores `sym`), in ONE launch,
  * and each value is written to out[a][b] and out[b][a]: out [A][A] is exactly symmetric.  dXr / dXt (Xr / Xt): the row-major and

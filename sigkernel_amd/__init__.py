@@ -11,10 +11,10 @@ from .sigkernel import SigKernel, _SigKernel, _SigKernelGram, k_kgrad, pad_paths
 from .stats import SigCHSIC, c_alpha, hypothesis_test
 from .transforms import AddTime, LeadLag, add_time, lead_lag, transform
 from .truncated import (truncated_sig_kernel, truncated_sig_kernel_paired, truncated_sig_kernel_levels, truncated_from_levels,
-                        truncated_robust_scales)
+                        truncated_robust_scales, TruncatedSigKernel)
 
 __all__ = ["SigKernel", "LinearKernel", "RBFKernel", "_SigKernel", "_SigKernelGram", "hypothesis_test", "SigCHSIC",
            "c_alpha", "transform", "add_time", "lead_lag", "AddTime", "LeadLag", "k_kgrad", "routes", "Linear_ID_Kernel", "RBF_ID_Kernel",
            "RBF_CEXP_Kernel", "RBF_SQR_Kernel", "CEXP", "cos_exp_kernel", "truncated_sig_kernel", "truncated_sig_kernel_paired", "truncated_sig_kernel_levels",
-           "truncated_from_levels", "truncated_robust_scales", "pad_paths"]
+           "truncated_from_levels", "truncated_robust_scales", "TruncatedSigKernel", "pad_paths"]
 __version__ = "0.1.0"

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libsigkernel_amd.so")
 
 SK_OK = 0
 # sk_route_query: operations and answers (include/sigkernel_amd.h)
-OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED = 0, 1, 2, 3, 4
+OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED, OP_TRUNCATED_ADJOINT = 0, 1, 2, 3, 4, 5
 ROUTE_STREAM, ROUTE_FUSED, ROUTE_FUSED_MB, ROUTE_FUSED_MB_SWAP, ROUTE_FUSED_SWAP = 0, 1, 2, 3, 4
 ROUTE_NO_STREAM = 1
 ROUTE_NO_SWAP = 2
@@ -95,6 +95,8 @@ SIGNATURES = {
     "sk_truncated_levels_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
     "sk_truncated_levels_paired_f64": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
     "sk_truncated_levels_paired_f32": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
+    "sk_truncated_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
+    "sk_truncated_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
     "sk_prep_pair_f64": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_prep_pair_f32": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_solve_fwd_static_workspace_bytes": (_sz, [_int, _i64, _int, _int, _int, _int]),
@@ -691,6 +693,51 @@ class HipBackend:
     def truncated_levels(self, X, Y, num_levels, order, paired=False):
         """The level terms k_0 .. k_L from ONE sweep per pair (the kernel's levels mode): (num_levels + 1, A, B), paired (num_levels + 1, P)."""
         return self._truncated(X, Y, num_levels, order, bool(paired), None)
+
+    def truncated_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
+        """whether truncated_adjoint serves the shape: SK_OP_TRUNCATED_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""
+        if self.route(OP_TRUNCATED_ADJOINT, 1, D, M, N, num_levels, False, elem_size) != ROUTE_FUSED:
+            return False
+        plan = (ctypes.c_int64 * 3)()
+        budget = (1 << 30) if workspace_bytes is None else max(0, int(workspace_bytes))
+        rc = load().sk_truncated_adjoint_plan(max(1, int(A)), max(1, int(B)), M, N, D, int(num_levels), int(bool(paired)), budget,
+                                              ctypes.cast(plan, ctypes.c_void_p))
+        if rc != 2:
+            _check(rc, "sk_truncated_adjoint_plan")
+        return rc == SK_OK
+
+    def truncated_adjoint(self, X, Y, w, num_levels, paired=False, workspace_bytes=None):
+        """The gradient of ``sum_pairs sum_m w[m - 1, pair] k_m(pair)`` with respect to X, by k_trunc_sig<1, 2> in its adjoint mode
+        (sk_truncated_adjoint): X (A, M, D) / Y (B, N, D) hold steps, w is (num_levels, A, B) -- paired (num_levels, P) -- and the result
+        (A, M, D) in fp64.  One launch: the kernel writes a part of dX per chunk of second paths (Tpart, chunks x A x M x 8 doubles) and
+        torch adds the chunks; between its two sweeps of a pair a block keeps the prefix factors in a slab of (num_levels - 1) x
+        (N + lanes - 1) KB, all blocks' within `workspace_bytes` (default 1 GiB; the block count is lowered until they fit).  None
+        outside the scope (sk_route_query(SK_OP_TRUNCATED_ADJOINT) != FUSED: order 1, dim <= 8) or when one block's slab does not fit."""
+        _dev(X, "X")
+        _dev(Y, "Y")
+        (A, M, D), (B, N), L = X.shape, Y.shape[:2], int(num_levels)
+        if self.route(OP_TRUNCATED_ADJOINT, 1, D, M, N, L, False, X.element_size()) != ROUTE_FUSED:
+            return None
+        if A == 0 or B == 0:
+            return torch.zeros(A, M, D, dtype=torch.float64, device=X.device)
+        lib = load()
+        plan = (ctypes.c_int64 * 3)()
+        budget = (1 << 30) if workspace_bytes is None else max(0, int(workspace_bytes))
+        rc = lib.sk_truncated_adjoint_plan(A, B, M, N, D, L, int(bool(paired)), budget, ctypes.cast(plan, ctypes.c_void_p))
+        if rc == 2:
+            return None
+        _check(rc, "sk_truncated_adjoint_plan")
+        n_chunks, slab_bytes = int(plan[0]), int(plan[2])
+        fd, Ncp = _truncated_staging(D, N)
+        w = w.to(dtype=torch.float64, device=X.device).contiguous()
+        with _device(X.device):
+            Xr, Yt = _prep_pair(X, Y, False, 1.0, M, Ncp, fd)
+            Tpart = torch.empty(n_chunks, A, M, fd, dtype=torch.float64, device=X.device)
+            slab = torch.empty(slab_bytes // 8, dtype=torch.float64, device=X.device) if slab_bytes else None
+            rc = lib.sk_truncated_adjoint(_ptr(Xr), _ptr(Yt), A, B, M, M, N, Ncp, D, fd, L, _ptr(w), _ptr(Tpart), n_chunks,
+                                          _ptr(slab) if slab is not None else None, slab_bytes, _stream(X), int(bool(paired)))
+        _check(rc, "sk_truncated_adjoint")
+        return (Tpart[0] if n_chunks == 1 else Tpart.sum(0))[:, :, :D]
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):
         """The loss wrappers' forward in THREE launches (csrc/sk_loss.hip): [X; Y] staged in both layouts straight from the two

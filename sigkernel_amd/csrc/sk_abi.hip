@@ -250,7 +250,7 @@ int device_cu_count() {
 
 extern "C" {
 
-// (340 still: sk_truncated_levels_{,paired_}{f64,f32} are additions, no exported signature changed)
+// (340 still: sk_truncated_levels_{,paired_}{f64,f32}, sk_truncated_adjoint and its plan are additions, no exported signature changed)
 // 340: sk_static_increments_* serve any path dim (D > 32: k_static_wide_mfma); sk_static_adjoint_* kind 1 with D > 32 writes the first
 // pass H [P][M][ldh] of the rbf chain rule instead of dL/dX
 // 330 (round 6): sk_linear_adjoint_fused_f64 takes ypart / ypart_doubles / ycols_out (the second-argument sums, route FUSED_SWAP)
@@ -501,6 +501,24 @@ int sk_truncated_levels_paired_f64(const double *Xr, const double *Yt, int64_t P
 int sk_truncated_levels_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
                                    int num_levels, int order, float *out, void *stream) {
     return truncated<float>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, nullptr, out, stream, 1, 1);
+}
+int sk_truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes, int64_t *plan) {
+    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
+    size_t slab = 0;
+    const int rc = truncated_adjoint_plan(A, B, M, N, D, num_levels, paired, workspace_bytes, plan, plan + 1, &slab);
+    if (rc == SK_OK) plan[2] = (int64_t)slab;
+    return rc;
+}
+int sk_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                         int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
+                         int paired) {
+    if (paired) B = A;
+    if (D < 1 || !Xr || !Yt || !w || !Tpart || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D ||
+        (slab_bytes && !slab))
+        return SK_ERR_BAD_ARG;
+    if (A == 0 || B == 0) return SK_OK;
+    return launch_truncated_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, w, Tpart, n_chunks, slab, slab_bytes,
+                                    (hipStream_t)stream, paired);
 }
 int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream) {

@@ -195,6 +195,15 @@ template <typename TO>
 int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
                      int order, const double *sigma, TO *out, hipStream_t s, int paired = 0, int levels = 0);
 bool truncated_in_scope(int D, int M, int N, int L, int order);   // the kernel's scope = the SK_OP_TRUNCATED rule of sk_route_query
+// The ADJOINT mode of k_trunc_sig<1, 2> (order 1, dim <= 8): Tpart [n_chunks][A][M][8] takes the chunks' parts of the gradient of
+// sum_pairs sum_m w[m - 1][pair] k_m(pair) with respect to the rows of x; w [L][A][B] (paired [L][A]) on the device.  slab: slab_bytes of
+// device memory for the prefix factors a block keeps between its two phases (none at L = 1).  The plan gives the chunk count, the
+// blocks and the slab bytes of a shape within `workspace` bytes; SK_ERR_UNSUPPORTED outside the scope or when one block's slab does not fit.
+int truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks, int64_t *blocks,
+                           size_t *slab_bytes);
+int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
+                             const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s, int paired);
+bool truncated_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_ADJOINT rule of sk_route_query
 
 // ---- sk_loss.hip: the glue of the loss wrappers (compute_mmd / scoring rules) as single launches ----
 template <typename T>

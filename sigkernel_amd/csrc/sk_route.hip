@@ -161,6 +161,13 @@ int route_query(int op, int kind, int D, int M, int N, int d, int naive, int ele
         if (!(flags & SK_ROUTE_NO_SWAP) && truncated_in_scope(D, N, M, d, kind)) return SK_ROUTE_FUSED_SWAP;
         return SK_ROUTE_STREAM;
     }
+    if (op == SK_OP_TRUNCATED_ADJOINT) {
+        // the gradient of the truncated kernel's level terms with respect to the FIRST batch (kind, d, M, N as above): FUSED = the adjoint
+        // mode of k_trunc_sig<1, 2> (truncated_adjoint_in_scope is the rule), STREAM = autograd of the torch restatement.  Never swapped: the
+        // gradient of the second batch is the same query on (N, M).
+        if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
+        return truncated_adjoint_in_scope(D, M, N, d, kind) ? SK_ROUTE_FUSED : SK_ROUTE_STREAM;
+    }
     if ((kind != 0 && kind != 1) || D < 1 || D > 16 || M < 2 || N < 2 || d < 0 || d > 2) return SK_ROUTE_STREAM;
     if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
     const int Mc = M - 1, Nc = N - 1;

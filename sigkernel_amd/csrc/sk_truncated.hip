@@ -30,6 +30,9 @@
 // instead of their weighted sum, out[m][pair].  The step loop is the plain launch's, run with the weights (0, .., 0, 1): acc is then
 // level L, and the totals of the levels below are the running row sums rowS the loop keeps anyway.  The mode is an epilogue: a sum over
 // the lane's rows and the group's butterfly per level, and L + 1 stores per pair where the plain launch has one.
+// ADJOINT mode (TruncParams::adjoint, launch-time and wave-uniform, the <1, 2> instance only: order 1, fd = 8): the gradient of a weighted
+// sum of the pairs' level terms with respect to the rows of x, in Gram and paired mode -- trunc_adjoint below, with loops of its own; the
+// forward launches run the step loop they ran.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
 // order (1: one plane per level, or TR_OMAX) and the rows per lane.
 #include "sk_wave_common.h"
@@ -50,7 +53,184 @@ struct TruncParams {
     int paired;         // 0: the Gram matrix of A x B pairs; 1: the A = B pairs (x_p, y_p), one per lane group
     int levels;         // 0: one weighted value per pair; 1: the pair's L + 1 level terms, one plane of `out` per level
     double sigma[TR_LMAX + 1];
+    // ADJOINT mode (order 1, fd = 8: trunc_adjoint below).  `out` is not used.
+    int adjoint;        // 0: a forward launch; 1: dX of sum_pairs sum_m w[m][pair] k_m
+    int64_t n_chunks;   // Gram: the B pairs of a row tile go to this many positions; paired: 1
+    const double *w;    // [L][A][B], paired [L][A]: the weight of level m + 1 of every pair
+    double *Tpart;      // [n_chunks][A][M][8]: the chunks' parts of dX, summed by the caller
+    double *slab;       // [blocks][L - 1][N + W - 1][128]: a block's prefix factors between its two phases
 };
+
+// ADJOINT mode of k_trunc_sig<1, 2> (TruncParams::adjoint, launch-time and wave-uniform): the gradient with respect to the rows of x of
+//     sum_pairs sum_{m = 1 .. L} w_m(pair) k_m(pair),      k_m = sum_nodes R^m,  R^1 = G,  R^{m+1} = G P^m,  P^m = exclusive 2-D prefix of R^m.
+// With Rb^L = w_L and Rb^m = w_m + (exclusive 2-D SUFFIX of G Rb^{m+1}):  dG = sum_m Rb^m P^{m-1} (P^0 = 1),  dx_i = sum_j dG[i][j] y_j.
+// Rb needs G and w only, so the reverse sweep is the forward one mirrored; what it needs from the forward are the L - 1 prefix factors
+// of every node.  One position therefore runs two phases per pair, a lane keeping its two rows in both:
+//   phase 1  the forward step loop without its sums, storing per step t and level s < L - 1 the lane's qin[s] of both rows as they are
+//            BEFORE the node joins them (= P^{s+1}) to the block's slab in HBM, slab[(s steps + t) 128 + 2 lane + r]: one store
+//            instruction writes 1 KB contiguously;
+//   phase 2  steps backwards: lane l runs one column behind lane l + 1, row 1 before row 0, the hand-ups (per level the 2-D suffix of
+//            U^m = G Rb^m, mirroring qio) come from the lane below by DPP wave_shl:1 with 0 into a group's last lane, rowT mirrors rowS.
+//            Step t of phase 1 is step steps - 1 - t here for EVERY lane, so the lane reads back exactly the 16 bytes it wrote at that
+//            step: nothing beyond program order is needed, and the loads are as contiguous as the stores.
+// Pairs: a position keeps ONE tile of rows a (G lane groups) and walks a chunk of consecutive b, restaging the y block per b; dX stays in
+// registers across the chunk and is stored once, with plain stores, to the chunk's plane of Tpart -- no atomics, and the result does not
+// depend on scheduling.  Paired: one pair per lane group with its own y block as in the forward, chunks of one pair.
+// Padding rows and columns have G = 0; dG is masked off the columns exactly as g is, and rows beyond M are never stored.
+__device__ __forceinline__ void trunc_adjoint(const TruncParams &prm, double *ylds) {
+    constexpr int NS = TR_LMAX - 1;
+    const int lane = threadIdx.x;
+    const int W = 1 << prm.logW, G = WAVE >> prm.logW;
+    const int lam = lane & (W - 1), grp = lane >> prm.logW;
+    const int N = prm.N, Ncp = prm.Ncp, L = prm.L;
+    const int steps = N + W - 1;
+    const bool paired = prm.paired != 0;
+    const int64_t plane = paired ? prm.A : prm.A * prm.B;
+    double2 *slab = reinterpret_cast<double2 *>(prm.slab + (int64_t)blockIdx.x * (L - 1) * steps * 128) + lane;
+    for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
+        int64_t a, b0, b1, chunk = 0;
+        int nblk = 1;
+        if (paired) {
+            b0 = pos * G;
+            b1 = b0 + 1;
+            a = b0 + grp;
+            nblk = prm.A - b0 < G ? (int)(prm.A - b0) : G;
+        } else {
+            const int64_t at = pos / prm.n_chunks;
+            chunk = pos - at * prm.n_chunks;
+            b0 = chunk * prm.B / prm.n_chunks;
+            b1 = (chunk + 1) * prm.B / prm.n_chunks;
+            a = at * G + grp;
+        }
+        const bool live = a < prm.A;
+        const double *yl = ylds + ((paired && live) ? grp * 8 * Ncp : 0);
+        double xr[2][8], dX[2][8];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int row = lam * 2 + r;
+            const bool ok = live && row < prm.M;
+            const double *xp = prm.Xr + ((ok ? a : 0) * (int64_t)prm.Mrows + (ok ? row : 0)) * 8;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                xr[r][k] = ok ? xp[k] : 0.0;
+                dX[r][k] = 0.0;
+            }
+        }
+        for (int64_t b = b0; b < b1; ++b) {
+            __syncthreads();
+            {
+                const double *yb = prm.Yt + b * (int64_t)8 * Ncp;
+                for (int k = lane; k < nblk * 8 * Ncp; k += WAVE) ylds[k] = yb[k];
+            }
+            double w[TR_LMAX];
+#pragma unroll
+            for (int m = 0; m < TR_LMAX; ++m) w[m] = (live && m < L) ? prm.w[m * plane + (paired ? a : a * prm.B + b)] : 0.0;
+            __syncthreads();
+            {   // phase 1
+                double rowS[2][NS], qio[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) qio[s] = rowS[0][s] = rowS[1][s] = 0.0;
+                for (int t = 0; t < steps; ++t) {
+                    const int j = t - lam;
+                    const bool act = (unsigned)j < (unsigned)N;
+                    const int jc = act ? j : 0;
+                    double qin[NS], pf[2][NS], yv[8];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        const double v = s < L - 1 ? dpp_shr1_zero(qio[s]) : 0.0;
+                        qin[s] = lam == 0 ? 0.0 : v;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) yv[k] = yl[k * Ncp + jc];
+                    asm volatile("s_waitcnt lgkmcnt(0)"
+                                 : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        double g = 0.0;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) g = fma(xr[r][k], yv[k], g);
+                        g = act ? g : 0.0;
+                        double prev = g;
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) {
+                            pf[r][s] = qin[s];
+                            if (s < L - 1) {
+                                const double next = g * qin[s];
+                                qin[s] = qin[s] + rowS[r][s];
+                                rowS[r][s] += prev;
+                                prev = next;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        if (s < L - 1) slab[((int64_t)s * steps + t) * 64] = make_double2(pf[0][s], pf[1][s]);
+                        qio[s] = qin[s];
+                    }
+                }
+            }
+            {   // phase 2
+                double rowT[2][NS], sio[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) sio[s] = rowT[0][s] = rowT[1][s] = 0.0;
+                for (int t = steps - 1; t >= 0; --t) {
+                    const int j = t - lam;
+                    const bool act = (unsigned)j < (unsigned)N;
+                    const int jc = act ? j : 0;
+                    double sup[NS], yv[8];
+                    double2 pf[NS];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        pf[s] = s < L - 1 ? slab[((int64_t)s * steps + t) * 64] : make_double2(0.0, 0.0);
+                        const double v = s < L - 1 ? dpp_shl1(sio[s], 0.0) : 0.0;
+                        sup[s] = lam == W - 1 ? 0.0 : v;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) yv[k] = yl[k * Ncp + jc];
+                    asm volatile("s_waitcnt lgkmcnt(0)"
+                                 : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                    for (int r = 1; r >= 0; --r) {
+                        double g = 0.0;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) g = fma(xr[r][k], yv[k], g);
+                        g = act ? g : 0.0;
+                        double rb = 0.0, dG = 0.0;
+#pragma unroll
+                        for (int m = TR_LMAX; m >= 1; --m)
+                            if (m <= L) {
+                                rb = m == L ? w[m - 1] : rb;
+                                dG = m == 1 ? dG + rb : fma(rb, r ? pf[m > 1 ? m - 2 : 0].y : pf[m > 1 ? m - 2 : 0].x, dG);
+                                if (m > 1) {
+                                    const int s = m - 2;
+                                    const double u = g * rb;
+                                    rb = w[s] + sup[s];
+                                    sup[s] = sup[s] + rowT[r][s];
+                                    rowT[r][s] += u;
+                                }
+                            }
+                        dG = act ? dG : 0.0;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) dX[r][k] = fma(dG, yv[k], dX[r][k]);
+                    }
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) sio[s] = sup[s];
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int row = lam * 2 + r;
+                if (row < prm.M) {
+                    double *tp = prm.Tpart + ((chunk * prm.A + a) * prm.M + row) * 8;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) tp[k] = dX[r][k];
+                }
+            }
+        }
+    }
+}
 
 template <int OM, int RC>
 __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
@@ -64,6 +244,12 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     const bool wide = fd > 8;
     const int steps = N + W - 1;
     const bool paired = prm.paired != 0;
+    if constexpr (OM == 1 && RC == 2) {
+        if (prm.adjoint) {      // its own two loops: the forward launches' step loop below is as it was
+            trunc_adjoint(prm, ylds);
+            return;
+        }
+    }
     for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
         int64_t a, b;           // the lane group's row of Xr; the first y block the wave stages
         int nblk = 1;           // ... and how many: one per live group in paired mode
@@ -289,6 +475,7 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
     prm.out_f32 = sizeof(TO) == 4;
     prm.paired = paired != 0;
     prm.levels = levels != 0;
+    prm.adjoint = 0; prm.n_chunks = 1; prm.w = nullptr; prm.Tpart = nullptr; prm.slab = nullptr;
     for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = levels ? (m == L ? 1.0 : 0.0) : (m <= L ? sigma[m] : 0.0);
     const int RC = prm.order == 1 ? 2 : 1;
     const int lanes = (M + RC - 1) / RC;
@@ -304,6 +491,82 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
     const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
     if (RC == 2) SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     else SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
+    return check_launch();
+}
+
+// THE scope of the adjoint mode (the SK_OP_TRUNCATED_ADJOINT rule of sk_route_query): order 1, and a path dim of at most 8 -- xr, yv, the
+// dX accumulators and both phases' per-level state then stay within the 256 registers two waves per SIMD leave a lane.
+bool truncated_adjoint_in_scope(int D, int M, int N, int L, int order) {
+    return truncated_in_scope(D, M, N, L, order) && trunc_order(L, order) == 1 && D <= 8 && M <= 128;
+}
+
+namespace {
+struct AdjointPlan {
+    int logW;
+    int64_t n_pos, n_chunks, blocks;
+    size_t block_bytes;     // a block's slab: (L - 1) levels x (N + W - 1) steps x 1 KB
+};
+// The split of an adjoint launch.  Gram: the B pairs of a row tile in as many chunks as fill the resident blocks (at most B; lengths
+// differ by one at most).  The block count is lowered until blocks x slab fits `workspace`; false when one block does not.
+bool plan_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int L, int paired, size_t workspace, AdjointPlan *pl) {
+    const int lanes = (M + 1) / 2;
+    int logW = 0;
+    while ((1 << logW) < lanes) ++logW;
+    while (paired && (int64_t)(WAVE >> logW) * 8 * Ncp > TR_LDS_DOUBLES) ++logW;
+    const int G = WAVE >> logW;
+    const int64_t tiles = (A + G - 1) / G, resident = (int64_t)device_cu_count() * 8;
+    pl->logW = logW;
+    pl->n_chunks = 1;
+    if (!paired) {
+        pl->n_chunks = resident / tiles;
+        if (pl->n_chunks > B) pl->n_chunks = B;
+        if (pl->n_chunks < 1) pl->n_chunks = 1;
+    }
+    pl->n_pos = tiles * pl->n_chunks;
+    pl->blocks = pl->n_pos < resident ? pl->n_pos : resident;
+    pl->block_bytes = (size_t)(L - 1) * (size_t)(N + (1 << logW) - 1) * 1024;
+    if (pl->block_bytes) {
+        const int64_t fit = (int64_t)(workspace / pl->block_bytes);
+        if (fit < 1) return false;
+        if (pl->blocks > fit) pl->blocks = fit;
+    }
+    return true;
+}
+}  // namespace
+
+int truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                           int64_t *blocks, size_t *slab_bytes) {
+    if (!truncated_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    AdjointPlan pl;
+    if (!plan_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
+    *n_chunks = pl.n_chunks;
+    *blocks = pl.blocks;
+    *slab_bytes = (size_t)pl.blocks * pl.block_bytes;
+    return SK_OK;
+}
+
+int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
+                             const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s, int paired) {
+    if (!truncated_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    if (fd != 8 || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
+    if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
+    AdjointPlan pl;
+    if (!plan_adjoint(A, B, M, N, Ncp, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
+    TruncParams prm;
+    prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
+    prm.A = A; prm.B = B;
+    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
+    prm.order = 1; prm.out_f32 = 0;
+    prm.paired = paired != 0;
+    prm.levels = 0;
+    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
+    prm.adjoint = 1; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
+    prm.logW = pl.logW;
+    const int G = WAVE >> pl.logW;
+    prm.n_pos = (A + G - 1) / G * n_chunks;     // the caller's chunk count (Tpart is sized by it); the plan's block count for the slab
+    int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
+    const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
+    SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     return check_launch();
 }
 

@@ -33,6 +33,11 @@ truncation below L, every choice of weights and every rescaling of the paths is 
 Each thing is stated once.  ``_level_sums`` is the recursion and ``_restatement`` its tiling, behind all three torch routes; the three public
 functions share ``_prepare`` (stage, check), ``_routed`` (try (X, Y), then (Y, X)) and ``_chunked`` (paired launches within the workspace);
 the ctypes call and the staging rule are the backend's (``_lib.HipBackend._truncated``, ``_lib._truncated_staging``).
+
+``TruncatedSigKernel`` is the SigKernel-shaped front (paths in, ``compute_Gram`` / ``compute_kernel`` / ``compute_mmd``) and the one place where
+a gradient stays on the HIP route: ``_TruncatedLevels`` is an autograd function on the level terms whose forward is the levels mode and
+whose backward is the kernel's adjoint mode (``HipBackend.truncated_adjoint``: order 1, dim <= 8).  The three functions above keep their
+rule -- a gradient pending means the torch restatement.
 """
 import numpy as np
 import torch
@@ -40,7 +45,7 @@ import torch
 from . import _lib
 
 __all__ = ["truncated_sig_kernel", "truncated_sig_kernel_paired", "truncated_sig_kernel_levels", "truncated_from_levels",
-           "truncated_robust_scales"]
+           "truncated_robust_scales", "TruncatedSigKernel"]
 
 _DEFAULT_WORKSPACE = 1 << 30
 
@@ -376,3 +381,129 @@ def truncated_robust_scales(self_levels, C=4.0, a=1.0):
         lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
     lam = torch.where(s <= C, torch.ones_like(s), 0.5 * (lo + hi)).to(dtype)
     return lam.cpu().numpy() if as_numpy else lam
+
+
+def _pair_slices(P, M, N, D, workspace_bytes):
+    """the pairs of a paired batch in runs whose fp64 staging stays within `workspace_bytes` (_chunked's rule)"""
+    budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
+    fd, Ncp = _lib._truncated_staging(D, N)
+    pairs = int(max(1, min(P, budget // (8 * fd * (M + Ncp)))))
+    return [slice(p, p + pairs) for p in range(0, P, pairs)]
+
+
+def _adjoint(be, X, Y, w, L, paired, workspace_bytes):
+    """d / dX of sum_pairs sum_m w[m - 1, pair] k_m(pair) by the kernel's adjoint mode, in X's dtype; paired batches in _chunked's runs"""
+    if not paired:
+        parts = [be.truncated_adjoint(X, Y, w, L, False, workspace_bytes)]
+    else:
+        parts = [be.truncated_adjoint(X[sl], Y[sl], w[:, sl], L, True, workspace_bytes)
+                 for sl in _pair_slices(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], workspace_bytes)]
+    if any(t is None for t in parts):
+        raise RuntimeError("the adjoint mode of k_trunc_sig declined a shape its route query accepted")
+    return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)).to(X.dtype)
+
+
+class _TruncatedLevels(torch.autograd.Function):
+    """The level terms of STEP tensors on a HIP device -- (L + 1, A, B), paired (L + 1, P) -- with the HIP kernel on both sides (a gradient: order 1):
+    forward = the levels mode (one launch), backward = the adjoint mode with w = grad_levels[1:], one launch per batch that needs a
+    gradient: dY is the adjoint on (Y, X) with w transposed, and a symmetric call (Y is X) is ONE launch with w + w^T, since
+    k_m(x, y) = k_m(y, x).  The caller has asked the route table for every side it needs (TruncatedSigKernel._hip_serves)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, L, order, paired, sym, workspace_bytes):
+        be = _lib.get_backend()
+        call = lambda x, y: be.truncated_levels(x, y, L, order, paired=paired)
+        lev = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
+        if lev is None:
+            raise RuntimeError("the levels mode of k_trunc_sig declined a shape its route query accepted")
+        ctx.save_for_backward(X, Y)
+        ctx.mode = (L, paired, sym, workspace_bytes)
+        return lev
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        X, Y = ctx.saved_tensors
+        L, paired, sym, workspace_bytes = ctx.mode
+        be = _lib.get_backend()
+        w = grad[1:].double()
+        dX = dY = None
+        if sym:
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+                dX = _adjoint(be, X, X, w + w.transpose(1, 2), L, False, workspace_bytes)
+        else:
+            if ctx.needs_input_grad[0]:
+                dX = _adjoint(be, X, Y, w.contiguous(), L, paired, workspace_bytes)
+            if ctx.needs_input_grad[1]:
+                dY = _adjoint(be, Y, X, (w if paired else w.transpose(1, 2)).contiguous(), L, paired, workspace_bytes)
+        return dX, dY, None, None, None, None, None
+
+
+class TruncatedSigKernel:
+    """The truncated signature kernel behind SigKernel's interface: ``X`` and ``Y`` are PATHS ``(batch, length, dim)`` -- differenced here
+    with torch ops, so a gradient reaches whatever produced them -- and the kernel is truncated_sig_kernel's on the steps, ``num_levels``
+    levels with weights ``sigma`` (a scalar or num_levels + 1 values; a tensor that requires grad is differentiated) at ``order``
+    (default 1; -1: num_levels).
+
+    Every call works on the level terms of ONE sweep and forms ``sum_m sigma[m] k_m`` from them (truncated_from_levels).  On a HIP device
+    the sweep is the HIP kernel's levels mode, and at order 1 WITH a gradient pending too: the backward is then the kernel's adjoint mode,
+    one launch per batch that requires grad (one in all for ``sym=True``), nothing of size pairs x M x N allocated -- where the forward
+    and every batch that needs a gradient are in the kernel's scope (path dim <= 8 and at most 128 steps on a side that needs a gradient:
+    sk_route_query(SK_OP_TRUNCATED_ADJOINT)) and a block's slab of (num_levels - 1) x (steps of the other side + lanes - 1) KB fits
+    ``workspace_bytes`` (default 1 GiB).  Everything else -- CPU tensors, other orders, wider or longer paths -- takes the torch
+    restatement as a whole, tiled by ``workspace_bytes``: the values do not depend on the route beyond rounding."""
+
+    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None):
+        self.num_levels, self.sigma, self.order, self.workspace_bytes = num_levels, sigma, order, workspace_bytes
+
+    def _hip_serves(self, dx, dy, L, order, paired, sym):
+        """the HIP function serves the call: a HIP device, no empty axis, the forward in scope on (dx, dy) or (dy, dx), and on every side
+        that needs a gradient order 1 and the adjoint in scope, its slab within the workspace"""
+        if not dx.is_cuda or min(dx.shape[0], dx.shape[1], dy.shape[0], dy.shape[1]) == 0:
+            return False
+        be = _lib.get_backend()
+        if not (hasattr(be, "truncated_levels") and hasattr(be, "truncated_adjoint_fits")):
+            return False
+        (A, M, D), (B, N), es = dx.shape, dy.shape[:2], dx.element_size()
+        if be.route(_lib.OP_TRUNCATED, order, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
+            return False
+        grad = torch.is_grad_enabled()
+        if grad and order != 1 and (dx.requires_grad or dy.requires_grad):
+            return False
+        if grad and dx.requires_grad and not be.truncated_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
+            return False
+        if grad and dy.requires_grad and not sym and not be.truncated_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
+            return False
+        return True
+
+    def _levels(self, X, Y, paired, sym):
+        L, order = _check_args(X, Y, self.num_levels, self.order)
+        if paired and X.shape[0] != Y.shape[0]:
+            raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
+        if sym and Y is not X:
+            raise ValueError("sym=True needs Y is X")
+        dx = X[:, 1:] - X[:, :-1]
+        dy = dx if Y is X else Y[:, 1:] - Y[:, :-1]
+        if self._hip_serves(dx, dy, L, order, paired, sym):
+            dx = dx.contiguous()
+            return _TruncatedLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, order, paired, sym, self.workspace_bytes)
+        return _truncated_levels_torch(dx, dy, L, order, paired, self.workspace_bytes)
+
+    def compute_Gram(self, X, Y, sym=False):
+        """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim) -> (batch_X, batch_Y): the truncated kernel of every pair of paths.
+        ``sym=True`` needs ``Y is X``; with a gradient it costs one adjoint launch instead of two."""
+        return truncated_from_levels(self._levels(X, Y, False, bool(sym)), self.sigma)
+
+    def compute_kernel(self, X, Y):
+        """X (batch, len_x, dim), Y (batch, len_y, dim) -> (batch,): the truncated kernel of the pairs (X[i], Y[i])."""
+        return truncated_from_levels(self._levels(X, Y, True, False), self.sigma)
+
+    def compute_mmd(self, X, Y):
+        """The unbiased MMD^2 of the samples X and Y, SigKernel.compute_mmd's estimator: the means of K_XX and K_YY without their
+        diagonals, minus twice the mean of K_XY.  A batch that does not require grad costs no adjoint launch."""
+        K_XX = self.compute_Gram(X, X, sym=True)
+        K_YY = self.compute_Gram(Y, Y, sym=True)
+        K_XY = self.compute_Gram(X, Y)
+        K_XX_m = (torch.sum(K_XX) - torch.sum(torch.diag(K_XX))) / (K_XX.shape[0] * (K_XX.shape[0] - 1.))
+        K_YY_m = (torch.sum(K_YY) - torch.sum(torch.diag(K_YY))) / (K_YY.shape[0] * (K_YY.shape[0] - 1.))
+        return K_XX_m + K_YY_m - 2. * torch.mean(K_XY)
