@@ -5,7 +5,7 @@ kernel='precomputed', hyper-parameters by cross-validated grid search), on synth
 sets the reference downloads through tslearn are not available offline.
 
     python examples/time_series_classification.py [--n-train 120] [--n-test 80] [--length 60] [--ragged]
-    python examples/time_series_classification.py --truncated [--normalize | --robust]
+    python examples/time_series_classification.py --truncated [--normalize | --robust] [--static rbf [--rbf-sigma S]]
 
 --ragged: the variable-length variant -- every series is cut at a random length in [length / 2, length], the batch is padded by
 pad_paths and the Gram matrices come from compute_Gram_ragged.
@@ -14,6 +14,9 @@ pad_paths and the Gram matrices come from compute_Gram_ragged.
 kernel; --normalize divides it by sqrt(k(x, x) k(y, y)) (normalize=True: the A + B self-kernels come from one paired launch each).
 --robust: Chevyrev and Oberhauser's robust normalisation instead -- truncated_sig_kernel_levels (the level terms of one sweep) ->
 truncated_robust_scales (a scale per path from its paired self levels) -> truncated_from_levels (the kernel of the rescaled paths).
+--static rbf: the truncated kernel lifted through an RBF static kernel on the series' POINTS, as Kiraly and Oberhauser state it --
+TruncatedSigKernel(4, static_kernel=RBFKernel(S)).compute_Gram on the transformed series themselves, one HIP sweep per matrix;
+--normalize divides by the self-kernels from compute_kernel.  (The robust normalisation rescales steps and has no lifted form.)
 
 Class 0: Brownian paths with a slow sinusoidal drift; class 1: the same noise with the drift's frequency doubled.
 Runs on an MI355X (the Gram matrices come from the HIP kernels; there is no CPU fallback).
@@ -87,14 +90,29 @@ def robust_gram(X, Y, num_levels):
     return sigkernel.truncated_from_levels(sigkernel.truncated_sig_kernel_levels(X, Y, num_levels), 1., lam_x, lam_y)
 
 
-def truncated_svc(x_train, y_train, x_test, device, normalize, num_levels=4, cv=5, robust=False):
-    """The same pipeline with truncated_sig_kernel on the STEPS of the time-augmented series: (cv score, C, test predictions)."""
+def lifted_gram(tk, X, Y, normalize):
+    """The Gram matrix of a TruncatedSigKernel with a static kernel on two batches of PATHS, divided by sqrt(k(x, x) k(y, y)) on request."""
+    K = tk.compute_Gram(X, Y)
+    if normalize:
+        kx = tk.compute_kernel(X, X)
+        ky = kx if Y is X else tk.compute_kernel(Y, Y)
+        K = K / torch.sqrt(kx[:, None] * ky[None, :])
+    return K
+
+
+def truncated_svc(x_train, y_train, x_test, device, normalize, num_levels=4, cv=5, robust=False, static=None, rbf_sigma=1.0):
+    """The same pipeline with truncated_sig_kernel on the STEPS of the time-augmented series -- static="rbf": with the RBF-lifted
+    TruncatedSigKernel on their POINTS: (cv score, C, test predictions)."""
     from sklearn.model_selection import GridSearchCV
     from sklearn.svm import SVC
     top = np.abs(x_train).max()
-    steps = [torch.diff(sigkernel.transform(torch.tensor(x / top, dtype=torch.float64, device=device), at=True, ll=False, scale=1.0), dim=1)
-             for x in (x_train, x_test)]
-    if robust:
+    paths = [sigkernel.transform(torch.tensor(x / top, dtype=torch.float64, device=device), at=True, ll=False, scale=1.0) for x in (x_train, x_test)]
+    steps = [torch.diff(x, dim=1) for x in paths]
+    if static == "rbf":
+        tk = sigkernel.TruncatedSigKernel(num_levels, static_kernel=sigkernel.RBFKernel(rbf_sigma))
+        G_train = lifted_gram(tk, paths[0], paths[0], normalize).cpu().numpy()
+        G_test = lifted_gram(tk, paths[1], paths[0], normalize).cpu().numpy()
+    elif robust:
         G_train, G_test = robust_gram(steps[0], steps[0], num_levels).cpu().numpy(), robust_gram(steps[1], steps[0], num_levels).cpu().numpy()
     else:
         G_train = sigkernel.truncated_sig_kernel(steps[0], steps[0], num_levels, normalize=normalize).cpu().numpy()
@@ -127,7 +145,11 @@ def main():
     ap.add_argument("--truncated", action="store_true", help="truncated_sig_kernel of the series' steps instead of the PDE kernel")
     ap.add_argument("--normalize", action="store_true", help="with --truncated: k(x, y) / sqrt(k(x, x) k(y, y))")
     ap.add_argument("--robust", action="store_true", help="with --truncated: the robust normalisation, from the level terms of one sweep")
+    ap.add_argument("--static", choices=["rbf"], default=None, help="with --truncated: lift the kernel through this static kernel on the points")
+    ap.add_argument("--rbf-sigma", type=float, default=1.0, help="with --static rbf: the RBF kernel's sigma")
     args = ap.parse_args()
+    if args.static and (not args.truncated or args.robust):
+        raise SystemExit("--static goes with --truncated, plain or with --normalize")
     if (args.normalize or args.robust) and not args.truncated or args.truncated and args.ragged or args.normalize and args.robust:
         raise SystemExit("--normalize or --robust (one of them) goes with --truncated, and --truncated takes series of one length")
     if not torch.cuda.is_available():
@@ -136,9 +158,11 @@ def main():
     x_train, y_train = make_dataset(args.n_train, args.length, seed=0)
     x_test, y_test = make_dataset(args.n_test, args.length, seed=1)
     if args.truncated:
-        score, C, pred = truncated_svc(x_train, y_train, x_test, device, args.normalize, robust=args.robust)
+        score, C, pred = truncated_svc(x_train, y_train, x_test, device, args.normalize, robust=args.robust, static=args.static,
+                                       rbf_sigma=args.rbf_sigma)
         acc = float(np.mean(pred == y_test))
         how = " (normalised)" if args.normalize else " (robustly normalised)" if args.robust else ""
+        how = (", RBF(%g) lift" % args.rbf_sigma if args.static else "") + how
         print("truncated signature kernel%s + SVC: cv accuracy %.3f (C %g), test accuracy %.3f" % (how, score, C, acc))
         return acc
     if args.ragged:

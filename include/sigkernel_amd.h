@@ -63,7 +63,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -120,6 +120,11 @@ const char *sk_cost_note(int which);
                                  SK_OP_TRUNCATED): SK_ROUTE_FUSED = sk_truncated_adjoint: inside SK_OP_TRUNCATED's FUSED scope, order 1 (kind 1, or
                                  num_levels 1), path dim <= 8, M <= 128; SK_ROUTE_STREAM otherwise = autograd of the host layer's torch
                                  restatement.  Never swapped: the second batch's gradient is the same query on (N, M). */
+#define SK_OP_TRUNCATED_RBF 6  /* the truncated kernel lifted through an RBF static kernel (TruncatedSigKernel(static_kernel=RBFKernel(s)); no
+                                 counterpart in the reference): kind, dyadic as SK_OP_TRUNCATED, M / N = POINTS per path of the two batches, the
+                                 rows and columns of the sweep.  SK_ROUTE_FUSED = sk_truncated_points_* with kind 1: SK_OP_TRUNCATED's rule on
+                                 the points at order 1 (kind 1, or num_levels 1: M <= 128; 8 or 16 x ceil16(N) <= 2048) and M, N >= 2;
+                                 SK_ROUTE_FUSED_SWAP = the same on (y, x), transposed; SK_ROUTE_STREAM = the host layer's torch restatement. */
 #define SK_ROUTE_STREAM 0
 #define SK_ROUTE_FUSED 1
 #define SK_ROUTE_FUSED_MB 2
@@ -518,6 +523,22 @@ int sk_truncated_levels_paired_f64(const double *Xr, const double *Yt, int64_t P
                                    int num_levels, int order, double *out, void *stream);
 int sk_truncated_levels_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
                                    int num_levels, int order, float *out, void *stream);
+/* The same sweep with the static kernel as a launch-time mode, every output mode behind ONE entry point (no counterpart in the reference,
+ * whose truncated kernel knows inner products of steps only).  kind 0: Xr / Yt hold steps and the call is sk_truncated_gram_* (paired = 0,
+ * levels = 0), _paired_* (paired = 1: A pairs, B ignored), _levels_* or _levels_paired_* (levels = 1: sigma is not read and may be NULL).
+ * kind 1: Xr / Yt hold the M / N POINTS of the paths (at least 2 each) and the sweep runs on the M x N grid of points with
+ * G[i][j] = kap(x_i, y_j) - kap(x_i, y_{j-1}) - kap(x_{i-1}, y_j) + kap(x_{i-1}, y_{j-1}), kap(x, y) = exp(-|x - y|^2 param), param = 1 / sigma
+ * of RBFKernel > 0, zero in row 0 and column 0: the kernel of Kiraly and Oberhauser lifted through the RBF kernel.  kap is evaluated in
+ * the sweep from differences of coordinates (two polynomials per node and row: exp of the node, expm1 of the exponents' difference along
+ * the row); nothing of size pairs x M x N exists.
+ *   Staging, sigma, order, out and the _f32 rule as the kind-0 entry points'.  Forward only.
+ * Scope: kind 0 as sk_truncated_gram_*; kind 1: sk_route_query(SK_OP_TRUNCATED_RBF, order, D, M, N, num_levels, ...) == SK_ROUTE_FUSED. */
+int sk_truncated_points_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                            int num_levels, int order, int kind, double param, int paired, int levels, const double *sigma, double *out,
+                            void *stream);
+int sk_truncated_points_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                            int num_levels, int order, int kind, double param, int paired, int levels, const double *sigma, float *out,
+                            void *stream);
 /* The GRADIENT of the level terms with respect to the first batch, by the same kernel in its adjoint mode (no counterpart in the reference,
  * whose truncated kernel is numpy): for weights w [num_levels][A][B] (device fp64; paired: [num_levels][P]) -- the upstream gradient of level
  * m + 1 of every pair -- the chunks' parts of d / dX sum_pairs sum_m w[m][pair] k_{m+1}(pair) go to Tpart [n_chunks][A][M][8]; the caller

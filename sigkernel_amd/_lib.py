@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libsigkernel_amd.so")
 
 SK_OK = 0
 # sk_route_query: operations and answers (include/sigkernel_amd.h)
-OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED, OP_TRUNCATED_ADJOINT = 0, 1, 2, 3, 4, 5
+OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED, OP_TRUNCATED_ADJOINT, OP_TRUNCATED_RBF = 0, 1, 2, 3, 4, 5, 6
 ROUTE_STREAM, ROUTE_FUSED, ROUTE_FUSED_MB, ROUTE_FUSED_MB_SWAP, ROUTE_FUSED_SWAP = 0, 1, 2, 3, 4
 ROUTE_NO_STREAM = 1
 ROUTE_NO_SWAP = 2
@@ -95,6 +95,8 @@ SIGNATURES = {
     "sk_truncated_levels_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
     "sk_truncated_levels_paired_f64": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
     "sk_truncated_levels_paired_f32": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
+    "sk_truncated_points_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _int, _vp, _vp, _vp]),
+    "sk_truncated_points_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _int, _vp, _vp, _vp]),
     "sk_truncated_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
     "sk_truncated_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
     "sk_prep_pair_f64": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
@@ -658,41 +660,50 @@ class HipBackend:
         _check(rc, "sk_solve_prefix_at")
         return out
 
-    def _truncated(self, X, Y, num_levels, order, paired, sigma):
-        """The one call of k_trunc_sig (sk_truncated_{gram,paired,levels,levels_paired}_*, csrc/sk_truncated.hip): X (A, M, D) / Y (B, N, D) hold
-        steps; sigma: num_levels + 1 host weights -> (A, B), paired (P,); None -> the level terms under a leading axis of num_levels + 1, plane 0
-        ones.  None outside the kernel's scope (sk_route_query(SK_OP_TRUNCATED) != FUSED): FUSED_SWAP is the caller's call on (Y, X) -- a Gram
-        result transposed, a paired one as it is -- and STREAM its torch restatement (truncated.py)."""
+    def _truncated(self, X, Y, num_levels, order, paired, sigma, kind=0, param=0.0):
+        """The one call of k_trunc_sig (sk_truncated_{gram,paired,levels,levels_paired,points}_*, csrc/sk_truncated.hip): X (A, M, D) / Y (B, N, D)
+        hold steps; sigma: num_levels + 1 host weights -> (A, B), paired (P,); None -> the level terms under a leading axis of num_levels + 1,
+        plane 0 ones.  kind 1: X and Y hold POINTS and the sweep is the RBF lift with param = RBFKernel's sigma (the kernel's points mode,
+        scope SK_OP_TRUNCATED_RBF).  None outside the kernel's scope (sk_route_query != FUSED): FUSED_SWAP is the caller's call on (Y, X) -- a
+        Gram result transposed, a paired one as it is -- and STREAM its torch restatement (truncated.py)."""
         _dev(X, "X")
         _dev(Y, "Y")
         (A, M, D), (B, N), L = X.shape, Y.shape[:2], int(num_levels)
-        if self.route(OP_TRUNCATED, order, D, M, N, L, False, X.element_size()) != ROUTE_FUSED:
+        if kind and not float(param) > 0:
+            return None
+        if self.route(OP_TRUNCATED_RBF if kind else OP_TRUNCATED, order, D, M, N, L, False, X.element_size()) != ROUTE_FUSED:
             return None
         batches = (A,) if paired else (A, B)
         out = torch.empty(batches if sigma is not None else (L + 1,) + batches, dtype=X.dtype, device=X.device)
         if A == 0 or B == 0:
             return out
         fd, Ncp = _truncated_staging(D, N)
-        name = "sk_truncated_" + (("paired" if paired else "gram") if sigma is not None else ("levels_paired" if paired else "levels"))
         weights = () if sigma is None else ((ctypes.c_double * (L + 1))(*[float(v) for v in sigma]),)
+        if kind:
+            name = "sk_truncated_points"
+            modes = (int(kind), 1.0 / float(param), int(bool(paired)), int(sigma is None)) + (weights or (None,))
+            batches = (A, B)
+        else:
+            name = "sk_truncated_" + (("paired" if paired else "gram") if sigma is not None else ("levels_paired" if paired else "levels"))
+            modes = weights
         with _device(X.device):
             Xr, Yt = _prep_pair(X, Y, False, 1.0, M, Ncp, fd)
-            rc = getattr(load(), name + "_" + _suffix(X))(_ptr(Xr), _ptr(Yt), *batches, M, M, N, Ncp, D, fd, L, int(order), *weights,
+            rc = getattr(load(), name + "_" + _suffix(X))(_ptr(Xr), _ptr(Yt), *batches, M, M, N, Ncp, D, fd, L, int(order), *modes,
                                                           _ptr(out), _stream(X))
         _check(rc, name)
         return out
 
-    def truncated_gram(self, X, Y, num_levels, sigma, order):
+    def truncated_gram(self, X, Y, num_levels, sigma, order, kind=0, param=0.0):
         """The truncated signature kernel's (A, B) matrix in one sweep per pair, or None: _truncated with sigma's num_levels + 1 host values."""
-        return self._truncated(X, Y, num_levels, order, False, sigma)
+        return self._truncated(X, Y, num_levels, order, False, sigma, kind, param)
 
-    def truncated_paired(self, X, Y, num_levels, sigma, order):
+    def truncated_paired(self, X, Y, num_levels, sigma, order, kind=0, param=0.0):
         """... of the P pairs (X[p], Y[p]), (P,), by the same kernel in its paired mode: one pair per lane group, nothing of size P x P."""
-        return self._truncated(X, Y, num_levels, order, True, sigma)
+        return self._truncated(X, Y, num_levels, order, True, sigma, kind, param)
 
-    def truncated_levels(self, X, Y, num_levels, order, paired=False):
+    def truncated_levels(self, X, Y, num_levels, order, paired=False, kind=0, param=0.0):
         """The level terms k_0 .. k_L from ONE sweep per pair (the kernel's levels mode): (num_levels + 1, A, B), paired (num_levels + 1, P)."""
-        return self._truncated(X, Y, num_levels, order, bool(paired), None)
+        return self._truncated(X, Y, num_levels, order, bool(paired), None, kind, param)
 
     def truncated_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
         """whether truncated_adjoint serves the shape: SK_OP_TRUNCATED_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""

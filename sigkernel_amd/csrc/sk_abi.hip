@@ -169,16 +169,19 @@ int solve_prefix_at(int kind, const double *Xr, const double *Yt, int64_t A, int
 }
 
 // the truncated signature kernel (sk_truncated.hip), every mode of its one launch; argument checks before any HIP call.  paired != 0: the
-// A pairs (x_p, y_p), B ignored; levels != 0: the level terms of every pair, sigma not read -- and only then may it be null
+// A pairs (x_p, y_p), B ignored; levels != 0: the level terms of every pair, sigma not read -- and only then may it be null; kind 1: the
+// RBF lift on POINTS with param = 1 / sigma
 template <typename TO>
 int truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
-              int order, const double *sigma, TO *out, void *stream, int paired, int levels) {
+              int order, const double *sigma, TO *out, void *stream, int paired, int levels, int kind = 0, double param = 0.0) {
     if (paired) B = A;
+    if ((kind != 0 && kind != 1) || (kind == 1 && (!(param > 0.0) || !(param < 1e300)))) return SK_ERR_BAD_ARG;
     if (D < 1 || !Xr || !Yt || !out || (!sigma && !levels) || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N ||
         fd < D)
         return SK_ERR_BAD_ARG;
     if (A == 0 || B == 0) return SK_OK;
-    return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream, paired, levels);
+    return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream, paired, levels, kind,
+                                param);
 }
 
 }  // namespace
@@ -250,7 +253,8 @@ int device_cu_count() {
 
 extern "C" {
 
-// (340 still: sk_truncated_levels_{,paired_}{f64,f32}, sk_truncated_adjoint and its plan are additions, no exported signature changed)
+// (340 still: sk_truncated_levels_{,paired_}{f64,f32}, sk_truncated_adjoint and its plan, sk_truncated_points_{f64,f32} and SK_OP_TRUNCATED_RBF
+// are additions, no exported signature changed)
 // 340: sk_static_increments_* serve any path dim (D > 32: k_static_wide_mfma); sk_static_adjoint_* kind 1 with D > 32 writes the first
 // pass H [P][M][ldh] of the rbf chain rule instead of dL/dX
 // 330 (round 6): sk_linear_adjoint_fused_f64 takes ypart / ypart_doubles / ycols_out (the second-argument sums, route FUSED_SWAP)
@@ -501,6 +505,14 @@ int sk_truncated_levels_paired_f64(const double *Xr, const double *Yt, int64_t P
 int sk_truncated_levels_paired_f32(const double *Xr, const double *Yt, int64_t P, int Mrows, int M, int N, int Ncp, int D, int fd,
                                    int num_levels, int order, float *out, void *stream) {
     return truncated<float>(Xr, Yt, P, P, Mrows, M, N, Ncp, D, fd, num_levels, order, nullptr, out, stream, 1, 1);
+}
+int sk_truncated_points_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                            int num_levels, int order, int kind, double param, int paired, int levels, const double *sigma, double *out, void *stream) {
+    return truncated<double>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, paired, levels, kind, param);
+}
+int sk_truncated_points_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                            int num_levels, int order, int kind, double param, int paired, int levels, const double *sigma, float *out, void *stream) {
+    return truncated<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, paired, levels, kind, param);
 }
 int sk_truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes, int64_t *plan) {
     if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;

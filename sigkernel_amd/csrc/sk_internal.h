@@ -190,11 +190,13 @@ bool prefix_in_scope(int kind, int D, int Mc, int dyadic);   // the kernel's sco
 // Xr [A][Mrows][fd] / Yt [B][fd][Ncp]: the path POINTS as sk_prep_pair_* stages them (fd = 8 up to dim 8, else 16); sigma: L + 1 host
 // values; out [A][B].  paired != 0 (a launch-time mode of the same instances): A = B pairs (x_p, y_p), out [A].  levels != 0 (another):
 // the level terms k_0 .. k_L of every pair instead of their weighted sum, out [L + 1][A][B] / [L + 1][A]; sigma is not read.
-// SK_ERR_UNSUPPORTED outside truncated_in_scope, in every mode.
+// kind 1 (a third): the same sweep on the Mp x Np grid of POINTS, G = the second difference of exp(-|x - y|^2 param) -- M and N then
+// count points.  SK_ERR_UNSUPPORTED outside truncated_in_scope (kind 1: truncated_points_in_scope), in every mode.
 template <typename TO>
 int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
-                     int order, const double *sigma, TO *out, hipStream_t s, int paired = 0, int levels = 0);
+                     int order, const double *sigma, TO *out, hipStream_t s, int paired = 0, int levels = 0, int kind = 0, double param = 0.0);
 bool truncated_in_scope(int D, int M, int N, int L, int order);   // the kernel's scope = the SK_OP_TRUNCATED rule of sk_route_query
+bool truncated_points_in_scope(int D, int M, int N, int L, int order);   // ... of its points mode = the SK_OP_TRUNCATED_RBF rule
 // The ADJOINT mode of k_trunc_sig<1, 2> (order 1, dim <= 8): Tpart [n_chunks][A][M][8] takes the chunks' parts of the gradient of
 // sum_pairs sum_m w[m - 1][pair] k_m(pair) with respect to the rows of x; w [L][A][B] (paired [L][A]) on the device.  slab: slab_bytes of
 // device memory for the prefix factors a block keeps between its two phases (none at L = 1).  The plan gives the chunk count, the
@@ -375,6 +377,23 @@ __device__ __forceinline__ double exp_nonpos(double x) {
     p = fma(p, r, 1.0);
     p = fma(p, r, 1.0);
     return __builtin_ldexp(p, (int)n);
+}
+// exp(x) - 1 for x <= 0 without the cancellation of exp_nonpos(x) - 1 near 0 (first differences of RBF values along a path, as a value
+// times expm1 of the exponents' difference): with exp(x) = 2^n p(r), p - 1 = r + r^2 / 2 + r^3 q(r) is formed without its 1, and exp(x) - 1 = 2^n (p - 1) + (2^n - 1) is
+// one FMA on two exact constants -- the same polynomial and FMA count; near 0 the error is 2^-53 RELATIVE to |exp(x) - 1|, where
+// exp_nonpos(x) - 1 leaves 2^-53 absolute.
+__device__ __forceinline__ double expm1_nonpos(double x) {
+    x = exp_clamp(x);
+    const double n = __builtin_rint(x * 1.4426950408889634074);
+    double r = fma(n, -6.93147180369123816490e-01, x);
+    r = fma(n, -1.90821492927058770002e-10, r);
+    double p = ExpPoly<11>::k[0];
+#pragma unroll
+    for (int i = 1; i < ExpPoly<11>::N; ++i) p = fma(p, r, ExpPoly<11>::k[i]);
+    p = fma(p, r, 0.5);
+    p = fma(p, r, 1.0);
+    const double s = __builtin_ldexp(1.0, (int)n);
+    return fma(s, p * r, s - 1.0);
 }
 
 }  // namespace sk

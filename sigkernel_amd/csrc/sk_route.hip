@@ -161,6 +161,15 @@ int route_query(int op, int kind, int D, int M, int N, int d, int naive, int ele
         if (!(flags & SK_ROUTE_NO_SWAP) && truncated_in_scope(D, N, M, d, kind)) return SK_ROUTE_FUSED_SWAP;
         return SK_ROUTE_STREAM;
     }
+    if (op == SK_OP_TRUNCATED_RBF) {
+        // TruncatedSigKernel with an RBF static kernel: kind, d as above, M / N = POINTS of the two batches.  FUSED = k_trunc_sig in its points
+        // mode (truncated_points_in_scope is the rule), FUSED_SWAP = the same on (y, x), transposed (kappa is symmetric); STREAM = the torch
+        // restatement on second differences of the static Gram.
+        if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
+        if (truncated_points_in_scope(D, M, N, d, kind)) return SK_ROUTE_FUSED;
+        if (!(flags & SK_ROUTE_NO_SWAP) && truncated_points_in_scope(D, N, M, d, kind)) return SK_ROUTE_FUSED_SWAP;
+        return SK_ROUTE_STREAM;
+    }
     if (op == SK_OP_TRUNCATED_ADJOINT) {
         // the gradient of the truncated kernel's level terms with respect to the FIRST batch (kind, d, M, N as above): FUSED = the adjoint
         // mode of k_trunc_sig<1, 2> (truncated_adjoint_in_scope is the rule), STREAM = autograd of the torch restatement.  Never swapped: the

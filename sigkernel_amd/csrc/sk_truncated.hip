@@ -33,6 +33,10 @@
 // ADJOINT mode (TruncParams::adjoint, launch-time and wave-uniform, the <1, 2> instance only: order 1, fd = 8): the gradient of a weighted
 // sum of the pairs' level terms with respect to the rows of x, in Gram and paired mode -- trunc_adjoint below, with loops of its own; the
 // forward launches run the step loop they ran.
+// POINTS mode (TruncParams::adjoint = 2, launch-time and wave-uniform; order 1; Gram, paired and levels): the kernel of Kiraly and Oberhauser
+// lifted through the RBF static kernel -- x and y staged as POINTS, G the second difference of exp(-|x - y|^2 param) on the grid of points,
+// evaluated in the sweep: trunc_points below, with a loop of its own, compiled into the <TR_OMAX, 1> instance; the forward launches run
+// the step loop they ran.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
 // order (1: one plane per level, or TR_OMAX) and the rows per lane.
 #include "sk_wave_common.h"
@@ -54,11 +58,13 @@ struct TruncParams {
     int levels;         // 0: one weighted value per pair; 1: the pair's L + 1 level terms, one plane of `out` per level
     double sigma[TR_LMAX + 1];
     // ADJOINT mode (order 1, fd = 8: trunc_adjoint below).  `out` is not used.
-    int adjoint;        // 0: a forward launch; 1: dX of sum_pairs sum_m w[m][pair] k_m
+    int adjoint;        // 0: a forward launch; 1: dX of sum_pairs sum_m w[m][pair] k_m; 2: the POINTS mode, a forward launch on points (below)
     int64_t n_chunks;   // Gram: the B pairs of a row tile go to this many positions; paired: 1
     const double *w;    // [L][A][B], paired [L][A]: the weight of level m + 1 of every pair
     double *Tpart;      // [n_chunks][A][M][8]: the chunks' parts of dX, summed by the caller
     double *slab;       // [blocks][L - 1][N + W - 1][128]: a block's prefix factors between its two phases
+    // POINTS mode (order 1: trunc_points below); behind everything else, so that no field the other modes read moves
+    double param;       // adjoint == 2: one over the RBF kernel's sigma
 };
 
 // ADJOINT mode of k_trunc_sig<1, 2> (TruncParams::adjoint, launch-time and wave-uniform): the gradient with respect to the rows of x of
@@ -232,6 +238,166 @@ __device__ __forceinline__ void trunc_adjoint(const TruncParams &prm, double *yl
     }
 }
 
+// POINTS mode (TruncParams::adjoint = 2, launch-time and wave-uniform; order 1, two rows per lane, fd = 8 or 16; Gram, paired and levels):
+// the forward sweep on the M x N grid of POINTS with G the second difference of kap(x, y) = exp(-|x - y|^2 param).  The pair order, the
+// staging, the skew, the hand-downs and both epilogues are the order-1 forward launches'; the loop is this mode's own, and it is compiled
+// into k_trunc_sig<TR_OMAX, 1>, not into <1, 2> whose rows-per-lane it shares: the function does not depend on the template arguments, and
+// <1, 2> sits at the limit of its scalar registers, where any code beside its step loop moved the plain, paired and levels launches by
+// 1 - 4 % (inside the step loop: 12 - 15 %; profiles/truncated_static.txt).  So <1, 2> is the code it was, instruction for instruction, and
+// <TR_OMAX, 1>, whose own loops need more registers than this one, carries the mode at 242 VGPRs (241 without).  What differs is how g forms:
+//   X(i, c) = -|x_i - y_c|^2 param from differences of coordinates (a common offset of the paths costs no digits), kap = exp_nonpos(X);
+//   D(i, c) = kap(i, c) - kap(i, c - 1) is NOT formed by subtracting -- at a wide bandwidth every kap is 1 - small and the difference would
+//             keep 1e-16 absolute -- but as kap_low expm1(-|X(i, c) - X(i, c - 1)|), kap_low the one of the two with the smaller exponent
+//             left over: the error of D is then 2^-53 |X| / |dX| relative to D (dX is itself a subtraction) -- what subtracting leaves
+//             for |X| = O(1), far less where |X| << 1, the wide bandwidth, and nothing is lost where kap << 1;
+//   g(i, c) = D(i, c) - D(i - 1, c), zero in row 0, in column 0, in padding rows and off the columns.  A zero row and a zero column in
+//             front add nothing to any exclusive prefix, so the recursion below is the one of the steps.
+// A lane carries kap and X of column c - 1 for each of its two rows and D of its second row: five doubles.  The row above a lane's first
+// row is the lane above, one column ahead: its carried D, read by DPP at the top of the step before it is overwritten, is D(i - 1, c).
+__device__ __forceinline__ void trunc_points(const TruncParams &prm, double *ylds) {
+    constexpr int NS = TR_LMAX - 1;
+    const int lane = threadIdx.x;
+    const int W = 1 << prm.logW, G = WAVE >> prm.logW;
+    const int lam = lane & (W - 1), grp = lane >> prm.logW;
+    const int N = prm.N, Ncp = prm.Ncp, L = prm.L, fd = prm.fd;
+    const bool wide = fd > 8;
+    const int steps = N + W - 1;
+    const bool paired = prm.paired != 0;
+    const double nparam = -prm.param;
+    for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
+        int64_t a, b;
+        int nblk = 1;
+        if (paired) {
+            b = pos * G;
+            a = b + grp;
+            nblk = prm.A - b < G ? (int)(prm.A - b) : G;
+        } else {
+            const int64_t at = pos / prm.B;
+            b = pos - at * prm.B;
+            a = at * G + grp;
+        }
+        const bool live = a < prm.A;
+        const double *yl = ylds + ((paired && live) ? grp * fd * Ncp : 0);
+        __syncthreads();
+        {
+            const double *yb = prm.Yt + b * (int64_t)fd * Ncp;
+            for (int k = lane; k < nblk * fd * Ncp; k += WAVE) ylds[k] = yb[k];
+        }
+        double xr[2][16];
+        bool node[2];       // the row has nodes: not the first point, not padding
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int row = lam * 2 + r;
+            const bool ok = live && row < prm.M;
+            const double *xp = prm.Xr + ((ok ? a : 0) * (int64_t)prm.Mrows + (ok ? row : 0)) * fd;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) xr[r][k] = (ok && k < fd) ? xp[k] : 0.0;
+            node[r] = ok && row > 0;
+        }
+        __syncthreads();
+        double rowS[2][NS], qio[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) qio[s] = rowS[0][s] = rowS[1][s] = 0.0;
+        double acc = 0.0, kc[2] = {0.0, 0.0}, xc[2] = {0.0, 0.0}, dc = 0.0;
+        for (int t = 0; t < steps; ++t) {
+            const int j = t - lam;
+            const bool act = (unsigned)j < (unsigned)N;
+            const int jc = act ? j : 0;
+            double dup = dpp_shr1_zero(dc);     // D(i - 1, c) of the lane's first row (row 0 of a group: masked below)
+            double qin[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const double v = s < L - 1 ? dpp_shr1_zero(qio[s]) : 0.0;
+                qin[s] = lam == 0 ? 0.0 : v;
+            }
+            double yv[16];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) yv[k] = yl[k * Ncp + jc];
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+            if (wide) {
+#pragma unroll
+                for (int k = 8; k < 16; ++k) yv[k] = yl[k * Ncp + jc];
+                asm volatile("s_waitcnt lgkmcnt(0)"
+                             : "+v"(yv[8]), "+v"(yv[9]), "+v"(yv[10]), "+v"(yv[11]), "+v"(yv[12]), "+v"(yv[13]), "+v"(yv[14]), "+v"(yv[15]));
+            } else {
+#pragma unroll
+                for (int k = 8; k < 16; ++k) yv[k] = 0.0;
+            }
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                double d2 = 0.0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const double e = xr[r][k] - yv[k];
+                    d2 = fma(e, e, d2);
+                }
+                if (wide) {
+#pragma unroll
+                    for (int k = 8; k < 16; ++k) {
+                        const double e = xr[r][k] - yv[k];
+                        d2 = fma(e, e, d2);
+                    }
+                }
+                const double xn = d2 * nparam, kn = exp_nonpos(xn);
+                const double dx = xn - xc[r];
+                const double d = (dx <= 0.0 ? kc[r] : -kn) * expm1_nonpos(-__builtin_fabs(dx));
+                double g = d - dup;
+                g = (act && j > 0 && node[r]) ? g : 0.0;
+                kc[r] = kn;
+                xc[r] = xn;
+                dup = d;        // the next row's row above is this one
+                double prev = g;
+#pragma unroll
+                for (int lv = 1; lv <= TR_LMAX; ++lv)
+                    if (lv <= L) {
+                        acc = fma(prm.sigma[lv], prev, acc);
+                        if (lv < TR_LMAX && lv < L) {
+                            const int s = lv - 1;
+                            const double next = g * qin[s];
+                            qin[s] = qin[s] + rowS[r][s];
+                            rowS[r][s] += prev;
+                            prev = next;
+                        }
+                    }
+            }
+            dc = dup;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) qio[s] = qin[s];
+        }
+        for (int off = 1; off < W; off <<= 1) acc += __shfl_xor(acc, off, WAVE);
+        if (prm.levels) {       // the weights are (0, .., 0, 1): acc is level L, rowS[.][s] the total of level s + 1
+            const int64_t plane = paired ? prm.A : prm.A * prm.B;
+            const int64_t o = paired ? a : a * prm.B + b;
+            const bool st = lam == 0 && live;
+            if (st) {
+                if (prm.out_f32) {
+                    reinterpret_cast<float *>(prm.out)[o] = 1.0f;
+                    reinterpret_cast<float *>(prm.out)[L * plane + o] = (float)acc;
+                } else {
+                    reinterpret_cast<double *>(prm.out)[o] = 1.0;
+                    reinterpret_cast<double *>(prm.out)[L * plane + o] = acc;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (s < L - 1) {
+                    double v = rowS[0][s] + rowS[1][s];
+                    for (int off = 1; off < W; off <<= 1) v += __shfl_xor(v, off, WAVE);
+                    if (st) {
+                        if (prm.out_f32) reinterpret_cast<float *>(prm.out)[(s + 1) * plane + o] = (float)v;
+                        else reinterpret_cast<double *>(prm.out)[(s + 1) * plane + o] = v;
+                    }
+                }
+        } else if (lam == 0 && live) {
+            const double v = prm.sigma[0] + acc;
+            const int64_t o = paired ? a : a * prm.B + b;
+            if (prm.out_f32) reinterpret_cast<float *>(prm.out)[o] = (float)v;
+            else reinterpret_cast<double *>(prm.out)[o] = v;
+        }
+    }
+}
+
 template <int OM, int RC>
 __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     extern __shared__ __attribute__((aligned(16))) double ylds[];   // [fd][Ncp]; paired: [G][fd][Ncp], one block per lane group
@@ -247,6 +413,12 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     if constexpr (OM == 1 && RC == 2) {
         if (prm.adjoint) {      // its own two loops: the forward launches' step loop below is as it was
             trunc_adjoint(prm, ylds);
+            return;
+        }
+    }
+    if constexpr (OM > 1) {
+        if (prm.adjoint) {      // 2, the POINTS mode: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
+            trunc_points(prm, ylds);
             return;
         }
     }
@@ -461,11 +633,20 @@ bool truncated_in_scope(int D, int M, int N, int L, int order) {
     return (int64_t)trunc_fd(D) * ((N + 15) / 16 * 16) <= TR_LDS_DOUBLES;
 }
 
-// paired != 0: the A = B pairs (x_p, y_p), out [A].  levels != 0: sigma is not read, out [L + 1][A][B] (paired: [L + 1][A])
+// THE scope of the points mode (the SK_OP_TRUNCATED_RBF rule of sk_route_query): M and N are POINTS, the rows and columns of the sweep, so
+// the rule is the one above on them, at order 1 only -- the mode is trunc_points, a loop of its own with two rows per lane; inside the
+// shared step loop k_trunc_sig<TR_OMAX, 1>, at 241 registers without it, needed 264: one wave per SIMD -- and a path has at least one step.
+bool truncated_points_in_scope(int D, int M, int N, int L, int order) {
+    return M >= 2 && N >= 2 && trunc_order(L, order) == 1 && truncated_in_scope(D, M, N, L, order);
+}
+
+// paired != 0: the A = B pairs (x_p, y_p), out [A].  levels != 0: sigma is not read, out [L + 1][A][B] (paired: [L + 1][A]).
+// kind 1: M and N count POINTS, param = 1 / sigma of the RBF static kernel
 template <typename TO>
 int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
-                     int order, const double *sigma, TO *out, hipStream_t s, int paired, int levels) {
-    if (!truncated_in_scope(D, M, N, L, order)) return SK_ERR_UNSUPPORTED;
+                     int order, const double *sigma, TO *out, hipStream_t s, int paired, int levels, int kind, double param) {
+    if (kind != 0 && kind != 1) return SK_ERR_BAD_ARG;
+    if (!(kind ? truncated_points_in_scope(D, M, N, L, order) : truncated_in_scope(D, M, N, L, order))) return SK_ERR_UNSUPPORTED;
     if (fd != trunc_fd(D) || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
     TruncParams prm;
     prm.Xr = Xr; prm.Yt = Yt; prm.out = out;
@@ -475,7 +656,8 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
     prm.out_f32 = sizeof(TO) == 4;
     prm.paired = paired != 0;
     prm.levels = levels != 0;
-    prm.adjoint = 0; prm.n_chunks = 1; prm.w = nullptr; prm.Tpart = nullptr; prm.slab = nullptr;
+    prm.param = kind ? param : 0.0;
+    prm.adjoint = kind ? 2 : 0; prm.n_chunks = 1; prm.w = nullptr; prm.Tpart = nullptr; prm.slab = nullptr;
     for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = levels ? (m == L ? 1.0 : 0.0) : (m <= L ? sigma[m] : 0.0);
     const int RC = prm.order == 1 ? 2 : 1;
     const int lanes = (M + RC - 1) / RC;
@@ -489,7 +671,8 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
     int64_t blocks = (int64_t)device_cu_count() * 8;
     if (blocks > prm.n_pos) blocks = prm.n_pos;
     const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
-    if (RC == 2) SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
+    // the points mode is order 1 with two rows per lane (the plan above), but its loop is compiled into the <TR_OMAX, 1> instance
+    if (RC == 2 && !kind) SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     else SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     return check_launch();
 }
@@ -559,6 +742,7 @@ int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int6
     prm.order = 1; prm.out_f32 = 0;
     prm.paired = paired != 0;
     prm.levels = 0;
+    prm.param = 0.0;
     for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
     prm.adjoint = 1; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
     prm.logW = pl.logW;
@@ -571,8 +755,8 @@ int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int6
 }
 
 template int launch_truncated<double>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
-                                      double *, hipStream_t, int, int);
+                                      double *, hipStream_t, int, int, int, double);
 template int launch_truncated<float>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
-                                     float *, hipStream_t, int, int);
+                                     float *, hipStream_t, int, int, int, double);
 
 }  // namespace sk

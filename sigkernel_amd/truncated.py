@@ -30,19 +30,23 @@ differentiably, and with per-path scales ``(lx[a] ly[b])^m`` in front, because `
 truncation below L, every choice of weights and every rescaling of the paths is a re-weighting of ONE sweep's output.
 ``truncated_robust_scales`` solves the scales of Chevyrev and Oberhauser's robust normalisation from the paired self levels.
 
-Each thing is stated once.  ``_level_sums`` is the recursion and ``_restatement`` its tiling, behind all three torch routes; the three public
+Each thing is stated once.  ``_level_sums`` is the recursion on a given G and ``_restatement`` its tiling, behind all three torch routes
+(``_step_gram``: G of steps; ``_lifted_gram``: G of points under a static kernel, TruncatedSigKernel's); the three public
 functions share ``_prepare`` (stage, check), ``_routed`` (try (X, Y), then (Y, X)) and ``_chunked`` (paired launches within the workspace);
 the ctypes call and the staging rule are the backend's (``_lib.HipBackend._truncated``, ``_lib._truncated_staging``).
 
 ``TruncatedSigKernel`` is the SigKernel-shaped front (paths in, ``compute_Gram`` / ``compute_kernel`` / ``compute_mmd``) and the one place where
 a gradient stays on the HIP route: ``_TruncatedLevels`` is an autograd function on the level terms whose forward is the levels mode and
 whose backward is the kernel's adjoint mode (``HipBackend.truncated_adjoint``: order 1, dim <= 8).  The three functions above keep their
-rule -- a gradient pending means the torch restatement.
+rule -- a gradient pending means the torch restatement.  Its ``static_kernel`` is the one place where G is something other than inner
+products of steps: an RBFKernel is the kernel's points mode (forward only), anything else the restatement on ``_lifted_gram``.
 """
 import numpy as np
 import torch
 
 from . import _lib
+from .sigkernel import _functional
+from .static_kernels import LinearKernel, RBFKernel
 
 __all__ = ["truncated_sig_kernel", "truncated_sig_kernel_paired", "truncated_sig_kernel_levels", "truncated_from_levels",
            "truncated_robust_scales", "TruncatedSigKernel"]
@@ -85,10 +89,23 @@ def _check_args(X, Y, num_levels, order):
     return num_levels, (num_levels if order < 1 else order)
 
 
-def _level_sums(X, Y, L, order, paired=False):
-    """THE recursion: yields k_1 .. k_L, each level's planes summed over the step grid -- (A, B) of all pairs, or -- paired -- (P,) of the
-    pairs (X[p], Y[p]): everything below G works on its last two axes"""
-    G = torch.einsum("pid,pjd->pij", X, Y) if paired else torch.einsum("aid,bjd->abij", X, Y)
+def _step_gram(X, Y, paired):
+    """G of the plain kernel: inner products of the STEPS X (A, M, D) and Y (B, N, D) -> (A, B, M, N), paired (P, M, N)"""
+    return torch.einsum("pid,pjd->pij", X, Y) if paired else torch.einsum("aid,bjd->abij", X, Y)
+
+
+def _lifted_gram(static_kernel):
+    """G of the kernel lifted through `static_kernel` (anything with Gram_matrix / batch_kernel): X and Y hold POINTS, and
+    G[i][j] = k(x_{i+1}, y_{j+1}) - k(x_{i+1}, y_j) - k(x_i, y_{j+1}) + k(x_i, y_j), the second difference of the static Gram"""
+    def gram(X, Y, paired):
+        K = static_kernel.batch_kernel(X, Y) if paired else static_kernel.Gram_matrix(X, Y)
+        return (K[..., 1:, 1:] - K[..., 1:, :-1]) - (K[..., :-1, 1:] - K[..., :-1, :-1])
+    return gram
+
+
+def _level_sums(G, L, order):
+    """THE recursion on a given G -- (A, B, M, N) of all pairs, or (P, M, N) of the pairs (X[p], Y[p]): yields k_1 .. k_L, each level's
+    planes summed over the step grid; everything works on G's last two axes, whatever static kernel G came from"""
     yield G.sum((-2, -1))
     R = [[G]]
     for m in range(1, L):
@@ -106,30 +123,34 @@ def _level_sums(X, Y, L, order, paired=False):
         yield sum(sum(row) for row in R).sum((-2, -1))
 
 
-def _block(X, Y, L, order, paired, sig):
-    """one tile: the weighted value sig[0] + sum_m sig[m] k_m, folded level by level as the sums arrive; sig None: the sums themselves,
-    stacked under the ones of level 0"""
+def _block(G, L, order, sig):
+    """one tile, from its G: the weighted value sig[0] + sum_m sig[m] k_m, folded level by level as the sums arrive; sig None: the sums
+    themselves, stacked under the ones of level 0"""
     if sig is None:
-        out = list(_level_sums(X, Y, L, order, paired))
+        out = list(_level_sums(G, L, order))
         return torch.stack([torch.ones_like(out[0])] + out, 0)
     K = sig[0]
-    for m, k in enumerate(_level_sums(X, Y, L, order, paired), 1):
+    for m, k in enumerate(_level_sums(G, L, order), 1):
         K = K + sig[m] * k
     return K
 
 
-def _restatement(X, Y, num_levels, sigma, order, paired, workspace_bytes):
+def _restatement(X, Y, num_levels, sigma, order, paired, workspace_bytes, gram=None):
     """The three torch routes: check, empty case, and the recursion tiled over rows of X (over pairs) so that a tile's (2 d^2 + 6) arrays
     of the step grid -- times the levels autograd keeps -- stay within `workspace_bytes`.  sigma None: the level terms, tiles joined along
-    axis 1 under the level axis; else the weighted value."""
+    axis 1 under the level axis; else the weighted value.  `gram(X tile, Y, paired)` supplies a tile's G: None -- X and Y hold steps and G
+    is their inner products; a _lifted_gram -- they hold POINTS, the grid has one row and column fewer, and the tile's static Gram is one
+    more array of the workspace."""
     num_levels, order = _check_args(X, Y, num_levels, order)
     if paired and X.shape[0] != Y.shape[0]:
         raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
     sig = None if sigma is None else _sigma_vector(sigma, num_levels, X.dtype, X.device)
-    A, M = X.shape[0], X.shape[1]
-    B, N = Y.shape[0], Y.shape[1]
+    lifted = gram is not None
+    gram = gram or _step_gram
+    A, M = X.shape[0], X.shape[1] - lifted
+    B, N = Y.shape[0], Y.shape[1] - lifted
     shape = (A,) if paired else (A, B)
-    if A == 0 or B == 0 or M == 0 or N == 0:
+    if A == 0 or B == 0 or M <= 0 or N <= 0:
         if sig is not None:
             return sig[0] * torch.ones(shape, dtype=X.dtype, device=X.device)
         out = torch.zeros((num_levels + 1,) + shape, dtype=X.dtype, device=X.device)
@@ -138,16 +159,17 @@ def _restatement(X, Y, num_levels, sigma, order, paired, workspace_bytes):
     d = min(num_levels, order)
     budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
     kept = num_levels if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad) else 1
-    per_row = (1 if paired else B) * M * N * X.element_size() * (2 * d * d + 6) * kept
+    per_row = (1 if paired else B) * M * N * X.element_size() * (2 * d * d + 6 + lifted) * kept
     rows = int(max(1, min(A, budget // max(1, per_row))))
-    return torch.cat([_block(X[a:a + rows], Y[a:a + rows] if paired else Y, num_levels, order, paired, sig) for a in range(0, A, rows)],
+    return torch.cat([_block(gram(X[a:a + rows], Y[a:a + rows] if paired else Y, paired), num_levels, order, sig) for a in range(0, A, rows)],
                      1 if sig is None else 0)
 
 
-def _truncated_levels_torch(X, Y, num_levels, order=-1, paired=False, workspace_bytes=None):
+def _truncated_levels_torch(X, Y, num_levels, order=-1, paired=False, workspace_bytes=None, gram=None):
     """The level terms k_0 .. k_L in torch ops on the tensors' own device, differentiable: (L + 1, A, B), paired (L + 1, P).  The recursion
-    of _truncated_torch with each level's sum kept, tiled over rows of X (over pairs) by `workspace_bytes` exactly as it is."""
-    return _restatement(X, Y, num_levels, None, order, paired, workspace_bytes)
+    of _truncated_torch with each level's sum kept, tiled over rows of X (over pairs) by `workspace_bytes` exactly as it is.  `gram`:
+    _restatement's -- a _lifted_gram on POINTS."""
+    return _restatement(X, Y, num_levels, None, order, paired, workspace_bytes, gram)
 
 
 def _truncated_torch(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=None):
@@ -451,10 +473,22 @@ class TruncatedSigKernel:
     and every batch that needs a gradient are in the kernel's scope (path dim <= 8 and at most 128 steps on a side that needs a gradient:
     sk_route_query(SK_OP_TRUNCATED_ADJOINT)) and a block's slab of (num_levels - 1) x (steps of the other side + lanes - 1) KB fits
     ``workspace_bytes`` (default 1 GiB).  Everything else -- CPU tensors, other orders, wider or longer paths -- takes the torch
-    restatement as a whole, tiled by ``workspace_bytes``: the values do not depend on the route beyond rounding."""
+    restatement as a whole, tiled by ``workspace_bytes``: the values do not depend on the route beyond rounding.
 
-    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None):
+    ``static_kernel`` lifts the kernel through a static kernel k on the paths' POINTS, as Kiraly and Oberhauser state it:
+    ``G[i][j] = k(x_{i+1}, y_{j+1}) - k(x_{i+1}, y_j) - k(x_i, y_{j+1}) + k(x_i, y_j)`` takes the place of ``<dx_i, dy_j>``.  ``None`` (the
+    default) and a ``LinearKernel`` -- whose second difference IS ``<dx_i, dy_j>``, and whose ``Gram_matrix`` ignores ``scale`` -- are the
+    plain kernel on its own code path.  An ``RBFKernel(s)`` on a HIP device with no gradient pending is ONE launch of the same HIP kernel
+    in its points mode (k evaluated in the sweep from differences of coordinates, nothing of size pairs x M x N allocated) at order 1,
+    path dim <= 16, <= 8 levels and at most 128 POINTS on one side (sk_route_query(SK_OP_TRUNCATED_RBF)); the mode has no adjoint, so a
+    gradient, a CPU tensor or a shape outside that scope takes the torch restatement on the second differences of ``k.Gram_matrix`` /
+    ``k.batch_kernel`` -- as does every other duck-typed static kernel -- differentiable in the paths and in ``sigma`` and tiled by
+    ``workspace_bytes``.  A function-valued kernel (``features`` and ``base_kernel``) maps the paths through ``features`` once and lifts
+    its ``base_kernel``."""
+
+    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None, static_kernel=None):
         self.num_levels, self.sigma, self.order, self.workspace_bytes = num_levels, sigma, order, workspace_bytes
+        self.static_kernel = static_kernel
 
     def _hip_serves(self, dx, dy, L, order, paired, sym):
         """the HIP function serves the call: a HIP device, no empty axis, the forward in scope on (dx, dy) or (dy, dx), and on every side
@@ -476,12 +510,33 @@ class TruncatedSigKernel:
             return False
         return True
 
+    def _lifted_levels(self, X, Y, static_kernel, L, order, paired):
+        """the level terms of the POINTS X, Y under `static_kernel`: the HIP kernel's points mode for an RBFKernel where it serves (a HIP
+        device, no gradient pending, sk_route_query(SK_OP_TRUNCATED_RBF) on (X, Y) or (Y, X)), else the restatement on the lifted G"""
+        param = static_kernel.sigma if type(static_kernel) is RBFKernel else None
+        if param is not None and X.is_cuda and not _needs_grad(X, Y, param) and min(X.shape[0], Y.shape[0]) > 0:
+            be = _lib.get_backend()
+            if hasattr(be, "truncated_levels") and be.route(_lib.OP_TRUNCATED_RBF, order, X.shape[2], X.shape[1], Y.shape[1], L, False,
+                                                            X.element_size()) != _lib.ROUTE_STREAM:
+                call = lambda x, y: be.truncated_levels(x, y, L, order, paired=paired, kind=1, param=float(param))
+                lev = _routed(_chunked(call, self.workspace_bytes, 1) if paired else call, X.detach().contiguous(),
+                              Y.detach().contiguous(), not paired)
+                if lev is not None:
+                    return lev
+        return _truncated_levels_torch(X, Y, L, order, paired, self.workspace_bytes, _lifted_gram(static_kernel))
+
     def _levels(self, X, Y, paired, sym):
+        static_kernel = self.static_kernel
+        if static_kernel is not None and _functional(static_kernel):
+            fX = static_kernel.features(X)      # function-valued paths: mapped once, as SigKernel does
+            X, Y, static_kernel = fX, (fX if Y is X else static_kernel.features(Y)), static_kernel.base_kernel
         L, order = _check_args(X, Y, self.num_levels, self.order)
         if paired and X.shape[0] != Y.shape[0]:
             raise ValueError("X and Y must hold the same number of paths, got %d and %d" % (X.shape[0], Y.shape[0]))
         if sym and Y is not X:
             raise ValueError("sym=True needs Y is X")
+        if static_kernel is not None and type(static_kernel) is not LinearKernel:
+            return self._lifted_levels(X, Y, static_kernel, L, order, paired)
         dx = X[:, 1:] - X[:, :-1]
         dy = dx if Y is X else Y[:, 1:] - Y[:, :-1]
         if self._hip_serves(dx, dy, L, order, paired, sym):
