@@ -63,7 +63,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -125,6 +125,11 @@ const char *sk_cost_note(int which);
                                  rows and columns of the sweep.  SK_ROUTE_FUSED = sk_truncated_points_* with kind 1: SK_OP_TRUNCATED's rule on
                                  the points at order 1 (kind 1, or num_levels 1: M <= 128; 8 or 16 x ceil16(N) <= 2048) and M, N >= 2;
                                  SK_ROUTE_FUSED_SWAP = the same on (y, x), transposed; SK_ROUTE_STREAM = the host layer's torch restatement. */
+#define SK_OP_TRUNCATED_RBF_ADJOINT 7 /* the gradient of the lifted kernel's level terms with respect to the POINTS of the FIRST batch (kind,
+                                 dyadic, M, N as SK_OP_TRUNCATED_RBF: points): SK_ROUTE_FUSED = sk_truncated_points_adjoint: inside
+                                 SK_OP_TRUNCATED_RBF's FUSED scope with path dim <= 8 (order 1, 2 <= M <= 128, N >= 2, 8 x ceil16(N) <= 2048);
+                                 SK_ROUTE_STREAM otherwise = autograd of the host layer's torch restatement.  Never swapped: the second
+                                 batch's gradient is the same query on (N, M). */
 #define SK_ROUTE_STREAM 0
 #define SK_ROUTE_FUSED 1
 #define SK_ROUTE_FUSED_MB 2
@@ -554,6 +559,20 @@ int sk_truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num
 int sk_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                          int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
                          int paired);
+/* The same gradient for the kernel lifted through the RBF static kernel (sk_truncated_points_* with kind 1), with respect to the POINTS of
+ * the first batch: Xr / Yt hold the M / N points, param = 1 / sigma of RBFKernel > 0, w and Tpart [n_chunks][A][M][8] as above.  With
+ * dG the plain adjoint's gradient with respect to G on the nodes (i, c >= 1; zero elsewhere) and
+ * H(i, c) = dG(i, c) - dG(i, c + 1) - dG(i + 1, c) + dG(i + 1, c + 1):  dx_i = sum_c H(i, c) kap(i, c) (-2 param) (x_i - y_c) -- the first point of a
+ * path and the first column carry no node and do receive a gradient.  Two sweeps per pair as above; the slab holds one plane more, the
+ * node's G beside its prefix factors: num_levels (N + W - 1) KB per block.  Plain stores, no atomics: bit-reproducible.
+ *   sk_truncated_points_adjoint_plan  plan[0..2] as sk_truncated_adjoint_plan's.  Host only.
+ *   sk_truncated_points_adjoint       n_chunks in 1 .. B (paired: 1), usually the plan's; slab / slab_bytes: device scratch, never empty.
+ * Scope: sk_route_query(SK_OP_TRUNCATED_RBF_ADJOINT, 1, D, M, N, num_levels, ...) == SK_ROUTE_FUSED; else SK_ERR_UNSUPPORTED. */
+int sk_truncated_points_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
+                                     int64_t *plan);
+int sk_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                int num_levels, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab,
+                                size_t slab_bytes, void *stream, int paired);
 /* Symmetric Gram matrix of ONE path batch with the fused kernels above: only the A (A + 1) / 2 pairs on and above the diagonal are
  * solved (what the reference's CPU solver does for sym=True, cython_backend.pyx:74-97; its GPU path ignores `sym`), in ONE launch,
  * and each value is written to out[a][b] and out[b][a]: out [A][A] is exactly symmetric.  dXr / dXt (Xr / Xt): the row-major and

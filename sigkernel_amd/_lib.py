@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libsigkernel_amd.so")
 SK_OK = 0
 # sk_route_query: operations and answers (include/sigkernel_amd.h)
 OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED, OP_TRUNCATED_ADJOINT, OP_TRUNCATED_RBF = 0, 1, 2, 3, 4, 5, 6
+OP_TRUNCATED_RBF_ADJOINT = 7
 ROUTE_STREAM, ROUTE_FUSED, ROUTE_FUSED_MB, ROUTE_FUSED_MB_SWAP, ROUTE_FUSED_SWAP = 0, 1, 2, 3, 4
 ROUTE_NO_STREAM = 1
 ROUTE_NO_SWAP = 2
@@ -99,6 +100,9 @@ SIGNATURES = {
     "sk_truncated_points_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _int, _vp, _vp, _vp]),
     "sk_truncated_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
     "sk_truncated_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
+    "sk_truncated_points_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
+    "sk_truncated_points_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _i64, _vp, _sz,
+                                           _vp, _int]),
     "sk_prep_pair_f64": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_prep_pair_f32": (_int, [_vp, _i64, _int, _vp, _i64, _int, _int, _int, ctypes.c_double, ctypes.c_double, _vp, _int, _vp, _int, _int, _vp]),
     "sk_solve_fwd_static_workspace_bytes": (_sz, [_int, _i64, _int, _int, _int, _int]),
@@ -705,17 +709,66 @@ class HipBackend:
         """The level terms k_0 .. k_L from ONE sweep per pair (the kernel's levels mode): (num_levels + 1, A, B), paired (num_levels + 1, P)."""
         return self._truncated(X, Y, num_levels, order, bool(paired), None, kind, param)
 
-    def truncated_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
-        """whether truncated_adjoint serves the shape: SK_OP_TRUNCATED_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""
-        if self.route(OP_TRUNCATED_ADJOINT, 1, D, M, N, num_levels, False, elem_size) != ROUTE_FUSED:
+    def _adjoint_fits(self, op, plan_name, A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size):
+        """route `op` says FUSED and one block's slab fits `workspace_bytes`, by the plan entry point `plan_name`"""
+        if self.route(op, 1, D, M, N, num_levels, False, elem_size) != ROUTE_FUSED:
             return False
         plan = (ctypes.c_int64 * 3)()
         budget = (1 << 30) if workspace_bytes is None else max(0, int(workspace_bytes))
-        rc = load().sk_truncated_adjoint_plan(max(1, int(A)), max(1, int(B)), M, N, D, int(num_levels), int(bool(paired)), budget,
-                                              ctypes.cast(plan, ctypes.c_void_p))
+        rc = getattr(load(), plan_name)(max(1, int(A)), max(1, int(B)), M, N, D, int(num_levels), int(bool(paired)), budget,
+                                        ctypes.cast(plan, ctypes.c_void_p))
         if rc != 2:
-            _check(rc, "sk_truncated_adjoint_plan")
+            _check(rc, plan_name)
         return rc == SK_OK
+
+    def truncated_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
+        """whether truncated_adjoint serves the shape: SK_OP_TRUNCATED_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""
+        return self._adjoint_fits(OP_TRUNCATED_ADJOINT, "sk_truncated_adjoint_plan", A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size)
+
+    def truncated_points_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
+        """whether truncated_points_adjoint serves the shape (M, N in POINTS): SK_OP_TRUNCATED_RBF_ADJOINT says FUSED and one block's slab of
+        num_levels x (N + lanes - 1) KB fits `workspace_bytes`"""
+        return self._adjoint_fits(OP_TRUNCATED_RBF_ADJOINT, "sk_truncated_points_adjoint_plan", A, B, M, N, D, num_levels, paired,
+                                  workspace_bytes, elem_size)
+
+    def _adjoint(self, op, plan_name, launch_name, mode_args, X, Y, w, num_levels, paired, workspace_bytes):
+        """the one adjoint call of k_trunc_sig behind truncated_adjoint and truncated_points_adjoint: route `op`, the plan, the staging, the
+        launch (`mode_args` go between num_levels and w) and the sum over the chunks' parts; None outside the scope or the workspace"""
+        _dev(X, "X")
+        _dev(Y, "Y")
+        (A, M, D), (B, N), L = X.shape, Y.shape[:2], int(num_levels)
+        if self.route(op, 1, D, M, N, L, False, X.element_size()) != ROUTE_FUSED:
+            return None
+        if A == 0 or B == 0:
+            return torch.zeros(A, M, D, dtype=torch.float64, device=X.device)
+        lib = load()
+        plan = (ctypes.c_int64 * 3)()
+        budget = (1 << 30) if workspace_bytes is None else max(0, int(workspace_bytes))
+        rc = getattr(lib, plan_name)(A, B, M, N, D, L, int(bool(paired)), budget, ctypes.cast(plan, ctypes.c_void_p))
+        if rc == 2:
+            return None
+        _check(rc, plan_name)
+        n_chunks, slab_bytes = int(plan[0]), int(plan[2])
+        fd, Ncp = _truncated_staging(D, N)
+        w = w.to(dtype=torch.float64, device=X.device).contiguous()
+        with _device(X.device):
+            Xr, Yt = _prep_pair(X, Y, False, 1.0, M, Ncp, fd)
+            Tpart = torch.empty(n_chunks, A, M, fd, dtype=torch.float64, device=X.device)
+            slab = torch.empty(slab_bytes // 8, dtype=torch.float64, device=X.device) if slab_bytes else None
+            rc = getattr(lib, launch_name)(_ptr(Xr), _ptr(Yt), A, B, M, M, N, Ncp, D, fd, L, *mode_args, _ptr(w), _ptr(Tpart), n_chunks,
+                                           _ptr(slab) if slab is not None else None, slab_bytes, _stream(X), int(bool(paired)))
+        _check(rc, launch_name)
+        return (Tpart[0] if n_chunks == 1 else Tpart.sum(0))[:, :, :D]
+
+    def truncated_points_adjoint(self, X, Y, w, num_levels, param, paired=False, workspace_bytes=None):
+        """The gradient of ``sum_pairs sum_m w[m - 1, pair] k_m(pair)`` with respect to the POINTS X, the k_m those of the kernel lifted through
+        RBFKernel(param), by k_trunc_sig<4, 1> in its points-adjoint mode (sk_truncated_points_adjoint): X (A, M, D) / Y (B, N, D) hold
+        points, w and the result as truncated_adjoint's; the slab has one plane more, num_levels x (N + lanes - 1) KB per block.  None outside
+        the scope (sk_route_query(SK_OP_TRUNCATED_RBF_ADJOINT) != FUSED) or when one block's slab does not fit `workspace_bytes`."""
+        if not float(param) > 0:
+            return None
+        return self._adjoint(OP_TRUNCATED_RBF_ADJOINT, "sk_truncated_points_adjoint_plan", "sk_truncated_points_adjoint", (1.0 / float(param),),
+                             X, Y, w, num_levels, paired, workspace_bytes)
 
     def truncated_adjoint(self, X, Y, w, num_levels, paired=False, workspace_bytes=None):
         """The gradient of ``sum_pairs sum_m w[m - 1, pair] k_m(pair)`` with respect to X, by k_trunc_sig<1, 2> in its adjoint mode
@@ -724,31 +777,8 @@ class HipBackend:
         torch adds the chunks; between its two sweeps of a pair a block keeps the prefix factors in a slab of (num_levels - 1) x
         (N + lanes - 1) KB, all blocks' within `workspace_bytes` (default 1 GiB; the block count is lowered until they fit).  None
         outside the scope (sk_route_query(SK_OP_TRUNCATED_ADJOINT) != FUSED: order 1, dim <= 8) or when one block's slab does not fit."""
-        _dev(X, "X")
-        _dev(Y, "Y")
-        (A, M, D), (B, N), L = X.shape, Y.shape[:2], int(num_levels)
-        if self.route(OP_TRUNCATED_ADJOINT, 1, D, M, N, L, False, X.element_size()) != ROUTE_FUSED:
-            return None
-        if A == 0 or B == 0:
-            return torch.zeros(A, M, D, dtype=torch.float64, device=X.device)
-        lib = load()
-        plan = (ctypes.c_int64 * 3)()
-        budget = (1 << 30) if workspace_bytes is None else max(0, int(workspace_bytes))
-        rc = lib.sk_truncated_adjoint_plan(A, B, M, N, D, L, int(bool(paired)), budget, ctypes.cast(plan, ctypes.c_void_p))
-        if rc == 2:
-            return None
-        _check(rc, "sk_truncated_adjoint_plan")
-        n_chunks, slab_bytes = int(plan[0]), int(plan[2])
-        fd, Ncp = _truncated_staging(D, N)
-        w = w.to(dtype=torch.float64, device=X.device).contiguous()
-        with _device(X.device):
-            Xr, Yt = _prep_pair(X, Y, False, 1.0, M, Ncp, fd)
-            Tpart = torch.empty(n_chunks, A, M, fd, dtype=torch.float64, device=X.device)
-            slab = torch.empty(slab_bytes // 8, dtype=torch.float64, device=X.device) if slab_bytes else None
-            rc = lib.sk_truncated_adjoint(_ptr(Xr), _ptr(Yt), A, B, M, M, N, Ncp, D, fd, L, _ptr(w), _ptr(Tpart), n_chunks,
-                                          _ptr(slab) if slab is not None else None, slab_bytes, _stream(X), int(bool(paired)))
-        _check(rc, "sk_truncated_adjoint")
-        return (Tpart[0] if n_chunks == 1 else Tpart.sum(0))[:, :, :D]
+        return self._adjoint(OP_TRUNCATED_ADJOINT, "sk_truncated_adjoint_plan", "sk_truncated_adjoint", (), X, Y, w, num_levels, paired,
+                             workspace_bytes)
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):
         """The loss wrappers' forward in THREE launches (csrc/sk_loss.hip): [X; Y] staged in both layouts straight from the two

@@ -532,6 +532,25 @@ int sk_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t 
     return launch_truncated_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, w, Tpart, n_chunks, slab, slab_bytes,
                                     (hipStream_t)stream, paired);
 }
+int sk_truncated_points_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
+                                     int64_t *plan) {
+    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
+    size_t slab = 0;
+    const int rc = truncated_points_adjoint_plan(A, B, M, N, D, num_levels, paired, workspace_bytes, plan, plan + 1, &slab);
+    if (rc == SK_OK) plan[2] = (int64_t)slab;
+    return rc;
+}
+int sk_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                int num_levels, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab,
+                                size_t slab_bytes, void *stream, int paired) {
+    if (paired) B = A;
+    if (D < 1 || !Xr || !Yt || !w || !Tpart || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D ||
+        !(param > 0.0) || !slab || !slab_bytes)
+        return SK_ERR_BAD_ARG;
+    if (A == 0 || B == 0) return SK_OK;
+    return launch_truncated_points_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, param, w, Tpart, n_chunks, slab, slab_bytes,
+                                           (hipStream_t)stream, paired);
+}
 int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream) {
     return solve_prefix<double>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, queue, stream);

@@ -206,6 +206,15 @@ int truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int
 int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
                              const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s, int paired);
 bool truncated_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_ADJOINT rule of sk_route_query
+// The POINTS-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (order 1, dim <= 8): the same gradient for the kernel lifted through the RBF static
+// kernel, with respect to the POINTS of x -- M and N count points, param = 1 / sigma of the RBF kernel, Tpart [n_chunks][A][M][8], w as
+// above.  A block's slab holds one plane more than the plain adjoint's: the node's g beside its L - 1 prefix factors.
+int truncated_points_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                                  int64_t *blocks, size_t *slab_bytes);
+int launch_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                    int L, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes,
+                                    hipStream_t s, int paired);
+bool truncated_points_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_RBF_ADJOINT rule of sk_route_query
 
 // ---- sk_loss.hip: the glue of the loss wrappers (compute_mmd / scoring rules) as single launches ----
 template <typename T>

@@ -177,6 +177,12 @@ int route_query(int op, int kind, int D, int M, int N, int d, int naive, int ele
         if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
         return truncated_adjoint_in_scope(D, M, N, d, kind) ? SK_ROUTE_FUSED : SK_ROUTE_STREAM;
     }
+    if (op == SK_OP_TRUNCATED_RBF_ADJOINT) {
+        // ... of the lifted kernel's level terms with respect to the POINTS of the first batch (M / N = points): FUSED = the points-adjoint
+        // mode of k_trunc_sig<4, 1> (truncated_points_adjoint_in_scope is the rule), STREAM = autograd of the torch restatement.  Never swapped.
+        if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
+        return truncated_points_adjoint_in_scope(D, M, N, d, kind) ? SK_ROUTE_FUSED : SK_ROUTE_STREAM;
+    }
     if ((kind != 0 && kind != 1) || D < 1 || D > 16 || M < 2 || N < 2 || d < 0 || d > 2) return SK_ROUTE_STREAM;
     if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
     const int Mc = M - 1, Nc = N - 1;

@@ -37,6 +37,9 @@
 // lifted through the RBF static kernel -- x and y staged as POINTS, G the second difference of exp(-|x - y|^2 param) on the grid of points,
 // evaluated in the sweep: trunc_points below, with a loop of its own, compiled into the <TR_OMAX, 1> instance; the forward launches run
 // the step loop they ran.
+// POINTS-ADJOINT mode (TruncParams::adjoint = 3, launch-time and wave-uniform; order 1, fd = 8; Gram and paired): the gradient of a weighted
+// sum of the LIFTED kernel's level terms with respect to the points of x -- trunc_points_adjoint below, the two phases of trunc_adjoint on
+// the grid of points with the chain rule through kap; hosted by the <TR_OMAX, 1> instance beside trunc_points.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
 // order (1: one plane per level, or TR_OMAX) and the rows per lane.
 #include "sk_wave_common.h"
@@ -58,7 +61,8 @@ struct TruncParams {
     int levels;         // 0: one weighted value per pair; 1: the pair's L + 1 level terms, one plane of `out` per level
     double sigma[TR_LMAX + 1];
     // ADJOINT mode (order 1, fd = 8: trunc_adjoint below).  `out` is not used.
-    int adjoint;        // 0: a forward launch; 1: dX of sum_pairs sum_m w[m][pair] k_m; 2: the POINTS mode, a forward launch on points (below)
+    int adjoint;        // 0: a forward launch; 1: dX of sum_pairs sum_m w[m][pair] k_m; 2: the POINTS mode, a forward launch on points (below);
+                        // 3: the POINTS-ADJOINT mode, 1 for the lifted kernel (slab: L planes, the last one g)
     int64_t n_chunks;   // Gram: the B pairs of a row tile go to this many positions; paired: 1
     const double *w;    // [L][A][B], paired [L][A]: the weight of level m + 1 of every pair
     double *Tpart;      // [n_chunks][A][M][8]: the chunks' parts of dX, summed by the caller
@@ -398,6 +402,216 @@ __device__ __forceinline__ void trunc_points(const TruncParams &prm, double *yld
     }
 }
 
+// POINTS-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 3, launch-time and wave-uniform; order 1, two rows per lane, fd = 8):
+// the gradient with respect to the POINTS of x of  sum_pairs sum_m w_m(pair) k_m(pair)  for the lifted kernel of trunc_points.  With dG the
+// gradient with respect to g on the nodes (i, c >= 1) -- trunc_adjoint's reverse recursion, word for word -- and zero everywhere else,
+//     H(i, c) = dG(i, c) - dG(i, c + 1) - dG(i + 1, c) + dG(i + 1, c + 1)             is the gradient with respect to kap(i, c), and
+//     dx_i    = sum_c H(i, c) kap(i, c) (-2 param) (x_i - y_c).
+// Row 0 (a path's first point) and column 0 carry no node and DO receive a gradient: the sweep visits them with dG = 0.
+// Pairs, chunks, Tpart and the two phases are trunc_adjoint's; what differs:
+//   phase 1  is trunc_points' loop without its sums; beside the L - 1 prefix factors it stores the g of both rows as one more plane of the
+//            slab (plane L - 1): in phase 2 the lane above has not reached column c yet, so D(i - 1, c) cannot come down by DPP, and a third
+//            x row in registers (16 VGPRs and a second exp per node) costs more than 16 bytes of a store that is contiguous anyway;
+//   phase 2  reads the factors and g, runs the mirrored recursion, and forms H as the forward's dup / dc mirrored: a lane carries
+//            dG(i, c + 1) per row, E(i, c) = dG(i, c) - dG(i, c + 1); row 1 goes first and takes E(i + 1, c), the E of the lane below's first
+//            row one step ago, by one DPP wave_shl:1 at the top of the step (0 into a group's last lane); row 0 takes row 1's E of this
+//            step.  kap(i, c) is recomputed, one exp_nonpos per node, from the coordinate differences that then carry the gradient.
+// The level guards of a step compare against Ls, the level count read through an empty asm at the top of the step: hoisted out of the
+// step loops they are seven scalar register pairs per phase that live across the whole function, and this instance already spills scalar
+// registers to vector lanes -- with them hoisted the general step loop gained four lane reads a step and orders 2 - 4 lost 1.0 - 1.3 %
+// (profiles/truncated_static_adjoint.txt).
+__device__ __forceinline__ void trunc_points_adjoint(const TruncParams &prm, double *ylds) {
+    constexpr int NS = TR_LMAX - 1;
+    const int lane = threadIdx.x;
+    const int W = 1 << prm.logW, G = WAVE >> prm.logW;
+    const int lam = lane & (W - 1), grp = lane >> prm.logW;
+    const int N = prm.N, Ncp = prm.Ncp, L = prm.L;
+    const int steps = N + W - 1;
+    const bool paired = prm.paired != 0;
+    const int64_t plane = paired ? prm.A : prm.A * prm.B;
+    const double nparam = -prm.param;
+    double2 *slab = reinterpret_cast<double2 *>(prm.slab + (int64_t)blockIdx.x * L * steps * 128) + lane;
+    for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
+        int64_t a, b0, b1, chunk = 0;
+        int nblk = 1;
+        if (paired) {
+            b0 = pos * G;
+            b1 = b0 + 1;
+            a = b0 + grp;
+            nblk = prm.A - b0 < G ? (int)(prm.A - b0) : G;
+        } else {
+            const int64_t at = pos / prm.n_chunks;
+            chunk = pos - at * prm.n_chunks;
+            b0 = chunk * prm.B / prm.n_chunks;
+            b1 = (chunk + 1) * prm.B / prm.n_chunks;
+            a = at * G + grp;
+        }
+        const bool live = a < prm.A;
+        const double *yl = ylds + ((paired && live) ? grp * 8 * Ncp : 0);
+        double xr[2][8], dX[2][8];
+        bool node[2];       // the row has nodes: not the first point, not padding
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int row = lam * 2 + r;
+            const bool ok = live && row < prm.M;
+            const double *xp = prm.Xr + ((ok ? a : 0) * (int64_t)prm.Mrows + (ok ? row : 0)) * 8;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                xr[r][k] = ok ? xp[k] : 0.0;
+                dX[r][k] = 0.0;
+            }
+            node[r] = ok && row > 0;
+        }
+        for (int64_t b = b0; b < b1; ++b) {
+            __syncthreads();
+            {
+                const double *yb = prm.Yt + b * (int64_t)8 * Ncp;
+                for (int k = lane; k < nblk * 8 * Ncp; k += WAVE) ylds[k] = yb[k];
+            }
+            double w[TR_LMAX];
+#pragma unroll
+            for (int m = 0; m < TR_LMAX; ++m) w[m] = (live && m < L) ? prm.w[m * plane + (paired ? a : a * prm.B + b)] : 0.0;
+            __syncthreads();
+            {   // phase 1: trunc_points' loop
+                double rowS[2][NS], qio[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) qio[s] = rowS[0][s] = rowS[1][s] = 0.0;
+                double kc[2] = {0.0, 0.0}, xc[2] = {0.0, 0.0}, dc = 0.0;
+                for (int t = 0; t < steps; ++t) {
+                    int Ls = L;
+                    asm volatile("" : "+s"(Ls));      // the level guards of a step are scalar compares of its own
+                    const int j = t - lam;
+                    const bool act = (unsigned)j < (unsigned)N;
+                    const int jc = act ? j : 0;
+                    double dup = dpp_shr1_zero(dc);
+                    double qin[NS], pf[2][NS], gs[2], yv[8];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        const double v = s < Ls - 1 ? dpp_shr1_zero(qio[s]) : 0.0;
+                        qin[s] = lam == 0 ? 0.0 : v;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) yv[k] = yl[k * Ncp + jc];
+                    asm volatile("s_waitcnt lgkmcnt(0)"
+                                 : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        double d2 = 0.0;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) {
+                            const double e = xr[r][k] - yv[k];
+                            d2 = fma(e, e, d2);
+                        }
+                        const double xn = d2 * nparam, kn = exp_nonpos(xn);
+                        const double dx = xn - xc[r];
+                        const double d = (dx <= 0.0 ? kc[r] : -kn) * expm1_nonpos(-__builtin_fabs(dx));
+                        double g = d - dup;
+                        g = (act && j > 0 && node[r]) ? g : 0.0;
+                        kc[r] = kn;
+                        xc[r] = xn;
+                        dup = d;
+                        gs[r] = g;
+                        double prev = g;
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) {
+                            pf[r][s] = qin[s];
+                            if (s < Ls - 1) {
+                                const double next = g * qin[s];
+                                qin[s] = qin[s] + rowS[r][s];
+                                rowS[r][s] += prev;
+                                prev = next;
+                            }
+                        }
+                    }
+                    dc = dup;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        if (s < Ls - 1) slab[((int64_t)s * steps + t) * 64] = make_double2(pf[0][s], pf[1][s]);
+                        qio[s] = qin[s];
+                    }
+                    slab[((int64_t)(Ls - 1) * steps + t) * 64] = make_double2(gs[0], gs[1]);
+                }
+            }
+            {   // phase 2
+                double rowT[2][NS], sio[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) sio[s] = rowT[0][s] = rowT[1][s] = 0.0;
+                double dgn[2] = {0.0, 0.0};     // dG(i, c + 1) of the lane's two rows
+                double ec = 0.0;                // E(i, c) of the lane's first row at the column of the step before
+                for (int t = steps - 1; t >= 0; --t) {
+                    int Ls = L;
+                    asm volatile("" : "+s"(Ls));      // the level guards of a step are scalar compares of its own
+                    const int j = t - lam;
+                    const bool act = (unsigned)j < (unsigned)N;
+                    const int jc = act ? j : 0;
+                    double sup[NS], yv[8];
+                    double2 pf[NS];
+                    const double2 gg = slab[((int64_t)(Ls - 1) * steps + t) * 64];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        pf[s] = s < Ls - 1 ? slab[((int64_t)s * steps + t) * 64] : make_double2(0.0, 0.0);
+                        const double v = s < Ls - 1 ? dpp_shl1(sio[s], 0.0) : 0.0;
+                        sup[s] = lam == W - 1 ? 0.0 : v;
+                    }
+                    double eb = dpp_shl1(ec, 0.0);      // E(i + 1, c) of the lane's second row: the lane below was at column c one step ago
+                    eb = lam == W - 1 ? 0.0 : eb;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) yv[k] = yl[k * Ncp + jc];
+                    asm volatile("s_waitcnt lgkmcnt(0)"
+                                 : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                    for (int r = 1; r >= 0; --r) {
+                        const double g = r ? gg.y : gg.x;
+                        double rb = 0.0, dG = 0.0;
+#pragma unroll
+                        for (int m = TR_LMAX; m >= 1; --m)
+                            if (m <= Ls) {
+                                rb = m == Ls ? w[m - 1] : rb;
+                                dG = m == 1 ? dG + rb : fma(rb, r ? pf[m > 1 ? m - 2 : 0].y : pf[m > 1 ? m - 2 : 0].x, dG);
+                                if (m > 1) {
+                                    const int s = m - 2;
+                                    const double u = g * rb;
+                                    rb = w[s] + sup[s];
+                                    sup[s] = sup[s] + rowT[r][s];
+                                    rowT[r][s] += u;
+                                }
+                            }
+                        dG = (act && j > 0 && node[r]) ? dG : 0.0;
+                        const double E = dG - dgn[r];
+                        dgn[r] = dG;
+                        const double H = E - eb;
+                        eb = E;         // the row above's row below is this one
+                        double e[8], d2 = 0.0;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) {
+                            e[k] = xr[r][k] - yv[k];
+                            d2 = fma(e[k], e[k], d2);
+                        }
+                        double cf = (H * exp_nonpos(d2 * nparam)) * (2.0 * nparam);
+                        cf = act ? cf : 0.0;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) dX[r][k] = fma(cf, e[k], dX[r][k]);
+                    }
+                    ec = eb;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) sio[s] = sup[s];
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int row = lam * 2 + r;
+                if (row < prm.M) {
+                    double *tp = prm.Tpart + ((chunk * prm.A + a) * prm.M + row) * 8;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) tp[k] = dX[r][k];
+                }
+            }
+        }
+    }
+}
+
 template <int OM, int RC>
 __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     extern __shared__ __attribute__((aligned(16))) double ylds[];   // [fd][Ncp]; paired: [G][fd][Ncp], one block per lane group
@@ -417,8 +631,9 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
         }
     }
     if constexpr (OM > 1) {
-        if (prm.adjoint) {      // 2, the POINTS mode: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
-            trunc_points(prm, ylds);
+        if (prm.adjoint) {      // 2, the POINTS mode, and 3, its adjoint: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
+            if (prm.adjoint == 3) trunc_points_adjoint(prm, ylds);
+            else trunc_points(prm, ylds);
             return;
         }
     }
@@ -466,6 +681,10 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
             }
         }
         double acc = 0.0;
+        // <TR_OMAX, 1> only (<1, 2> is the code it was): its step loop, 7 KB of forward branches around the level and order guards, starts on
+        // a cache line.  Where the loop starts moves with every mode compiled in front of it, and orders 3 and 4 follow the offset by 1 %
+        // (offset 44 of 64: +0.9 %; 36, the offset before the points-adjoint mode: the time before it; here: profiles/truncated_static_adjoint.txt).
+        if constexpr (OM > 1) asm volatile(".p2align 6");
         for (int t = 0; t < steps; ++t) {
             const int j = t - lam;
             const bool act = (unsigned)j < (unsigned)N;
@@ -687,11 +906,11 @@ namespace {
 struct AdjointPlan {
     int logW;
     int64_t n_pos, n_chunks, blocks;
-    size_t block_bytes;     // a block's slab: (L - 1) levels x (N + W - 1) steps x 1 KB
+    size_t block_bytes;     // a block's slab: planes x (N + W - 1) steps x 1 KB; planes = L - 1 prefix factors, and g in the points-adjoint mode
 };
 // The split of an adjoint launch.  Gram: the B pairs of a row tile in as many chunks as fill the resident blocks (at most B; lengths
 // differ by one at most).  The block count is lowered until blocks x slab fits `workspace`; false when one block does not.
-bool plan_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int L, int paired, size_t workspace, AdjointPlan *pl) {
+bool plan_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int planes, int paired, size_t workspace, AdjointPlan *pl) {
     const int lanes = (M + 1) / 2;
     int logW = 0;
     while ((1 << logW) < lanes) ++logW;
@@ -707,7 +926,7 @@ bool plan_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int L, int paired
     }
     pl->n_pos = tiles * pl->n_chunks;
     pl->blocks = pl->n_pos < resident ? pl->n_pos : resident;
-    pl->block_bytes = (size_t)(L - 1) * (size_t)(N + (1 << logW) - 1) * 1024;
+    pl->block_bytes = (size_t)planes * (size_t)(N + (1 << logW) - 1) * 1024;
     if (pl->block_bytes) {
         const int64_t fit = (int64_t)(workspace / pl->block_bytes);
         if (fit < 1) return false;
@@ -721,7 +940,7 @@ int truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int
                            int64_t *blocks, size_t *slab_bytes) {
     if (!truncated_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
     AdjointPlan pl;
-    if (!plan_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
+    if (!plan_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L - 1, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
     *n_chunks = pl.n_chunks;
     *blocks = pl.blocks;
     *slab_bytes = (size_t)pl.blocks * pl.block_bytes;
@@ -734,7 +953,7 @@ int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int6
     if (fd != 8 || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
     if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
     AdjointPlan pl;
-    if (!plan_adjoint(A, B, M, N, Ncp, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
+    if (!plan_adjoint(A, B, M, N, Ncp, L - 1, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
     TruncParams prm;
     prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
     prm.A = A; prm.B = B;
@@ -751,6 +970,50 @@ int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int6
     int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
     const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
     SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
+    return check_launch();
+}
+
+// THE scope of the points-adjoint mode (the SK_OP_TRUNCATED_RBF_ADJOINT rule of sk_route_query; M and N are POINTS): the points mode's with
+// a path dim of at most 8, for the reason the adjoint mode has -- xr, the dX accumulators and either phase's per-level state within 256 registers.
+bool truncated_points_adjoint_in_scope(int D, int M, int N, int L, int order) {
+    return truncated_points_in_scope(D, M, N, L, order) && D <= 8;
+}
+
+int truncated_points_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                                  int64_t *blocks, size_t *slab_bytes) {
+    if (!truncated_points_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    AdjointPlan pl;
+    if (!plan_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
+    *n_chunks = pl.n_chunks;
+    *blocks = pl.blocks;
+    *slab_bytes = (size_t)pl.blocks * pl.block_bytes;
+    return SK_OK;
+}
+
+int launch_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                    int L, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes,
+                                    hipStream_t s, int paired) {
+    if (!truncated_points_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    if (fd != 8 || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B) || !(param > 0.0)) return SK_ERR_BAD_ARG;
+    if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
+    AdjointPlan pl;
+    if (!plan_adjoint(A, B, M, N, Ncp, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
+    TruncParams prm;
+    prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
+    prm.A = A; prm.B = B;
+    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
+    prm.order = 1; prm.out_f32 = 0;
+    prm.paired = paired != 0;
+    prm.levels = 0;
+    prm.param = param;
+    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
+    prm.adjoint = 3; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
+    prm.logW = pl.logW;
+    const int G = WAVE >> pl.logW;
+    prm.n_pos = (A + G - 1) / G * n_chunks;
+    int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
+    const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
+    SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     return check_launch();
 }
 

@@ -39,7 +39,8 @@ the ctypes call and the staging rule are the backend's (``_lib.HipBackend._trunc
 a gradient stays on the HIP route: ``_TruncatedLevels`` is an autograd function on the level terms whose forward is the levels mode and
 whose backward is the kernel's adjoint mode (``HipBackend.truncated_adjoint``: order 1, dim <= 8).  The three functions above keep their
 rule -- a gradient pending means the torch restatement.  Its ``static_kernel`` is the one place where G is something other than inner
-products of steps: an RBFKernel is the kernel's points mode (forward only), anything else the restatement on ``_lifted_gram``.
+products of steps: an RBFKernel is the kernel's points mode -- forward only, unless ``points_adjoint=True`` asks for ``_LiftedLevels``, whose
+backward is the kernel's points-adjoint mode (``HipBackend.truncated_points_adjoint``) -- anything else the restatement on ``_lifted_gram``.
 """
 import numpy as np
 import torch
@@ -405,6 +406,11 @@ def truncated_robust_scales(self_levels, C=4.0, a=1.0):
     return lam.cpu().numpy() if as_numpy else lam
 
 
+def _on_hip(t):
+    """the tensor lives on a HIP device: the one place TruncatedSigKernel asks (and the seam where the host tests stand a backend in on CPU tensors)"""
+    return t.is_cuda
+
+
 def _pair_slices(P, M, N, D, workspace_bytes):
     """the pairs of a paired batch in runs whose fp64 staging stays within `workspace_bytes` (_chunked's rule)"""
     budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
@@ -413,16 +419,38 @@ def _pair_slices(P, M, N, D, workspace_bytes):
     return [slice(p, p + pairs) for p in range(0, P, pairs)]
 
 
-def _adjoint(be, X, Y, w, L, paired, workspace_bytes):
-    """d / dX of sum_pairs sum_m w[m - 1, pair] k_m(pair) by the kernel's adjoint mode, in X's dtype; paired batches in _chunked's runs"""
-    if not paired:
-        parts = [be.truncated_adjoint(X, Y, w, L, False, workspace_bytes)]
+def _adjoint(be, X, Y, w, L, paired, workspace_bytes, param=None):
+    """d / dX of sum_pairs sum_m w[m - 1, pair] k_m(pair) by the kernel's adjoint mode, in X's dtype; paired batches in _chunked's runs.
+    `param`: X and Y hold POINTS and the k_m are those of the lift through RBFKernel(param) -- the points-adjoint mode"""
+    if param is None:
+        call = lambda x, y, v, p: be.truncated_adjoint(x, y, v, L, p, workspace_bytes)
     else:
-        parts = [be.truncated_adjoint(X[sl], Y[sl], w[:, sl], L, True, workspace_bytes)
-                 for sl in _pair_slices(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], workspace_bytes)]
+        call = lambda x, y, v, p: be.truncated_points_adjoint(x, y, v, L, param, p, workspace_bytes)
+    if not paired:
+        parts = [call(X, Y, w, False)]
+    else:
+        parts = [call(X[sl], Y[sl], w[:, sl], True) for sl in _pair_slices(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], workspace_bytes)]
     if any(t is None for t in parts):
         raise RuntimeError("the adjoint mode of k_trunc_sig declined a shape its route query accepted")
     return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)).to(X.dtype)
+
+
+def _levels_backward(ctx, grad, param=None):
+    """the backward of both autograd functions below: one adjoint launch per batch that needs a gradient, w = grad_levels[1:]"""
+    X, Y = ctx.saved_tensors
+    L, paired, sym, workspace_bytes = ctx.mode
+    be = _lib.get_backend()
+    w = grad[1:].double()
+    dX = dY = None
+    if sym:
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dX = _adjoint(be, X, X, w + w.transpose(1, 2), L, False, workspace_bytes, param)
+    else:
+        if ctx.needs_input_grad[0]:
+            dX = _adjoint(be, X, Y, w.contiguous(), L, paired, workspace_bytes, param)
+        if ctx.needs_input_grad[1]:
+            dY = _adjoint(be, Y, X, (w if paired else w.transpose(1, 2)).contiguous(), L, paired, workspace_bytes, param)
+    return dX, dY, None, None, None, None, None
 
 
 class _TruncatedLevels(torch.autograd.Function):
@@ -445,20 +473,30 @@ class _TruncatedLevels(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
-        X, Y = ctx.saved_tensors
-        L, paired, sym, workspace_bytes = ctx.mode
+        return _levels_backward(ctx, grad)
+
+
+class _LiftedLevels(torch.autograd.Function):
+    """_TruncatedLevels for POINT tensors under RBFKernel(param), order 1: forward = the points mode's levels launch (on (Y, X), transposed,
+    when only the second batch fits the lanes), backward = the points-adjoint mode, one launch per batch that needs a gradient and ONE with
+    w + w^T for a symmetric call.  The caller has asked the route table for every side (TruncatedSigKernel._points_adjoint_serves)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, L, param, paired, sym, workspace_bytes):
         be = _lib.get_backend()
-        w = grad[1:].double()
-        dX = dY = None
-        if sym:
-            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-                dX = _adjoint(be, X, X, w + w.transpose(1, 2), L, False, workspace_bytes)
-        else:
-            if ctx.needs_input_grad[0]:
-                dX = _adjoint(be, X, Y, w.contiguous(), L, paired, workspace_bytes)
-            if ctx.needs_input_grad[1]:
-                dY = _adjoint(be, Y, X, (w if paired else w.transpose(1, 2)).contiguous(), L, paired, workspace_bytes)
-        return dX, dY, None, None, None, None, None
+        call = lambda x, y: be.truncated_levels(x, y, L, 1, paired=paired, kind=1, param=param)
+        lev = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
+        if lev is None:
+            raise RuntimeError("the points mode of k_trunc_sig declined a shape its route query accepted")
+        ctx.save_for_backward(X, Y)
+        ctx.mode = (L, paired, sym, workspace_bytes)
+        ctx.param = param
+        return lev
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        return _levels_backward(ctx, grad, ctx.param)
 
 
 class TruncatedSigKernel:
@@ -480,20 +518,30 @@ class TruncatedSigKernel:
     default) and a ``LinearKernel`` -- whose second difference IS ``<dx_i, dy_j>``, and whose ``Gram_matrix`` ignores ``scale`` -- are the
     plain kernel on its own code path.  An ``RBFKernel(s)`` on a HIP device with no gradient pending is ONE launch of the same HIP kernel
     in its points mode (k evaluated in the sweep from differences of coordinates, nothing of size pairs x M x N allocated) at order 1,
-    path dim <= 16, <= 8 levels and at most 128 POINTS on one side (sk_route_query(SK_OP_TRUNCATED_RBF)); the mode has no adjoint, so a
-    gradient, a CPU tensor or a shape outside that scope takes the torch restatement on the second differences of ``k.Gram_matrix`` /
+    path dim <= 16, <= 8 levels and at most 128 POINTS on one side (sk_route_query(SK_OP_TRUNCATED_RBF)).  By default a gradient, like
+    a CPU tensor or a shape outside that scope, takes the torch restatement on the second differences of ``k.Gram_matrix`` /
     ``k.batch_kernel`` -- as does every other duck-typed static kernel -- differentiable in the paths and in ``sigma`` and tiled by
     ``workspace_bytes``.  A function-valued kernel (``features`` and ``base_kernel``) maps the paths through ``features`` once and lifts
-    its ``base_kernel``."""
+    its ``base_kernel``.
 
-    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None, static_kernel=None):
+    ``points_adjoint=True`` keeps the RBF lift on the HIP route WITH a gradient pending: the forward is the points mode's launch and the
+    backward the same kernel's points-adjoint mode, one launch per batch that requires grad (one in all for ``sym=True``), bit-reproducible,
+    nothing of size pairs x M x N allocated.  It takes effect for ``type(static_kernel) is RBFKernel`` at order 1 on a HIP device when the
+    forward is in the points mode's scope and every batch that requires grad has path dim <= 8, at most 128 points
+    (sk_route_query(SK_OP_TRUNCATED_RBF_ADJOINT)) and a block's slab of num_levels x (points of the other side + lanes - 1) KB within
+    ``workspace_bytes``; every other call takes the restatement as a whole, as without the keyword.  ``sigma`` keeps its gradient either way
+    (the RBF bandwidth is a float and has none).  The default is False -- every call then does what it did before the keyword existed --
+    and flipping it is left to a later change."""
+
+    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None, static_kernel=None, points_adjoint=False):
         self.num_levels, self.sigma, self.order, self.workspace_bytes = num_levels, sigma, order, workspace_bytes
         self.static_kernel = static_kernel
+        self.points_adjoint = bool(points_adjoint)
 
     def _hip_serves(self, dx, dy, L, order, paired, sym):
         """the HIP function serves the call: a HIP device, no empty axis, the forward in scope on (dx, dy) or (dy, dx), and on every side
         that needs a gradient order 1 and the adjoint in scope, its slab within the workspace"""
-        if not dx.is_cuda or min(dx.shape[0], dx.shape[1], dy.shape[0], dy.shape[1]) == 0:
+        if not _on_hip(dx) or min(dx.shape[0], dx.shape[1], dy.shape[0], dy.shape[1]) == 0:
             return False
         be = _lib.get_backend()
         if not (hasattr(be, "truncated_levels") and hasattr(be, "truncated_adjoint_fits")):
@@ -510,11 +558,34 @@ class TruncatedSigKernel:
             return False
         return True
 
-    def _lifted_levels(self, X, Y, static_kernel, L, order, paired):
+    def _points_adjoint_serves(self, X, Y, L, order, paired, sym):
+        """points_adjoint=True applies: point tensors on a HIP device with a gradient pending, order 1, no empty batch, the forward in the
+        points mode's scope on (X, Y) or (Y, X), and every side that needs a gradient in the points-adjoint mode's, its slab in the workspace"""
+        if not (self.points_adjoint and _on_hip(X) and order == 1 and min(X.shape[0], Y.shape[0]) > 0):
+            return False
+        if not (torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad)):
+            return False
+        be = _lib.get_backend()
+        if not (hasattr(be, "truncated_levels") and hasattr(be, "truncated_points_adjoint_fits")):
+            return False
+        (A, M, D), (B, N), es = X.shape, Y.shape[:2], X.element_size()
+        if be.route(_lib.OP_TRUNCATED_RBF, 1, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
+            return False
+        if X.requires_grad and not be.truncated_points_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
+            return False
+        if Y.requires_grad and not sym and not be.truncated_points_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
+            return False
+        return True
+
+    def _lifted_levels(self, X, Y, static_kernel, L, order, paired, sym=False):
         """the level terms of the POINTS X, Y under `static_kernel`: the HIP kernel's points mode for an RBFKernel where it serves (a HIP
-        device, no gradient pending, sk_route_query(SK_OP_TRUNCATED_RBF) on (X, Y) or (Y, X)), else the restatement on the lifted G"""
+        device, sk_route_query(SK_OP_TRUNCATED_RBF) on (X, Y) or (Y, X), and no gradient pending -- or points_adjoint=True and
+        _points_adjoint_serves: _LiftedLevels), else the restatement on the lifted G"""
         param = static_kernel.sigma if type(static_kernel) is RBFKernel else None
-        if param is not None and X.is_cuda and not _needs_grad(X, Y, param) and min(X.shape[0], Y.shape[0]) > 0:
+        if param is not None and not isinstance(param, torch.Tensor) and float(param) > 0 and self._points_adjoint_serves(X, Y, L, order, paired, sym):
+            Xc = X.contiguous()
+            return _LiftedLevels.apply(Xc, Xc if Y is X else Y.contiguous(), L, float(param), paired, sym, self.workspace_bytes)
+        if param is not None and _on_hip(X) and not _needs_grad(X, Y, param) and min(X.shape[0], Y.shape[0]) > 0:
             be = _lib.get_backend()
             if hasattr(be, "truncated_levels") and be.route(_lib.OP_TRUNCATED_RBF, order, X.shape[2], X.shape[1], Y.shape[1], L, False,
                                                             X.element_size()) != _lib.ROUTE_STREAM:
@@ -536,7 +607,7 @@ class TruncatedSigKernel:
         if sym and Y is not X:
             raise ValueError("sym=True needs Y is X")
         if static_kernel is not None and type(static_kernel) is not LinearKernel:
-            return self._lifted_levels(X, Y, static_kernel, L, order, paired)
+            return self._lifted_levels(X, Y, static_kernel, L, order, paired, sym)
         dx = X[:, 1:] - X[:, :-1]
         dy = dx if Y is X else Y[:, 1:] - Y[:, :-1]
         if self._hip_serves(dx, dy, L, order, paired, sym):
