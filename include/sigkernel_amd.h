@@ -63,7 +63,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -130,6 +130,12 @@ const char *sk_cost_note(int which);
                                  SK_OP_TRUNCATED_RBF's FUSED scope with path dim <= 8 (order 1, 2 <= M <= 128, N >= 2, 8 x ceil16(N) <= 2048);
                                  SK_ROUTE_STREAM otherwise = autograd of the host layer's torch restatement.  Never swapped: the second
                                  batch's gradient is the same query on (N, M). */
+#define SK_OP_TRUNCATED_LONG 8 /* truncated_sig_kernel at order 1 on paths of ANY length (kind, dyadic, M, N as SK_OP_TRUNCATED: steps):
+                                 SK_ROUTE_FUSED = sk_truncated_long_*: order 1 (kind 1, or num_levels 1), path dim <= 16, num_levels <= 8,
+                                 1 <= M, N <= 2^20 -- every order-1 shape of SK_OP_TRUNCATED's FUSED scope is inside; SK_ROUTE_FUSED_SWAP = the
+                                 same on (y, x), the result transposed, where that sweep takes fewer steps; SK_ROUTE_STREAM otherwise = the
+                                 host layer's torch restatement.  The host layer asks only where SK_OP_TRUNCATED said STREAM, and only when
+                                 its switch (sigkernel_amd.routes.truncated_long) is on. */
 #define SK_ROUTE_STREAM 0
 #define SK_ROUTE_FUSED 1
 #define SK_ROUTE_FUSED_MB 2
@@ -544,6 +550,23 @@ int sk_truncated_points_f64(const double *Xr, const double *Yt, int64_t A, int64
 int sk_truncated_points_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                             int num_levels, int order, int kind, double param, int paired, int levels, const double *sigma, float *out,
                             void *stream);
+/* The same sweep on paths of ANY length, order 1, forward only (kind 0: Xr / Yt hold steps): the rows go in bands of 128 -- what the last
+ * row of a band hands down is carried to the next band through `slab` -- and the columns in tiles of the wave's y block (2048 / fd).
+ *   sk_truncated_long_plan  plan[0..2] = blocks, slab bytes of ONE block, slab bytes of the launch.  A block's slab is
+ *                           (num_levels - 1) x ceil64(N) doubles, and none when M <= 128 (one band) or num_levels = 1; the blocks are
+ *                           lowered from 8 per CU until their slabs fit workspace_bytes; SK_ERR_UNSUPPORTED when one does not, or outside
+ *                           the scope.  Host only.
+ *   sk_truncated_long_*     Xr, Yt, Mrows, Ncp (a multiple of 16), fd, sigma, order (must resolve to 1), paired, levels and out as
+ *                           sk_truncated_points_* at kind 0; slab / slab_bytes: device scratch of at least one block's slab (the launch
+ *                           takes as many blocks as fit), NULL / 0 where the plan says 0.
+ * Scope: sk_route_query(SK_OP_TRUNCATED_LONG, order, D, M, N, num_levels, ...) != SK_ROUTE_STREAM; else SK_ERR_UNSUPPORTED. */
+int sk_truncated_long_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes, int64_t *plan);
+int sk_truncated_long_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, int order, int paired, int levels, const double *sigma, double *slab, size_t slab_bytes, double *out,
+                          void *stream);
+int sk_truncated_long_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, int order, int paired, int levels, const double *sigma, double *slab, size_t slab_bytes, float *out,
+                          void *stream);
 /* The GRADIENT of the level terms with respect to the first batch, by the same kernel in its adjoint mode (no counterpart in the reference,
  * whose truncated kernel is numpy): for weights w [num_levels][A][B] (device fp64; paired: [num_levels][P]) -- the upstream gradient of level
  * m + 1 of every pair -- the chunks' parts of d / dX sum_pairs sum_m w[m][pair] k_{m+1}(pair) go to Tpart [n_chunks][A][M][8]; the caller

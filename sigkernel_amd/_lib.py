@@ -17,6 +17,7 @@ SK_OK = 0
 # sk_route_query: operations and answers (include/sigkernel_amd.h)
 OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED, OP_TRUNCATED_ADJOINT, OP_TRUNCATED_RBF = 0, 1, 2, 3, 4, 5, 6
 OP_TRUNCATED_RBF_ADJOINT = 7
+OP_TRUNCATED_LONG = 8
 ROUTE_STREAM, ROUTE_FUSED, ROUTE_FUSED_MB, ROUTE_FUSED_MB_SWAP, ROUTE_FUSED_SWAP = 0, 1, 2, 3, 4
 ROUTE_NO_STREAM = 1
 ROUTE_NO_SWAP = 2
@@ -98,6 +99,9 @@ SIGNATURES = {
     "sk_truncated_levels_paired_f32": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp]),
     "sk_truncated_points_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _int, _vp, _vp, _vp]),
     "sk_truncated_points_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _int, _vp, _vp, _vp]),
+    "sk_truncated_long_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
+    "sk_truncated_long_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _sz, _vp, _vp]),
+    "sk_truncated_long_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _sz, _vp, _vp]),
     "sk_truncated_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
     "sk_truncated_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
     "sk_truncated_points_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
@@ -708,6 +712,43 @@ class HipBackend:
     def truncated_levels(self, X, Y, num_levels, order, paired=False, kind=0, param=0.0):
         """The level terms k_0 .. k_L from ONE sweep per pair (the kernel's levels mode): (num_levels + 1, A, B), paired (num_levels + 1, P)."""
         return self._truncated(X, Y, num_levels, order, bool(paired), None, kind, param)
+
+    def truncated_long(self, X, Y, num_levels, sigma, paired=False, workspace_bytes=None, no_swap=False):
+        """The truncated kernel at order 1 on paths of ANY length, by k_trunc_sig<4, 1> in its long mode (sk_truncated_long_*: row bands of
+        128 steps with the carry in a slab, column tiles of the y block): X (A, M, D) / Y (B, N, D) hold steps; sigma: num_levels + 1 host
+        weights -> (A, B), paired (P,); None -> the level terms under a leading axis of num_levels + 1 -- exactly what _truncated returns.
+        A block's slab is (num_levels - 1) x ceil64(N) doubles (none up to 128 steps of X or at one level), all blocks' within
+        `workspace_bytes` (default 1 GiB; the block count is lowered until they fit).  None outside the scope
+        (sk_route_query(SK_OP_TRUNCATED_LONG) != FUSED: FUSED_SWAP is the caller's call on (Y, X)) or when one slab does not fit.
+        no_swap: the sweep on (X, Y) as given also where the one on (Y, X) is shorter (SK_ROUTE_NO_SWAP: measurements, and the tests that
+        hold one orientation's bands and tiles to the reference)."""
+        _dev(X, "X")
+        _dev(Y, "Y")
+        (A, M, D), (B, N), L = X.shape, Y.shape[:2], int(num_levels)
+        if self.route(OP_TRUNCATED_LONG, 1, D, M, N, L, False, X.element_size(), no_swap=bool(no_swap)) != ROUTE_FUSED:
+            return None
+        batches = (A,) if paired else (A, B)
+        out = torch.empty(batches if sigma is not None else (L + 1,) + batches, dtype=X.dtype, device=X.device)
+        if A == 0 or B == 0:
+            return out
+        lib = load()
+        plan = (ctypes.c_int64 * 3)()
+        budget = (1 << 30) if workspace_bytes is None else max(0, int(workspace_bytes))
+        rc = lib.sk_truncated_long_plan(A, B, M, N, D, L, int(bool(paired)), budget, ctypes.cast(plan, ctypes.c_void_p))
+        if rc == 2:
+            return None
+        _check(rc, "sk_truncated_long_plan")
+        slab_bytes = int(plan[2])
+        fd, Ncp = _truncated_staging(D, N)
+        weights = None if sigma is None else (ctypes.c_double * (L + 1))(*[float(v) for v in sigma])
+        with _device(X.device):
+            Xr, Yt = _prep_pair(X, Y, False, 1.0, M, Ncp, fd)
+            slab = torch.empty(slab_bytes // 8, dtype=torch.float64, device=X.device) if slab_bytes else None
+            rc = getattr(lib, "sk_truncated_long_" + _suffix(X))(_ptr(Xr), _ptr(Yt), A, B, M, M, N, Ncp, D, fd, L, 1, int(bool(paired)),
+                                                                 int(sigma is None), weights, _ptr(slab) if slab is not None else None,
+                                                                 slab_bytes, _ptr(out), _stream(X))
+        _check(rc, "sk_truncated_long")
+        return out
 
     def _adjoint_fits(self, op, plan_name, A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size):
         """route `op` says FUSED and one block's slab fits `workspace_bytes`, by the plan entry point `plan_name`"""

@@ -22,6 +22,11 @@ the same with its SK_* knobs, sk_abi.hip):
                          faster default (sk_route_query with SK_ROUTE_NO_STREAM)
     SK_NO_FUSED_PREFIX   compute_Gram_prefixes / compute_kernel_prefixes never through the fused prefix kernel: increments in HBM, the
                          streaming solver's full grid, sliced (what every shape outside that kernel's scope takes anyway)
+    SK_TRUNCATED_LONG    opt-in (every other switch takes a route away; this one adds one): truncated_sig_kernel, its paired and levels
+                         forms and TruncatedSigKernel on its plain kernel take the HIP kernel's LONG mode (sk_route_query with
+                         SK_OP_TRUNCATED_LONG: order 1, any number of steps) where the plain launch declined both orientations and no
+                         gradient is pending -- paths beyond 128 steps, which otherwise take the torch restatement.  Off by default:
+                         every call then does what it did before the mode existed
 
 A running process flips them through the attributes of `sigkernel_amd.routes` (tests: monkeypatch.setattr), or calls
 `routes.reload()` after changing the environment."""
@@ -30,7 +35,7 @@ import os
 _ENV = {"no_fused_rbf": "SK_NO_FUSED_RBF", "no_fused_mb": "SK_NO_FUSED_MB", "no_fused_adjoint": "SK_NO_FUSED_ADJOINT",
         "no_fused_deriv": "SK_NO_FUSED_DERIV", "no_stream": "SK_NO_STREAM", "no_mmd_streams": "SK_NO_MMD_STREAMS",
         "no_merged_loss": "SK_NO_MERGED_LOSS", "no_loss_launch": "SK_NO_LOSS_LAUNCH", "no_adjoint_swap": "SK_NO_ADJOINT_SWAP",
-        "no_fused_prefix": "SK_NO_FUSED_PREFIX"}
+        "no_fused_prefix": "SK_NO_FUSED_PREFIX", "truncated_long": "SK_TRUNCATED_LONG"}
 
 
 class Routes:

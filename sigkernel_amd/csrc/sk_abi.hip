@@ -171,15 +171,20 @@ int solve_prefix_at(int kind, const double *Xr, const double *Yt, int64_t A, int
 // the truncated signature kernel (sk_truncated.hip), every mode of its one launch; argument checks before any HIP call.  paired != 0: the
 // A pairs (x_p, y_p), B ignored; levels != 0: the level terms of every pair, sigma not read -- and only then may it be null; kind 1: the
 // RBF lift on POINTS with param = 1 / sigma
+// long_mode: the LONG mode (kind 0: steps; order 1, any length) with its slab
 template <typename TO>
 int truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int num_levels,
-              int order, const double *sigma, TO *out, void *stream, int paired, int levels, int kind = 0, double param = 0.0) {
+              int order, const double *sigma, TO *out, void *stream, int paired, int levels, int kind = 0, double param = 0.0,
+              bool long_mode = false, double *slab = nullptr, size_t slab_bytes = 0) {
     if (paired) B = A;
-    if ((kind != 0 && kind != 1) || (kind == 1 && (!(param > 0.0) || !(param < 1e300)))) return SK_ERR_BAD_ARG;
+    if ((kind != 0 && kind != 1) || (long_mode && kind) || (kind == 1 && (!(param > 0.0) || !(param < 1e300)))) return SK_ERR_BAD_ARG;
     if (D < 1 || !Xr || !Yt || !out || (!sigma && !levels) || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N ||
-        fd < D)
+        fd < D || (slab_bytes && !slab))
         return SK_ERR_BAD_ARG;
     if (A == 0 || B == 0) return SK_OK;
+    if (long_mode)
+        return launch_truncated_long<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream, paired, levels,
+                                         slab, slab_bytes);
     return launch_truncated<TO>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, (hipStream_t)stream, paired, levels, kind,
                                 param);
 }
@@ -253,8 +258,8 @@ int device_cu_count() {
 
 extern "C" {
 
-// (340 still: sk_truncated_levels_{,paired_}{f64,f32}, sk_truncated_adjoint and its plan, sk_truncated_points_{f64,f32} and SK_OP_TRUNCATED_RBF
-// are additions, no exported signature changed)
+// (340 still: sk_truncated_levels_{,paired_}{f64,f32}, sk_truncated_adjoint and its plan, sk_truncated_points_{f64,f32} and SK_OP_TRUNCATED_RBF,
+// sk_truncated_long_{f64,f32}, its plan and SK_OP_TRUNCATED_LONG are additions, no exported signature changed)
 // 340: sk_static_increments_* serve any path dim (D > 32: k_static_wide_mfma); sk_static_adjoint_* kind 1 with D > 32 writes the first
 // pass H [P][M][ldh] of the rbf chain rule instead of dL/dX
 // 330 (round 6): sk_linear_adjoint_fused_f64 takes ypart / ypart_doubles / ycols_out (the second-argument sums, route FUSED_SWAP)
@@ -513,6 +518,26 @@ int sk_truncated_points_f64(const double *Xr, const double *Yt, int64_t A, int64
 int sk_truncated_points_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                             int num_levels, int order, int kind, double param, int paired, int levels, const double *sigma, float *out, void *stream) {
     return truncated<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, paired, levels, kind, param);
+}
+int sk_truncated_long_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes, int64_t *plan) {
+    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
+    size_t block = 0;
+    const int rc = truncated_long_plan(A, B, M, N, D, num_levels, paired, workspace_bytes, plan, &block);
+    if (rc == SK_OK) {
+        plan[1] = (int64_t)block;
+        plan[2] = plan[0] * (int64_t)block;
+    }
+    return rc;
+}
+int sk_truncated_long_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, int order, int paired, int levels, const double *sigma, double *slab, size_t slab_bytes, double *out,
+                          void *stream) {
+    return truncated<double>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, paired, levels, 0, 0.0, true, slab, slab_bytes);
+}
+int sk_truncated_long_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, int order, int paired, int levels, const double *sigma, double *slab, size_t slab_bytes, float *out,
+                          void *stream) {
+    return truncated<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, paired, levels, 0, 0.0, true, slab, slab_bytes);
 }
 int sk_truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes, int64_t *plan) {
     if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;

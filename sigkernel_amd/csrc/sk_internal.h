@@ -215,6 +215,17 @@ int launch_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t 
                                     int L, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes,
                                     hipStream_t s, int paired);
 bool truncated_points_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_RBF_ADJOINT rule of sk_route_query
+// The LONG mode of k_trunc_sig<TR_OMAX, 1> (order 1, forward only): any number of steps on either side -- the rows in bands of 128 with the
+// last row's hand-down carried through `slab`, the columns in tiles of the y block.  paired, levels, sigma, out as launch_truncated's at
+// kind 0.  The plan gives the blocks and ONE block's slab bytes, (L - 1) x ceil64(N) doubles (0 with one band or one level), the blocks
+// lowered from 8 per CU until their slabs fit `workspace`; SK_ERR_UNSUPPORTED outside the scope or when one slab does not fit.
+int truncated_long_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *blocks, size_t *block_bytes);
+template <typename TO>
+int launch_truncated_long(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
+                          int order, const double *sigma, TO *out, hipStream_t s, int paired, int levels, double *slab, size_t slab_bytes);
+bool truncated_long_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_LONG rule of sk_route_query
+int truncated_long_logw(int M, int Ncp, int fd, int paired);           // log2 of the lanes of a pair's group in that mode
+int64_t truncated_long_steps(int D, int M, int N);                     // sk_route.hip: the lane-steps of a pair in that mode
 
 // ---- sk_loss.hip: the glue of the loss wrappers (compute_mmd / scoring rules) as single launches ----
 template <typename T>

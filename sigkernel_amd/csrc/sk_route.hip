@@ -150,6 +150,16 @@ const char *cost_name(int which) { return which >= 0 && which < N_COSTS ? COSTS[
 const char *cost_note(int which) { return which >= 0 && which < N_COSTS ? COSTS[which].note : nullptr; }
 double cost_by_name(const char *name) { return cost(name); }
 
+// THE step count of the long mode of k_trunc_sig (sk_truncated.hip: trunc_long), per pair and in lane-steps -- what its loops execute for M
+// rows and N columns at path dim D: every band of 2 W rows sweeps every tile of Tc = 2048 / fd columns in (columns + W - 1) steps (the skew
+// drains at a tile's end), and a group of W lanes is W / 64 of the wave that takes the step.
+int64_t truncated_long_steps(int D, int M, int N) {
+    const int fd = D <= 8 ? 8 : 16, Ncp = (N + 15) / 16 * 16;
+    const int W = 1 << truncated_long_logw(M, Ncp, fd, 0), Tc = 2048 / fd;
+    const int64_t bands = (M + 2 * W - 1) / (2 * W), tiles = (N + Tc - 1) / Tc;
+    return bands * (N + tiles * (W - 1)) * W;
+}
+
 int route_query(int op, int kind, int D, int M, int N, int d, int naive, int elem_size, int flags) {
     const bool may_stream = !(flags & SK_ROUTE_NO_STREAM);
     if (op == SK_OP_TRUNCATED) {
@@ -182,6 +192,14 @@ int route_query(int op, int kind, int D, int M, int N, int d, int naive, int ele
         // mode of k_trunc_sig<4, 1> (truncated_points_adjoint_in_scope is the rule), STREAM = autograd of the torch restatement.  Never swapped.
         if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
         return truncated_points_adjoint_in_scope(D, M, N, d, kind) ? SK_ROUTE_FUSED : SK_ROUTE_STREAM;
+    }
+    if (op == SK_OP_TRUNCATED_LONG) {
+        // truncated_sig_kernel at order 1 on paths of ANY length (kind, d, M, N as SK_OP_TRUNCATED): FUSED = the long mode of k_trunc_sig<4, 1>
+        // (truncated_long_in_scope is the rule), FUSED_SWAP = the same on (y, x) where that sweep takes fewer steps; STREAM = the torch restatement.
+        if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
+        if (!truncated_long_in_scope(D, M, N, d, kind)) return SK_ROUTE_STREAM;
+        if ((flags & SK_ROUTE_NO_SWAP) || truncated_long_steps(D, M, N) <= truncated_long_steps(D, N, M)) return SK_ROUTE_FUSED;
+        return SK_ROUTE_FUSED_SWAP;
     }
     if ((kind != 0 && kind != 1) || D < 1 || D > 16 || M < 2 || N < 2 || d < 0 || d > 2) return SK_ROUTE_STREAM;
     if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;

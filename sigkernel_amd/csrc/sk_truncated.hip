@@ -40,6 +40,9 @@
 // POINTS-ADJOINT mode (TruncParams::adjoint = 3, launch-time and wave-uniform; order 1, fd = 8; Gram and paired): the gradient of a weighted
 // sum of the LIFTED kernel's level terms with respect to the points of x -- trunc_points_adjoint below, the two phases of trunc_adjoint on
 // the grid of points with the chain rule through kap; hosted by the <TR_OMAX, 1> instance beside trunc_points.
+// LONG mode (TruncParams::adjoint = 4, launch-time and wave-uniform; order 1, fd = 8 or 16; Gram, paired and levels; forward only): paths of
+// any length -- trunc_long below: the rows in bands of 128 with the hand-down of a band's last row carried through HBM, the columns in tiles of
+// the y block with the row sums kept in registers; hosted by the <TR_OMAX, 1> instance beside the points modes.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
 // order (1: one plane per level, or TR_OMAX) and the rows per lane.
 #include "sk_wave_common.h"
@@ -63,6 +66,8 @@ struct TruncParams {
     // ADJOINT mode (order 1, fd = 8: trunc_adjoint below).  `out` is not used.
     int adjoint;        // 0: a forward launch; 1: dX of sum_pairs sum_m w[m][pair] k_m; 2: the POINTS mode, a forward launch on points (below);
                         // 3: the POINTS-ADJOINT mode, 1 for the lifted kernel (slab: L planes, the last one g)
+                        // 4: the LONG mode, a forward launch on any number of steps (trunc_long; slab: [blocks][L - 1][ceil64(N)], the carry
+                        // between a pair's row bands)
     int64_t n_chunks;   // Gram: the B pairs of a row tile go to this many positions; paired: 1
     const double *w;    // [L][A][B], paired [L][A]: the weight of level m + 1 of every pair
     double *Tpart;      // [n_chunks][A][M][8]: the chunks' parts of dX, summed by the caller
@@ -612,6 +617,204 @@ __device__ __forceinline__ void trunc_points_adjoint(const TruncParams &prm, dou
     }
 }
 
+// lane `l` (wave-uniform) of v, to every lane
+__device__ __forceinline__ double lane_read(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
+// LONG mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 4, launch-time and wave-uniform; order 1, two rows per lane, fd = 8 or 16; Gram,
+// paired and levels; forward only): ANY number of steps on either side.  The node's recursion is the order-1 step loop's (phase 1 of
+// trunc_adjoint with the sums kept); an order-1 level is G times the exclusive 2-D prefix of the level below, and that prefix splits exactly:
+//   ROW BANDS  the rows go 2 W at a time (bands exist only beyond 128 rows: W = 64, one pair per wave; up to 128 rows the lane groups are
+//              the plain launch's).  What the last row of a band would hand down at column j -- qin[s] after its node has joined it, the
+//              exclusive prefix of level s + 1 at the first row of the next band -- is the CARRY: lane 63 stores it to the block's slab in HBM,
+//              slab[s Ns + j] (Ns = ceil64(N); L - 1 planes), and in the next band lane 0 takes it where the other loops put 0.0.  Band 0 of
+//              every position takes zeros.  Only the wave that wrote the slab reads it: program order and a vmcnt wait at a band's end are
+//              all the ordering there is.  In place: the columns of a band come in 64 at a time, one load per level by all lanes, issued 64
+//              steps before their first use (column j is read at step j - 64 at the earliest and overwritten at step j + 63), and lane 0
+//              takes its step's value by a lane read -- no load is waited for in the step that uses it.
+//              rowS restarts per band; acc runs on; the level totals of the levels mode add up per lane across the bands (in LDS, behind the y tiles).
+//   COLUMN TILES  the y block of the wave holds Tc = min(Ncp, 2048 / fd) columns; a longer second side goes tile by tile with rowS kept in
+//              registers -- at order 1 nothing else crosses a tile boundary.  The skew is drained at a tile's end and restarted: W - 1 idle
+//              steps per tile.
+// Padding rows and columns have G = 0, and every carry value a lane can see is finite (columns beyond N are loaded as zeros).
+__device__ __forceinline__ void trunc_long(const TruncParams &prm, double *ylds) {
+    constexpr int NS = TR_LMAX - 1;
+    const int lane = threadIdx.x;
+    const int W = 1 << prm.logW, G = WAVE >> prm.logW;
+    const int lam = lane & (W - 1), grp = lane >> prm.logW;
+    const int N = prm.N, Ncp = prm.Ncp, L = prm.L, fd = prm.fd;
+    const bool wide = fd > 8;
+    const bool paired = prm.paired != 0;
+    const int Tc = Ncp < TR_LDS_DOUBLES / fd ? Ncp : TR_LDS_DOUBLES / fd;
+    const int Ns = (N + 63) & ~63;
+    const int bands = (prm.M + 2 * W - 1) / (2 * W);
+    double *slab = prm.slab + (int64_t)blockIdx.x * (L - 1) * Ns;       // read and written only with more than one band
+    // the lane's level totals over the bands (levels mode), behind the y tiles: 14 registers the step loop does not have; no other lane
+    // reads them
+    double *totl = ylds + (paired ? G : 1) * fd * Tc + lane;
+    for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
+        int64_t a, b;
+        int nblk = 1;
+        if (paired) {
+            b = pos * G;
+            a = b + grp;
+            nblk = prm.A - b < G ? (int)(prm.A - b) : G;
+        } else {
+            const int64_t at = pos / prm.B;
+            b = pos - at * prm.B;
+            a = at * G + grp;
+        }
+        const bool live = a < prm.A;
+        const double *yl = ylds + ((paired && live) ? grp * fd * Tc : 0);
+        const double *yb = prm.Yt + b * (int64_t)fd * Ncp;
+        double rowS[2][NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) totl[s * WAVE] = 0.0;
+        double acc = 0.0;
+        for (int band = 0; band < bands; ++band) {
+            const bool cin = band > 0, cout = band + 1 < bands;
+            double xr[2][16];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int row = (band * W + lam) * 2 + r;
+                const bool ok = live && row < prm.M;
+                const double *xp = prm.Xr + ((ok ? a : 0) * (int64_t)prm.Mrows + (ok ? row : 0)) * fd;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) xr[r][k] = (ok && k < fd) ? xp[k] : 0.0;
+            }
+            double qio[NS], cbuf[NS], cnext[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) qio[s] = rowS[0][s] = rowS[1][s] = cbuf[s] = cnext[s] = 0.0;
+            for (int c0 = 0; c0 < N; c0 += Tc) {
+                const int nt = N - c0 < Tc ? N - c0 : Tc;
+                if (cin) {      // the carry of the tile's first 64 columns
+#pragma unroll
+                    for (int s = 0; s < NS; ++s)
+                        if (s < L - 1) cnext[s] = c0 + lane < N ? slab[s * Ns + c0 + lane] : 0.0;
+                }
+                __syncthreads();
+                for (int row = 0; row < nblk * fd; ++row)
+                    for (int c = lane; c < Tc; c += WAVE) ylds[row * Tc + c] = c0 + c < Ncp ? yb[(int64_t)row * Ncp + c0 + c] : 0.0;
+                __syncthreads();
+                const int steps = nt + W - 1;
+                for (int t0 = 0; t0 < steps; t0 += 64) {
+                    if (cin) {  // the columns t0 .. t0 + 63 of the tile, asked for a chunk ago; ask for the next ones
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) cbuf[s] = cnext[s];
+                        if (t0 + 64 < nt) {
+                            const int col = c0 + t0 + 64 + lane;
+#pragma unroll
+                            for (int s = 0; s < NS; ++s)
+                                if (s < L - 1) cnext[s] = col < N ? slab[s * Ns + col] : 0.0;
+                        }
+                    }
+                    const int t1 = t0 + 64 < steps ? t0 + 64 : steps;
+                    for (int t = t0; t < t1; ++t) {
+                        int Ls = L;
+                        asm volatile("" : "+s"(Ls));      // the level guards of a step are scalar compares of its own
+                        const int j = t - lam;
+                        const bool act = (unsigned)j < (unsigned)nt;
+                        const int jc = act ? j : 0;
+                        double qin[NS];
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) {
+                            const double v = s < Ls - 1 ? dpp_shr1_zero(qio[s]) : 0.0;
+                            const double c = s < Ls - 1 ? lane_read(cbuf[s], t - t0) : 0.0;
+                            qin[s] = lam == 0 ? c : v;
+                        }
+                        // the column of y in two halves of eight: the second half reuses the registers of the first (the sums are the plain loop's, term by term)
+                        double yv[8], gr[2] = {0.0, 0.0};
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) yv[k] = yl[k * Tc + jc];
+                        asm volatile("s_waitcnt lgkmcnt(0)"
+                                     : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) gr[r] = fma(xr[r][k], yv[k], gr[r]);
+                        if (wide) {
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) yv[k] = yl[(k + 8) * Tc + jc];
+                            asm volatile("s_waitcnt lgkmcnt(0)"
+                                         : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                                for (int k = 0; k < 8; ++k) gr[r] = fma(xr[r][k + 8], yv[k], gr[r]);
+                        }
+#pragma unroll
+                        for (int r = 0; r < 2; ++r) {
+                            double g = gr[r];
+                            g = act ? g : 0.0;
+                            double prev = g;
+#pragma unroll
+                            for (int lv = 1; lv <= TR_LMAX; ++lv)
+                                if (lv <= Ls) {
+                                    acc = fma(prm.sigma[lv], prev, acc);
+                                    if (lv < TR_LMAX && lv < Ls) {
+                                        const int s = lv - 1;
+                                        const double next = g * qin[s];
+                                        qin[s] = qin[s] + rowS[r][s];
+                                        rowS[r][s] += prev;
+                                        prev = next;
+                                    }
+                                }
+                        }
+                        if (cout && lam == W - 1 && act) {      // more than one band: W = 64, the wave's last lane
+#pragma unroll
+                            for (int s = 0; s < NS; ++s)
+                                if (s < Ls - 1) slab[s * Ns + c0 + j] = qin[s];
+                        }
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) qio[s] = qin[s];
+                    }
+                }
+            }
+            {   // (read, wait in one piece, write: the build's hazard lint holds every LDS read of this unit to a full wait)
+                double tv[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) tv[s] = totl[s * WAVE];
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]), "+v"(tv[3]), "+v"(tv[4]), "+v"(tv[5]), "+v"(tv[6]));
+#pragma unroll
+                for (int s = 0; s < NS; ++s) totl[s * WAVE] = tv[s] + (rowS[0][s] + rowS[1][s]);
+            }
+            // the band's carry is in memory before the next band asks for it
+            if (cout) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        for (int off = 1; off < W; off <<= 1) acc += __shfl_xor(acc, off, WAVE);
+        if (prm.levels) {       // the weights are (0, .., 0, 1): acc is level L, totl[s] the lane's total of level s + 1
+            const int64_t plane = paired ? prm.A : prm.A * prm.B;
+            const int64_t o = paired ? a : a * prm.B + b;
+            const bool st = lam == 0 && live;
+            if (st) {
+                if (prm.out_f32) {
+                    reinterpret_cast<float *>(prm.out)[o] = 1.0f;
+                    reinterpret_cast<float *>(prm.out)[L * plane + o] = (float)acc;
+                } else {
+                    reinterpret_cast<double *>(prm.out)[o] = 1.0;
+                    reinterpret_cast<double *>(prm.out)[L * plane + o] = acc;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (s < L - 1) {
+                    double v = totl[s * WAVE];
+                    for (int off = 1; off < W; off <<= 1) v += __shfl_xor(v, off, WAVE);
+                    if (st) {
+                        if (prm.out_f32) reinterpret_cast<float *>(prm.out)[(s + 1) * plane + o] = (float)v;
+                        else reinterpret_cast<double *>(prm.out)[(s + 1) * plane + o] = v;
+                    }
+                }
+        } else if (lam == 0 && live) {
+            const double v = prm.sigma[0] + acc;
+            const int64_t o = paired ? a : a * prm.B + b;
+            if (prm.out_f32) reinterpret_cast<float *>(prm.out)[o] = (float)v;
+            else reinterpret_cast<double *>(prm.out)[o] = v;
+        }
+    }
+}
+
 template <int OM, int RC>
 __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     extern __shared__ __attribute__((aligned(16))) double ylds[];   // [fd][Ncp]; paired: [G][fd][Ncp], one block per lane group
@@ -631,8 +834,9 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
         }
     }
     if constexpr (OM > 1) {
-        if (prm.adjoint) {      // 2, the POINTS mode, and 3, its adjoint: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
+        if (prm.adjoint) {      // 2, the POINTS mode, 3, its adjoint, and 4, the LONG mode: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
             if (prm.adjoint == 3) trunc_points_adjoint(prm, ylds);
+            else if (prm.adjoint == 4) trunc_long(prm, ylds);
             else trunc_points(prm, ylds);
             return;
         }
@@ -1017,6 +1221,88 @@ int launch_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t 
     return check_launch();
 }
 
+// THE scope of the long mode (the SK_OP_TRUNCATED_LONG rule of sk_route_query): order 1 and what the staging and the unrolled level loop
+// hold; the steps of either side are bounded only by the indices (2^20: a slab plane, a row of Yt).  Every order-1 shape of
+// truncated_in_scope is inside.
+bool truncated_long_in_scope(int D, int M, int N, int L, int order) {
+    if (D < 1 || D > 16 || L < 1 || L > TR_LMAX || M < 1 || N < 1 || M > (1 << 20) || N > (1 << 20)) return false;
+    return trunc_order(L, order) == 1;
+}
+
+// lanes of a pair's group in the long mode: 64 beyond 128 rows; paired: every group keeps its own tile of y, so fewer, wider groups until
+// G tiles of Tc = min(Ncp, 2048 / fd) columns fit the wave's 16 KB
+int truncated_long_logw(int M, int Ncp, int fd, int paired) {
+    const int lanes = M > 128 ? 64 : (M + 1) / 2;
+    int logW = 0;
+    while ((1 << logW) < lanes) ++logW;
+    const int Tc = Ncp < TR_LDS_DOUBLES / fd ? Ncp : TR_LDS_DOUBLES / fd;
+    while (paired && (int64_t)(WAVE >> logW) * fd * Tc > TR_LDS_DOUBLES) ++logW;
+    return logW;
+}
+
+namespace {
+struct LongPlan {
+    int logW;
+    int64_t n_pos, blocks;
+    size_t block_bytes;     // a block's slab: L - 1 planes of ceil64(N) doubles; none with one band or one level
+};
+bool plan_long(int64_t A, int64_t B, int M, int N, int Ncp, int fd, int L, int paired, size_t workspace, LongPlan *pl) {
+    pl->logW = truncated_long_logw(M, Ncp, fd, paired);
+    const int G = WAVE >> pl->logW;
+    pl->n_pos = paired ? (A + G - 1) / G : (A + G - 1) / G * B;
+    pl->blocks = (int64_t)device_cu_count() * 8;
+    if (pl->blocks > pl->n_pos) pl->blocks = pl->n_pos;
+    pl->block_bytes = M > 128 ? (size_t)(L - 1) * (size_t)((N + 63) / 64 * 64) * sizeof(double) : 0;
+    if (pl->block_bytes) {
+        const int64_t fit = (int64_t)(workspace / pl->block_bytes);
+        if (fit < 1) return false;
+        if (pl->blocks > fit) pl->blocks = fit;
+    }
+    return true;
+}
+}  // namespace
+
+int truncated_long_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *blocks, size_t *block_bytes) {
+    if (!truncated_long_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    LongPlan pl;
+    if (!plan_long(A, paired ? A : B, M, N, (N + 15) / 16 * 16, trunc_fd(D), L, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
+    *blocks = pl.blocks;
+    *block_bytes = pl.block_bytes;
+    return SK_OK;
+}
+
+// the long mode's launch: the modes of launch_truncated at kind 0 (paired, levels), order 1; slab: what truncated_long_plan asks for
+template <typename TO>
+int launch_truncated_long(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
+                          int order, const double *sigma, TO *out, hipStream_t s, int paired, int levels, double *slab, size_t slab_bytes) {
+    if (!truncated_long_in_scope(D, M, N, L, order)) return SK_ERR_UNSUPPORTED;
+    if (fd != trunc_fd(D) || Ncp < N || Ncp % 16 || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
+    LongPlan pl;
+    if (!plan_long(A, B, M, N, Ncp, fd, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
+    TruncParams prm;
+    prm.Xr = Xr; prm.Yt = Yt; prm.out = out;
+    prm.A = A; prm.B = B;
+    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
+    prm.order = 1;
+    prm.out_f32 = sizeof(TO) == 4;
+    prm.paired = paired != 0;
+    prm.levels = levels != 0;
+    prm.param = 0.0;
+    prm.adjoint = 4; prm.n_chunks = 1; prm.w = nullptr; prm.Tpart = nullptr; prm.slab = slab;
+    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = levels ? (m == L ? 1.0 : 0.0) : (m <= L ? sigma[m] : 0.0);
+    prm.logW = pl.logW;
+    prm.n_pos = pl.n_pos;
+    const int G = WAVE >> pl.logW;
+    const int Tc = Ncp < TR_LDS_DOUBLES / fd ? Ncp : TR_LDS_DOUBLES / fd;
+    const size_t lds = sizeof(double) * ((size_t)fd * Tc * (paired ? G : 1) + (size_t)WAVE * (TR_LMAX - 1));   // the y tiles; the lanes' level totals
+    SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)pl.blocks), dim3(WAVE), lds, s, prm);
+    return check_launch();
+}
+
+template int launch_truncated_long<double>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
+                                           double *, hipStream_t, int, int, double *, size_t);
+template int launch_truncated_long<float>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
+                                          float *, hipStream_t, int, int, double *, size_t);
 template int launch_truncated<double>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,
                                       double *, hipStream_t, int, int, int, double);
 template int launch_truncated<float>(const double *, const double *, int64_t, int64_t, int, int, int, int, int, int, int, int, const double *,

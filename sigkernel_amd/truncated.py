@@ -19,6 +19,14 @@ Two routes, chosen by ``sk_route_query(SK_OP_TRUNCATED, ...)``:
 * ``_truncated_torch``: the same recursion as ``cumsum`` and slicing on the paths' device, tiled over rows of X by ``workspace_bytes``;
   differentiable by autograd -- it serves every input that requires grad and every shape outside the kernel's scope.
 
+A third, OPT-IN route serves order 1 beyond that scope -- more than 128 steps on both sides, or a second side beyond the wave's y block:
+the kernel's LONG mode (``HipBackend.truncated_long``, ``sk_route_query(SK_OP_TRUNCATED_LONG, ...)``: the rows in bands of 128 with the
+last row's hand-down carried through a slab in HBM, the columns in tiles of the y block; any number of steps, path dim <= 16, forward
+only).  With ``sigkernel_amd.routes.truncated_long`` on (environment ``SK_TRUNCATED_LONG``), the three functions and
+``TruncatedSigKernel`` on its plain kernel ask it where the plain launch declined both orientations, the order is 1 and no gradient is
+pending; the slabs stay within ``workspace_bytes``.  The switch is off by default -- every call then does what it did -- and flipping
+it is left to a later change.
+
 ``truncated_sig_kernel_paired`` is the same kernel on P pairs ``(X[p], Y[p])``: the same two routes (the HIP kernel in its paired mode, one
 pair per lane group; the torch restatement tiled over pairs), the same scope, and nothing of size P x P on either.  It is what
 ``truncated_sig_kernel(..., normalize=True)`` -- ``K[a, b] / sqrt(k(x_a, x_a) k(y_b, y_b))`` -- takes its two diagonals from.
@@ -46,6 +54,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._routes import routes
 from .sigkernel import _functional
 from .static_kernels import LinearKernel, RBFKernel
 
@@ -249,6 +258,19 @@ def _hip_serves(be, method, X, Y, sigma):
     return not _needs_grad(X, Y, sigma) and min(X.shape[0], X.shape[1], Y.shape[0], Y.shape[1]) > 0 and hasattr(be, method)
 
 
+def _long_serves(be, X, Y, sigma, order):
+    """the kernel's LONG mode may be asked (after the plain launch declined both orientations): the opt-in switch routes.truncated_long is
+    on, order 1, no gradient pending, no empty axis, and a backend that has the method (the mode is forward only)"""
+    return bool(routes.truncated_long) and order == 1 and _hip_serves(be, "truncated_long", X, Y, sigma)
+
+
+def _long(be, X, Y, num_levels, weights, paired, workspace_bytes):
+    """HipBackend.truncated_long on (X, Y), or on (Y, X) where the route query says that sweep is the shorter one; paired batches in
+    _chunked's runs; `weights` None: the level terms.  None where it declines (one block's slab beyond the workspace)."""
+    call = lambda x, y: be.truncated_long(x, y, num_levels, weights, paired, workspace_bytes)
+    return _routed(_chunked(call, workspace_bytes, 0 if weights is not None else 1) if paired else call, X.detach(), Y.detach(), not paired)
+
+
 def truncated_sig_kernel_paired(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=None):
     """The truncated signature kernel of the pairs (X[p], Y[p]): X (P, M, D) and Y (P, N, D) hold STEPS, the result is (P,) with
     ``out[p] = truncated_sig_kernel(X[p:p+1], Y[p:p+1], ...)[0, 0]`` -- the diagonal of the matrix without the matrix.  ``num_levels``,
@@ -266,6 +288,8 @@ def truncated_sig_kernel_paired(X, Y, num_levels, sigma=1., order=-1, workspace_
         weights = sig.detach().double().cpu().tolist()
         call = lambda x, y: be.truncated_paired(x, y, num_levels, weights, order)
         k = _routed(_chunked(call, workspace_bytes, 0), X.detach(), Y.detach(), False)
+    if k is None and _long_serves(be, X, Y, sigma, order):
+        k = _long(be, X, Y, num_levels, sig.detach().double().cpu().tolist(), True, workspace_bytes)
     if k is None:
         k = _truncated_paired_torch(X, Y, num_levels, sig, order, workspace_bytes)
     return k.cpu().numpy() if as_numpy else k
@@ -299,6 +323,8 @@ def truncated_sig_kernel(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=N
     if _hip_serves(be, "truncated_gram", X, Y, sigma):
         weights = sig.detach().double().cpu().tolist()
         K = _routed(lambda x, y: be.truncated_gram(x, y, num_levels, weights, order), X.detach(), Y.detach(), True)
+    if K is None and _long_serves(be, X, Y, sigma, order):
+        K = _long(be, X, Y, num_levels, sig.detach().double().cpu().tolist(), False, workspace_bytes)
     if K is None:
         K = _truncated_torch(X, Y, num_levels, sig, order, workspace_bytes)
     if normalize:
@@ -323,6 +349,8 @@ def truncated_sig_kernel_levels(X, Y, num_levels, order=-1, paired=False, worksp
     if _hip_serves(be, "truncated_levels", X, Y, None):
         call = lambda x, y: be.truncated_levels(x, y, num_levels, order, paired=paired)
         K = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
+    if K is None and _long_serves(be, X, Y, None, order):
+        K = _long(be, X, Y, num_levels, None, paired, workspace_bytes)
     if K is None:
         K = _truncated_levels_torch(X, Y, num_levels, order, paired, workspace_bytes)
     return K.cpu().numpy() if as_numpy else K
@@ -613,6 +641,10 @@ class TruncatedSigKernel:
         if self._hip_serves(dx, dy, L, order, paired, sym):
             dx = dx.contiguous()
             return _TruncatedLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, order, paired, sym, self.workspace_bytes)
+        if _on_hip(dx) and _long_serves(_lib.get_backend(), dx, dy, None, order):     # opt-in: steps beyond the plain launch, no gradient pending
+            lev = _long(_lib.get_backend(), dx.contiguous(), dy.contiguous(), L, None, paired, self.workspace_bytes)
+            if lev is not None:
+                return lev
         return _truncated_levels_torch(dx, dy, L, order, paired, self.workspace_bytes)
 
     def compute_Gram(self, X, Y, sym=False):
