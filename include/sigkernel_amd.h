@@ -63,7 +63,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -136,6 +136,12 @@ const char *sk_cost_note(int which);
                                  same on (y, x), the result transposed, where that sweep takes fewer steps; SK_ROUTE_STREAM otherwise = the
                                  host layer's torch restatement.  The host layer asks only where SK_OP_TRUNCATED said STREAM, and only when
                                  its switch (sigkernel_amd.routes.truncated_long) is on. */
+#define SK_OP_TRUNCATED_LONG_ADJOINT 9 /* the gradient of SK_OP_TRUNCATED_ADJOINT on paths of ANY length (kind, dyadic, M, N as SK_OP_TRUNCATED:
+                                 steps): SK_ROUTE_FUSED = sk_truncated_long_adjoint: order 1 (kind 1, or num_levels 1), path dim <= 8,
+                                 num_levels <= 8, 1 <= M, N <= 2^20 -- every shape of SK_OP_TRUNCATED_ADJOINT's FUSED scope is inside;
+                                 SK_ROUTE_STREAM otherwise = autograd of the host layer's torch restatement.  Never swapped: the gradient goes
+                                 to the rows, and the second batch's is the same query on (N, M).  The host layer asks only where
+                                 SK_OP_TRUNCATED_ADJOINT's route declined, and only for TruncatedSigKernel(long_adjoint=True). */
 #define SK_ROUTE_STREAM 0
 #define SK_ROUTE_FUSED 1
 #define SK_ROUTE_FUSED_MB 2
@@ -567,6 +573,25 @@ int sk_truncated_long_f64(const double *Xr, const double *Yt, int64_t A, int64_t
 int sk_truncated_long_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                           int num_levels, int order, int paired, int levels, const double *sigma, double *slab, size_t slab_bytes, float *out,
                           void *stream);
+/* The gradient of sk_truncated_adjoint (below: w, Tpart, n_chunks, the staging and the reproducibility are its) on paths of ANY length,
+ * order 1, D <= 8: the reverse sweep in the bands and tiles of sk_truncated_long_*.  Per pair, with more than one band of 128 rows, one forward
+ * pass that keeps every band's incoming carry, then the bands from the last to the first: the band's forward sweep again, storing its prefix
+ * factors, and its mirrored sweep, which hands a reverse carry up to the band above and continues the band's rows of dX in Tpart.
+ * A block's slab, in this order (W the lanes of a pair's group: 64 beyond 128 rows; tiles = ceil(N / min(ceil16(N), 256))):
+ *     factors        [num_levels - 1][N + tiles (W - 1)][128] doubles: 1 KB per level and step of ONE band
+ *     forward carry  [bands][num_levels - 1][ceil64(N)] doubles          (only with more than one band; plane 0 is never touched)
+ *     reverse carry  [2][num_levels - 1][ceil64(N)] doubles              (only with more than one band; band k writes half k & 1)
+ *   sk_truncated_long_adjoint_plan  plan[0..3] = n_chunks, blocks, slab bytes of the launch (blocks x one block's), slab bytes of ONE block.
+ *                                   The blocks are lowered from 8 per CU until their slabs fit workspace_bytes; SK_ERR_UNSUPPORTED when one
+ *                                   block's does not, or outside the scope.  Host only.
+ *   sk_truncated_long_adjoint       arguments as sk_truncated_adjoint's, Ncp a multiple of 16; slab / slab_bytes: device scratch of at least
+ *                                   one block's slab (the launch takes as many blocks as fit), may be NULL / 0 at num_levels = 1.
+ * Scope: sk_route_query(SK_OP_TRUNCATED_LONG_ADJOINT, 1, D, M, N, num_levels, ...) == SK_ROUTE_FUSED; else SK_ERR_UNSUPPORTED. */
+int sk_truncated_long_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
+                                   int64_t *plan);
+int sk_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                              int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
+                              int paired);
 /* The GRADIENT of the level terms with respect to the first batch, by the same kernel in its adjoint mode (no counterpart in the reference,
  * whose truncated kernel is numpy): for weights w [num_levels][A][B] (device fp64; paired: [num_levels][P]) -- the upstream gradient of level
  * m + 1 of every pair -- the chunks' parts of d / dX sum_pairs sum_m w[m][pair] k_{m+1}(pair) go to Tpart [n_chunks][A][M][8]; the caller

@@ -18,6 +18,7 @@ SK_OK = 0
 OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED, OP_TRUNCATED_ADJOINT, OP_TRUNCATED_RBF = 0, 1, 2, 3, 4, 5, 6
 OP_TRUNCATED_RBF_ADJOINT = 7
 OP_TRUNCATED_LONG = 8
+OP_TRUNCATED_LONG_ADJOINT = 9
 ROUTE_STREAM, ROUTE_FUSED, ROUTE_FUSED_MB, ROUTE_FUSED_MB_SWAP, ROUTE_FUSED_SWAP = 0, 1, 2, 3, 4
 ROUTE_NO_STREAM = 1
 ROUTE_NO_SWAP = 2
@@ -103,6 +104,8 @@ SIGNATURES = {
     "sk_truncated_long_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _sz, _vp, _vp]),
     "sk_truncated_long_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _sz, _vp, _vp]),
     "sk_truncated_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
+    "sk_truncated_long_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
+    "sk_truncated_long_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
     "sk_truncated_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
     "sk_truncated_points_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
     "sk_truncated_points_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _i64, _vp, _sz,
@@ -754,7 +757,7 @@ class HipBackend:
         """route `op` says FUSED and one block's slab fits `workspace_bytes`, by the plan entry point `plan_name`"""
         if self.route(op, 1, D, M, N, num_levels, False, elem_size) != ROUTE_FUSED:
             return False
-        plan = (ctypes.c_int64 * 3)()
+        plan = (ctypes.c_int64 * 4)()       # (the long adjoint's plan has a fourth entry)
         budget = (1 << 30) if workspace_bytes is None else max(0, int(workspace_bytes))
         rc = getattr(load(), plan_name)(max(1, int(A)), max(1, int(B)), M, N, D, int(num_levels), int(bool(paired)), budget,
                                         ctypes.cast(plan, ctypes.c_void_p))
@@ -783,7 +786,7 @@ class HipBackend:
         if A == 0 or B == 0:
             return torch.zeros(A, M, D, dtype=torch.float64, device=X.device)
         lib = load()
-        plan = (ctypes.c_int64 * 3)()
+        plan = (ctypes.c_int64 * 4)()       # (the long adjoint's plan has a fourth entry)
         budget = (1 << 30) if workspace_bytes is None else max(0, int(workspace_bytes))
         rc = getattr(lib, plan_name)(A, B, M, N, D, L, int(bool(paired)), budget, ctypes.cast(plan, ctypes.c_void_p))
         if rc == 2:
@@ -820,6 +823,21 @@ class HipBackend:
         outside the scope (sk_route_query(SK_OP_TRUNCATED_ADJOINT) != FUSED: order 1, dim <= 8) or when one block's slab does not fit."""
         return self._adjoint(OP_TRUNCATED_ADJOINT, "sk_truncated_adjoint_plan", "sk_truncated_adjoint", (), X, Y, w, num_levels, paired,
                              workspace_bytes)
+
+    def truncated_long_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
+        """whether truncated_long_adjoint serves the shape: SK_OP_TRUNCATED_LONG_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""
+        return self._adjoint_fits(OP_TRUNCATED_LONG_ADJOINT, "sk_truncated_long_adjoint_plan", A, B, M, N, D, num_levels, paired,
+                                  workspace_bytes, elem_size)
+
+    def truncated_long_adjoint(self, X, Y, w, num_levels, paired=False, workspace_bytes=None):
+        """truncated_adjoint's gradient on paths of ANY length, by k_trunc_sig<4, 1> in its long-adjoint mode (sk_truncated_long_adjoint):
+        X, Y, w and the result (A, M, D) in fp64 as there, staged as there.  One launch: per pair the reverse sweep goes through the long
+        mode's row bands of 128 steps, last band first, and its column tiles; a block keeps the prefix factors of ONE band, (num_levels - 1) x
+        (N + tiles x (lanes - 1)) KB, and with more than one band (bands + 2) x (num_levels - 1) x ceil64(N) doubles of carries, all blocks'
+        within `workspace_bytes` (default 1 GiB; the block count is lowered from 8 per CU until they fit, so long paths want more).  None
+        outside the scope (sk_route_query(SK_OP_TRUNCATED_LONG_ADJOINT) != FUSED: order 1, dim <= 8) or when one block's slab does not fit."""
+        return self._adjoint(OP_TRUNCATED_LONG_ADJOINT, "sk_truncated_long_adjoint_plan", "sk_truncated_long_adjoint", (), X, Y, w, num_levels,
+                             paired, workspace_bytes)
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):
         """The loss wrappers' forward in THREE launches (csrc/sk_loss.hip): [X; Y] staged in both layouts straight from the two

@@ -226,6 +226,17 @@ int launch_truncated_long(const double *Xr, const double *Yt, int64_t A, int64_t
 bool truncated_long_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_LONG rule of sk_route_query
 int truncated_long_logw(int M, int Ncp, int fd, int paired);           // log2 of the lanes of a pair's group in that mode
 int64_t truncated_long_steps(int D, int M, int N);                     // sk_route.hip: the lane-steps of a pair in that mode
+// The LONG-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (order 1, dim <= 8): launch_truncated_adjoint's gradient on any number of steps -- the
+// reverse sweep in the long mode's bands and tiles.  Tpart, w and n_chunks as there.  A block's slab: the prefix factors of ONE band,
+// (L - 1) x (N + tiles (W - 1)) KB, and with more than one band (bands + 2) x (L - 1) x ceil64(N) doubles of forward and reverse carries.
+// The plan gives the chunk count, the blocks -- lowered from 8 per CU until their slabs fit `workspace` -- and ONE block's slab bytes;
+// SK_ERR_UNSUPPORTED outside the scope or when one block's slab does not fit.
+int truncated_long_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                                int64_t *blocks, size_t *block_bytes);
+int launch_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                  int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
+                                  int paired);
+bool truncated_long_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_LONG_ADJOINT rule of sk_route_query
 
 // ---- sk_loss.hip: the glue of the loss wrappers (compute_mmd / scoring rules) as single launches ----
 template <typename T>

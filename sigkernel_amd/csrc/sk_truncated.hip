@@ -43,6 +43,9 @@
 // LONG mode (TruncParams::adjoint = 4, launch-time and wave-uniform; order 1, fd = 8 or 16; Gram, paired and levels; forward only): paths of
 // any length -- trunc_long below: the rows in bands of 128 with the hand-down of a band's last row carried through HBM, the columns in tiles of
 // the y block with the row sums kept in registers; hosted by the <TR_OMAX, 1> instance beside the points modes.
+// LONG-ADJOINT mode (TruncParams::adjoint = 5, launch-time and wave-uniform; order 1, fd = 8; Gram and paired): the adjoint mode's gradient on
+// paths of any length -- trunc_long_adjoint below: the reverse recursion split as the long mode splits the forward, the forward carries kept
+// per band, a reverse carry handed up between the bands; hosted by the <TR_OMAX, 1> instance beside the long mode.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
 // order (1: one plane per level, or TR_OMAX) and the rows per lane.
 #include "sk_wave_common.h"
@@ -68,6 +71,9 @@ struct TruncParams {
                         // 3: the POINTS-ADJOINT mode, 1 for the lifted kernel (slab: L planes, the last one g)
                         // 4: the LONG mode, a forward launch on any number of steps (trunc_long; slab: [blocks][L - 1][ceil64(N)], the carry
                         // between a pair's row bands)
+                        // 5: the LONG-ADJOINT mode, 1 on any number of steps (trunc_long_adjoint; slab per block: the factors of one band,
+                        // [N + tiles (W - 1)][L - 1][128], then with more than one band the forward carries [bands][ceil64(N)][L - 1] and the
+                        // two halves of the reverse carry [2][ceil64(N)][L - 1])
     int64_t n_chunks;   // Gram: the B pairs of a row tile go to this many positions; paired: 1
     const double *w;    // [L][A][B], paired [L][A]: the weight of level m + 1 of every pair
     double *Tpart;      // [n_chunks][A][M][8]: the chunks' parts of dX, summed by the caller
@@ -622,6 +628,8 @@ __device__ __forceinline__ double lane_read(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
+typedef double trunc_d2 __attribute__((ext_vector_type(2)));       // 16 bytes of LDS as one asm operand
+
 // LONG mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 4, launch-time and wave-uniform; order 1, two rows per lane, fd = 8 or 16; Gram,
 // paired and levels; forward only): ANY number of steps on either side.  The node's recursion is the order-1 step loop's (phase 1 of
 // trunc_adjoint with the sums kept); an order-1 level is G times the exclusive 2-D prefix of the level below, and that prefix splits exactly:
@@ -815,6 +823,322 @@ __device__ __forceinline__ void trunc_long(const TruncParams &prm, double *ylds)
     }
 }
 
+// LONG-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 5, launch-time and wave-uniform; order 1, two rows per lane, fd = 8; Gram
+// and paired): trunc_adjoint's gradient -- dX of sum_pairs sum_m w_m(pair) k_m(pair) -- on ANY number of steps.  The reverse recursion is the
+// forward one mirrored, so it splits as trunc_long splits the forward.  Per pair a block runs 2 bands - 1 JOBS:
+//   bands - 1 CARRY jobs (bands 0 .. bands - 2; none with one band): trunc_long's band/tile loop without its sums.  What the last row of band
+//              `band` hands down at column j goes to plane band + 1 of the block's forward-carry planes, fcar[band + 1][j][s] -- not in place:
+//              every band's incoming carry is needed again below;
+//   bands ADJOINT jobs, band = bands - 1 .. 0, each
+//     (a) the band's forward sweep again from its stored incoming carry, through the column tiles left to right, storing per step and level
+//         s < L - 1 the qin[s] of both rows before the node joins them (phase 1 of trunc_adjoint) to the block's factor slab at step counter u,
+//         fac[(u (L - 1) + s) 64 + lane] as double2 -- 1 KB contiguous per store, the levels of a step side by side so that one running
+//         address serves them all; u runs through the band's tiles, bsteps = N + tiles (W - 1) steps in all;
+//     (b) the mirrored sweep: tiles right to left, steps downwards, u counted back, so that every lane reads the 16 bytes it wrote itself;
+//         program order and the vmcnt(0) wait between (a) and (b) are all the ordering there is -- no other wave touches a block's slabs.
+//         REVERSE CARRY: what lane 0 hands up at column j -- sup[s] after its node has joined it, the suffix of U^{s+2} over all later rows --
+//         with the weight w_{s+1} folded in (below) -- goes to half band & 1 of rcar[2][j][s]; the band above reads the other half, lane W - 1
+//         taking it where trunc_adjoint puts 0.0 (the last band: the weights).  It is fetched as trunc_long fetches its carry: one coalesced load per level for 64 steps, issued 64 steps
+//         before their first use, and a lane read per step.  rowT stays in registers across the tiles; the skew drains and restarts per tile.
+// dX: with one band it stays in registers over the chunk of b and is stored once, as trunc_adjoint's.  With bands a lane's rows change per
+// band: at the start of (b) the lane loads its rows of the chunk's plane of Tpart (zeros for the chunk's first b), continues the FMAs on them
+// and stores them at the band's end -- load, continue, store with plain stores: the summation order is that of uninterrupted accumulation.
+// Pairs, chunks and Tpart are trunc_adjoint's; the lane groups and the y tiles are trunc_long's at fd = 8.  Padding rows and columns have
+// G = 0; dG is masked off the columns exactly as g is, rows beyond M are never stored, and every value a lane can see is finite.
+__device__ __forceinline__ void trunc_long_adjoint(const TruncParams &prm, double *ylds) {
+    constexpr int NS = TR_LMAX - 1;
+    const int lane = threadIdx.x;
+    const int W = 1 << prm.logW, G = WAVE >> prm.logW;
+    const int lam = lane & (W - 1), grp = lane >> prm.logW;
+    const int N = prm.N, Ncp = prm.Ncp, L = prm.L;
+    const bool paired = prm.paired != 0;
+    const int Tc = Ncp < TR_LDS_DOUBLES / 8 ? Ncp : TR_LDS_DOUBLES / 8;
+    const int Ns = (N + 63) & ~63;
+    // the y tile in LDS: ylds[(k / 2) YS + 2 c + (k & 1)], coordinates in pairs at a constant stride -- a step's column is four 16-byte reads of one address
+    constexpr int YS = TR_LDS_DOUBLES / 4;
+    const int bands = (prm.M + 2 * W - 1) / (2 * W);
+    const int tiles = (N + Tc - 1) / Tc;
+    const int64_t bsteps = N + (int64_t)tiles * (W - 1);
+    const int64_t plane = paired ? prm.A : prm.A * prm.B;
+    const int64_t cplane = (int64_t)(L - 1) * Ns;               // one band's carry: L - 1 planes of ceil64(N)
+    const int64_t fsize = (int64_t)(L - 1) * bsteps * 128;      // the factor slab, in doubles
+    double *fcar = prm.slab + (int64_t)blockIdx.x * (fsize + (bands > 1 ? (bands + 2) * cplane : 0)) + fsize;    // [bands][Ns][L - 1]
+    double *rcar = fcar + bands * cplane;                                                                         // [2][Ns][L - 1]
+    double2 *fac = reinterpret_cast<double2 *>(fcar - fsize) + lane + 3 * 64;        // centred on level 3: the levels of a step are immediate offsets
+    // what a group's last lane takes from below in (b), behind the y tiles: with a band below the reverse carry of the chunk's 64 steps,
+    // rcl[k 8 + s], else the weights of the group's pair, rcl[grp 8 + s] -- every lane reads it with the step's column of y
+    double *rcl = ylds + TR_LDS_DOUBLES;
+    for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
+        int64_t a, b0, b1, chunk = 0;
+        int nblk = 1;
+        if (paired) {
+            b0 = pos * G;
+            b1 = b0 + 1;
+            a = b0 + grp;
+            nblk = prm.A - b0 < G ? (int)(prm.A - b0) : G;
+        } else {
+            const int64_t at = pos / prm.n_chunks;
+            chunk = pos - at * prm.n_chunks;
+            b0 = chunk * prm.B / prm.n_chunks;
+            b1 = (chunk + 1) * prm.B / prm.n_chunks;
+            a = at * G + grp;
+        }
+        const bool live = a < prm.A;
+        const trunc_d2 *yl = reinterpret_cast<const trunc_d2 *>(ylds) + ((paired && live) ? grp * Tc : 0);      // paired: the groups' tiles side by side, G Tc <= 256
+        double *tpl = prm.Tpart + (chunk * prm.A + (live ? a : 0)) * prm.M * 8;      // the lane group's rows of the chunk's plane
+        double dX[2][8];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dX[r][k] = 0.0;
+        for (int64_t b = b0; b < b1; ++b) {
+            const double *yb = prm.Yt + b * (int64_t)8 * Ncp;
+            for (int job = 0; job < 2 * bands - 1; ++job) {
+                const bool keep = job >= bands - 1;             // an adjoint job: (a) stores the factors, then (b)
+                const int band = keep ? 2 * bands - 2 - job : job;
+                const bool cin = band > 0, rin = band + 1 < bands;
+                const double *cinp = fcar + band * cplane;
+                double *coutp = fcar + (band + 1) * cplane;     // written by the carry jobs only: band + 1 < bands
+                double2 *fp = fac;      // the step's factors: (a) runs it up through the band's tiles, (b) back down
+                double xr[2][8];
+                bool rok[2];
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const int row = (band * W + lam) * 2 + r;
+                    rok[r] = live && row < prm.M;
+                    const double *xp = prm.Xr + ((rok[r] ? a : 0) * (int64_t)prm.Mrows + (rok[r] ? row : 0)) * 8;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) xr[r][k] = rok[r] ? xp[k] : 0.0;
+                }
+                {   // the band's forward sweep: trunc_long's loop without its sums
+                    double rowS[2][NS], qio[NS], cbuf[NS], cnext[NS];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) qio[s] = rowS[0][s] = rowS[1][s] = cbuf[s] = cnext[s] = 0.0;
+                    for (int c0 = 0; c0 < N; c0 += Tc) {
+                        const int nt = N - c0 < Tc ? N - c0 : Tc;
+                        if (cin) {      // the carry of the tile's first 64 columns
+#pragma unroll
+                            for (int s = 0; s < NS; ++s)
+                                if (s < L - 1) cnext[s] = c0 + lane < N ? cinp[(c0 + lane) * (L - 1) + s] : 0.0;
+                        }
+                        __syncthreads();
+                        for (int row = 0; row < nblk * 8; ++row)
+                            for (int c = lane; c < Tc; c += WAVE)
+                                ylds[((row & 7) >> 1) * YS + ((row >> 3) * Tc + c) * 2 + (row & 1)] = c0 + c < Ncp ? yb[(int64_t)row * Ncp + c0 + c] : 0.0;
+                        __syncthreads();
+                        const int steps = nt + W - 1;
+                        for (int t0 = 0; t0 < steps; t0 += 64) {
+                            if (cin) {  // the columns t0 .. t0 + 63 of the tile, asked for a chunk ago; ask for the next ones
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) cbuf[s] = cnext[s];
+                                if (t0 + 64 < nt) {
+                                    const int col = c0 + t0 + 64 + lane;
+#pragma unroll
+                                    for (int s = 0; s < NS; ++s)
+                                        if (s < L - 1) cnext[s] = col < N ? cinp[col * (L - 1) + s] : 0.0;
+                                }
+                            }
+                            const int t1 = t0 + 64 < steps ? t0 + 64 : steps;
+                            for (int t = t0; t < t1; ++t, fp += (L - 1) * 64) {
+                                int Ls = L;
+                                asm volatile("" : "+s"(Ls));      // the level guards of a step are scalar compares of its own
+                                const int j = t - lam;
+                                const bool act = (unsigned)j < (unsigned)nt;
+                                const int jc = act ? j : 0;
+                                double qin[NS], pf[2][NS], yv[8];
+                                trunc_d2 yq[4];
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) {
+                                    const double v = s < Ls - 1 ? dpp_shr1_zero(qio[s]) : 0.0;
+                                    const double c = s < Ls - 1 ? lane_read(cbuf[s], t - t0) : 0.0;
+                                    qin[s] = lam == 0 ? c : v;
+                                }
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) yq[k] = yl[k * (YS / 2) + jc];
+                                // (the wait takes the reads as they land, 16 bytes each: nothing copies a half out before it)
+                                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(yq[0]), "+v"(yq[1]), "+v"(yq[2]), "+v"(yq[3]));
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    yv[2 * k] = yq[k].x;
+                                    yv[2 * k + 1] = yq[k].y;
+                                }
+#pragma unroll
+                                for (int r = 0; r < 2; ++r) {
+                                    double g = 0.0;
+#pragma unroll
+                                    for (int k = 0; k < 8; ++k) g = fma(xr[r][k], yv[k], g);
+                                    g = act ? g : 0.0;
+                                    double prev = g;
+#pragma unroll
+                                    for (int s = 0; s < NS; ++s) {
+                                        pf[r][s] = qin[s];
+                                        if (s < Ls - 1) {
+                                            const double next = g * qin[s];
+                                            qin[s] = qin[s] + rowS[r][s];
+                                            rowS[r][s] += prev;
+                                            prev = next;
+                                        }
+                                    }
+                                }
+                                if (keep) {
+#pragma unroll
+                                    for (int s = 0; s < NS; ++s)
+                                        if (s < Ls - 1) fp[(s - 3) * 64] = make_double2(pf[0][s], pf[1][s]);
+                                } else if (lam == W - 1 && act) {       // a carry job: more than one band, W = 64, the wave's last lane
+#pragma unroll
+                                    for (int s = 0; s < NS; ++s)
+                                        if (s < Ls - 1) coutp[(c0 + j) * (Ls - 1) + s] = qin[s];
+                                }
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) qio[s] = qin[s];
+                            }
+                        }
+                    }
+                }
+                // the carry is in memory before the next band asks for it, the factors before (b) does
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (!keep) continue;
+                {   // (b): the band's sweep mirrored
+                    const double *rinp = rcar + ((band + 1) & 1) * cplane;
+                    double *routp = rcar + (band & 1) * cplane;
+                    // The hand-ups carry w_{s+1} + (suffix of U^{s+2}), not the suffix alone: Rb^{s+1} is then the hand-up as it arrives, and the
+                    // weights below the top one enter once, where trunc_adjoint puts 0.0 -- at the last lane of the last band's group.
+                    const int64_t pw = paired ? a : a * prm.B + b;
+                    const double wtop = live ? prm.w[(L - 1) * plane + pw] : 0.0;
+                    if (!rin && lam == 0) {
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) rcl[grp * 8 + s] = (live && s < L - 1) ? prm.w[s * plane + pw] : 0.0;
+                    }
+                    if (bands > 1) {    // the lane's rows change per band: continue on what the chunk has left in its plane of Tpart
+#pragma unroll
+                        for (int r = 0; r < 2; ++r) {
+                            const bool ld = rok[r] && b > b0;
+                            const double *tp = tpl + (ld ? (int64_t)((band * W + lam) * 2 + r) * 8 : 0);
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) dX[r][k] = ld ? tp[k] : 0.0;
+                        }
+                    }
+                    double rowT[2][NS], sio[NS], cnext[NS];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) sio[s] = rowT[0][s] = rowT[1][s] = cnext[s] = 0.0;
+                    for (int c0 = (tiles - 1) * Tc; c0 >= 0; c0 -= Tc) {
+                        const int nt = N - c0 < Tc ? N - c0 : Tc;
+                        if (rin) {      // the reverse carry of the tile's last 64 columns, lane k that of column nt - 1 - k
+#pragma unroll
+                            for (int s = 0; s < NS; ++s)
+                                if (s < L - 1) cnext[s] = lane < nt ? rinp[(c0 + nt - 1 - lane) * (L - 1) + s] : 0.0;
+                        }
+                        __syncthreads();
+                        for (int row = 0; row < nblk * 8; ++row)
+                            for (int c = lane; c < Tc; c += WAVE)
+                                ylds[((row & 7) >> 1) * YS + ((row >> 3) * Tc + c) * 2 + (row & 1)] = c0 + c < Ncp ? yb[(int64_t)row * Ncp + c0 + c] : 0.0;
+                        __syncthreads();
+                        const int steps = nt + W - 1;
+                        for (int t0 = 0; t0 < steps; t0 += 64) {        // t0, tt count the steps of the mirrored sweep: step t = steps - 1 - tt
+                            if (rin) {  // lane W - 1 is at column nt - 1 - tt: asked for a chunk ago, to LDS now; ask for the next 64
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) rcl[lane * 8 + s] = cnext[s];
+                                if (t0 + 64 < nt) {
+                                    const int col = nt - 1 - (t0 + 64) - lane;
+#pragma unroll
+                                    for (int s = 0; s < NS; ++s)
+                                        if (s < L - 1) cnext[s] = col >= 0 ? rinp[(c0 + col) * (L - 1) + s] : 0.0;
+                                }
+                            }
+                            const int t1 = t0 + 64 < steps ? t0 + 64 : steps;
+                            for (int tt = t0; tt < t1; ++tt) {
+                                int Ls = L;
+                                asm volatile("" : "+s"(Ls));      // the level guards of a step are scalar compares of its own
+                                fp -= (L - 1) * 64;
+                                const int j = steps - 1 - tt - lam;
+                                const bool act = (unsigned)j < (unsigned)nt;
+                                const int jc = act ? j : 0;
+                                double sup[NS], yv[8], rc[NS];
+                                trunc_d2 yq[4], rq[4];
+                                double2 pf[NS];
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) pf[s] = s < Ls - 1 ? fp[(s - 3) * 64] : make_double2(0.0, 0.0);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) yq[k] = yl[k * (YS / 2) + jc];
+                                const trunc_d2 *rcp = reinterpret_cast<const trunc_d2 *>(rcl + (rin ? tt - t0 : grp) * 8);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) rq[k] = rcp[k];
+                                asm volatile("s_waitcnt lgkmcnt(0)"
+                                             : "+v"(yq[0]), "+v"(yq[1]), "+v"(yq[2]), "+v"(yq[3]), "+v"(rq[0]), "+v"(rq[1]), "+v"(rq[2]), "+v"(rq[3]));
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    yv[2 * k] = yq[k].x;
+                                    yv[2 * k + 1] = yq[k].y;
+                                    rc[2 * k] = rq[k].x;
+                                    if (2 * k + 1 < NS) rc[2 * k + 1] = rq[k].y;
+                                }
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) {
+                                    const double v = s < Ls - 1 ? dpp_shl1(sio[s], 0.0) : 0.0;
+                                    sup[s] = lam == W - 1 ? rc[s] : v;
+                                }
+#pragma unroll
+                                for (int r = 1; r >= 0; --r) {
+                                    double g = 0.0;
+#pragma unroll
+                                    for (int k = 0; k < 8; ++k) g = fma(xr[r][k], yv[k], g);
+                                    g = act ? g : 0.0;
+                                    double rb = 0.0, dG = 0.0;
+#pragma unroll
+                                    for (int m = TR_LMAX; m >= 1; --m)
+                                        if (m <= Ls) {
+                                            rb = m == Ls ? wtop : rb;
+                                            dG = m == 1 ? dG + rb : fma(rb, r ? pf[m > 1 ? m - 2 : 0].y : pf[m > 1 ? m - 2 : 0].x, dG);
+                                            if (m > 1) {
+                                                const int s = m - 2;
+                                                const double uu = g * rb;
+                                                rb = sup[s];
+                                                sup[s] = sup[s] + rowT[r][s];
+                                                rowT[r][s] += uu;
+                                            }
+                                        }
+                                    dG = act ? dG : 0.0;
+#pragma unroll
+                                    for (int k = 0; k < 8; ++k) dX[r][k] = fma(dG, yv[k], dX[r][k]);
+                                }
+                                if (cin && lam == 0 && act) {       // a band above: W = 64, the wave's first lane
+#pragma unroll
+                                    for (int s = 0; s < NS; ++s)
+                                        if (s < Ls - 1) routp[(c0 + j) * (Ls - 1) + s] = sup[s];
+                                }
+#pragma unroll
+                                for (int s = 0; s < NS; ++s) sio[s] = sup[s];
+                            }
+                        }
+                    }
+                    if (bands > 1) {
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+                            if (rok[r]) {
+                                double *tp = tpl + (int64_t)((band * W + lam) * 2 + r) * 8;
+#pragma unroll
+                                for (int k = 0; k < 8; ++k) tp[k] = dX[r][k];
+                            }
+                    }
+                }
+                // the reverse carry and the rows of dX are in memory before the next job asks for them
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        if (bands == 1 && live) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int row = lam * 2 + r;
+                if (row < prm.M) {
+                    double *tp = tpl + (int64_t)row * 8;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) tp[k] = dX[r][k];
+                }
+            }
+        }
+    }
+}
+
 template <int OM, int RC>
 __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     extern __shared__ __attribute__((aligned(16))) double ylds[];   // [fd][Ncp]; paired: [G][fd][Ncp], one block per lane group
@@ -834,10 +1158,11 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
         }
     }
     if constexpr (OM > 1) {
-        if (prm.adjoint) {      // 2, the POINTS mode, 3, its adjoint, and 4, the LONG mode: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
+        if (prm.adjoint) {      // 2, the POINTS mode, 3, its adjoint, 4, the LONG mode, and 5, its adjoint: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
             if (prm.adjoint == 3) trunc_points_adjoint(prm, ylds);
             else if (prm.adjoint == 4) trunc_long(prm, ylds);
-            else trunc_points(prm, ylds);
+            else if (prm.adjoint == 2) trunc_points(prm, ylds);
+            else trunc_long_adjoint(prm, ylds);         // (last: of the placements tried the one that moves the general loop least)
             return;
         }
     }
@@ -1296,6 +1621,84 @@ int launch_truncated_long(const double *Xr, const double *Yt, int64_t A, int64_t
     const int Tc = Ncp < TR_LDS_DOUBLES / fd ? Ncp : TR_LDS_DOUBLES / fd;
     const size_t lds = sizeof(double) * ((size_t)fd * Tc * (paired ? G : 1) + (size_t)WAVE * (TR_LMAX - 1));   // the y tiles; the lanes' level totals
     SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)pl.blocks), dim3(WAVE), lds, s, prm);
+    return check_launch();
+}
+
+// THE scope of the long-adjoint mode (the SK_OP_TRUNCATED_LONG_ADJOINT rule of sk_route_query): the long mode's with a path dim of at most 8,
+// for the reason the adjoint mode has.  Every shape of truncated_adjoint_in_scope is inside.
+bool truncated_long_adjoint_in_scope(int D, int M, int N, int L, int order) {
+    return truncated_long_in_scope(D, M, N, L, order) && D <= 8;
+}
+
+namespace {
+struct LongAdjointPlan {
+    int logW;
+    int64_t n_pos, n_chunks, blocks;
+    size_t block_bytes;     // a block's slab: the factors of one band, (L - 1) x (N + tiles (W - 1)) KB, and with more than one band the
+                            // forward carries and the two reverse-carry halves, (bands + 2) x (L - 1) x ceil64(N) doubles
+};
+// The split of a long-adjoint launch: plan_adjoint's chunks on the long mode's lane groups.  The block count is lowered until blocks x slab
+// fits `workspace`; false when one block does not.
+bool plan_long_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int L, int paired, size_t workspace, LongAdjointPlan *pl) {
+    pl->logW = truncated_long_logw(M, Ncp, 8, paired);
+    const int W = 1 << pl->logW, G = WAVE >> pl->logW;
+    const int64_t rtiles = (A + G - 1) / G, resident = (int64_t)device_cu_count() * 8;
+    pl->n_chunks = 1;
+    if (!paired) {
+        pl->n_chunks = resident / rtiles;
+        if (pl->n_chunks > B) pl->n_chunks = B;
+        if (pl->n_chunks < 1) pl->n_chunks = 1;
+    }
+    pl->n_pos = rtiles * pl->n_chunks;
+    pl->blocks = pl->n_pos < resident ? pl->n_pos : resident;
+    const int Tc = Ncp < TR_LDS_DOUBLES / 8 ? Ncp : TR_LDS_DOUBLES / 8;
+    const int64_t ctiles = (N + Tc - 1) / Tc, bands = (M + 2 * W - 1) / (2 * W), Ns = (N + 63) / 64 * 64;
+    pl->block_bytes = (size_t)(L - 1) * ((size_t)(N + ctiles * (W - 1)) * 1024 + (bands > 1 ? (size_t)(bands + 2) * Ns * sizeof(double) : 0));
+    if (pl->block_bytes) {
+        const int64_t fit = (int64_t)(workspace / pl->block_bytes);
+        if (fit < 1) return false;
+        if (pl->blocks > fit) pl->blocks = fit;
+    }
+    return true;
+}
+}  // namespace
+
+int truncated_long_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                                int64_t *blocks, size_t *block_bytes) {
+    if (!truncated_long_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    LongAdjointPlan pl;
+    if (!plan_long_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
+    *n_chunks = pl.n_chunks;
+    *blocks = pl.blocks;
+    *block_bytes = pl.block_bytes;
+    return SK_OK;
+}
+
+int launch_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                  int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
+                                  int paired) {
+    if (!truncated_long_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    if (fd != 8 || Ncp < N || Ncp % 16 || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
+    if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
+    LongAdjointPlan pl;
+    if (!plan_long_adjoint(A, B, M, N, Ncp, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
+    TruncParams prm;
+    prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
+    prm.A = A; prm.B = B;
+    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
+    prm.order = 1; prm.out_f32 = 0;
+    prm.paired = paired != 0;
+    prm.levels = 0;
+    prm.param = 0.0;
+    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
+    prm.adjoint = 5; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
+    prm.logW = pl.logW;
+    const int G = WAVE >> pl.logW;
+    prm.n_pos = (A + G - 1) / G * n_chunks;     // the caller's chunk count (Tpart is sized by it); the plan's block count for the slab
+    int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
+    // the y tiles at their constant stride; the reverse carry of 64 steps, eight doubles a step
+    const size_t lds = sizeof(double) * ((size_t)TR_LDS_DOUBLES + (size_t)WAVE * TR_LMAX);
+    SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     return check_launch();
 }
 

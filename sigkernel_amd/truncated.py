@@ -49,6 +49,8 @@ whose backward is the kernel's adjoint mode (``HipBackend.truncated_adjoint``: o
 rule -- a gradient pending means the torch restatement.  Its ``static_kernel`` is the one place where G is something other than inner
 products of steps: an RBFKernel is the kernel's points mode -- forward only, unless ``points_adjoint=True`` asks for ``_LiftedLevels``, whose
 backward is the kernel's points-adjoint mode (``HipBackend.truncated_points_adjoint``) -- anything else the restatement on ``_lifted_gram``.
+Beyond the adjoint mode's 128 steps a gradient takes the restatement too, unless ``long_adjoint=True`` asks for ``_LongLevels``: the long
+mode's levels launch forward, the kernel's long-adjoint mode backward (``HipBackend.truncated_long_adjoint``: order 1, dim <= 8, any steps).
 """
 import numpy as np
 import torch
@@ -449,9 +451,12 @@ def _pair_slices(P, M, N, D, workspace_bytes):
 
 def _adjoint(be, X, Y, w, L, paired, workspace_bytes, param=None):
     """d / dX of sum_pairs sum_m w[m - 1, pair] k_m(pair) by the kernel's adjoint mode, in X's dtype; paired batches in _chunked's runs.
-    `param`: X and Y hold POINTS and the k_m are those of the lift through RBFKernel(param) -- the points-adjoint mode"""
+    `param`: X and Y hold POINTS and the k_m are those of the lift through RBFKernel(param) -- the points-adjoint mode; the string
+    "long": steps of any number -- the long-adjoint mode"""
     if param is None:
         call = lambda x, y, v, p: be.truncated_adjoint(x, y, v, L, p, workspace_bytes)
+    elif param == "long":
+        call = lambda x, y, v, p: be.truncated_long_adjoint(x, y, v, L, p, workspace_bytes)
     else:
         call = lambda x, y, v, p: be.truncated_points_adjoint(x, y, v, L, param, p, workspace_bytes)
     if not paired:
@@ -527,6 +532,26 @@ class _LiftedLevels(torch.autograd.Function):
         return _levels_backward(ctx, grad, ctx.param)
 
 
+class _LongLevels(torch.autograd.Function):
+    """_TruncatedLevels for STEP tensors beyond the plain launch, order 1: forward = the long mode's levels launch (_long: on (Y, X),
+    transposed, where that sweep is the shorter one), backward = the long-adjoint mode, one launch per batch that needs a gradient and ONE
+    with w + w^T for a symmetric call.  The caller has asked the route table for every side (TruncatedSigKernel._long_adjoint_serves)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, L, order, paired, sym, workspace_bytes):
+        lev = _long(_lib.get_backend(), X, Y, L, None, paired, workspace_bytes)
+        if lev is None:
+            raise RuntimeError("the long mode of k_trunc_sig declined a shape its route query accepted")
+        ctx.save_for_backward(X, Y)
+        ctx.mode = (L, paired, sym, workspace_bytes)
+        return lev
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        return _levels_backward(ctx, grad, "long")
+
+
 class TruncatedSigKernel:
     """The truncated signature kernel behind SigKernel's interface: ``X`` and ``Y`` are PATHS ``(batch, length, dim)`` -- differenced here
     with torch ops, so a gradient reaches whatever produced them -- and the kernel is truncated_sig_kernel's on the steps, ``num_levels``
@@ -559,12 +584,26 @@ class TruncatedSigKernel:
     (sk_route_query(SK_OP_TRUNCATED_RBF_ADJOINT)) and a block's slab of num_levels x (points of the other side + lanes - 1) KB within
     ``workspace_bytes``; every other call takes the restatement as a whole, as without the keyword.  ``sigma`` keeps its gradient either way
     (the RBF bandwidth is a float and has none).  The default is False -- every call then does what it did before the keyword existed --
-    and flipping it is left to a later change."""
+    and flipping it is left to a later change.
 
-    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None, static_kernel=None, points_adjoint=False):
+    ``long_adjoint=True`` keeps the PLAIN kernel (``static_kernel`` None or a LinearKernel) on the HIP route with a gradient pending beyond
+    those 128 steps: the forward is the long mode's levels launch (row bands of 128 steps, column tiles of 256) and the backward the same
+    kernel's long-adjoint mode -- the reverse sweep through the same bands and tiles -- one launch per batch that requires grad (one in all
+    for ``sym=True``), bit-reproducible, nothing of size pairs x M x N allocated.  It takes effect at order 1 on a HIP device where the
+    route above declined, the forward is in the long mode's scope (sk_route_query(SK_OP_TRUNCATED_LONG): path dim <= 16) and every batch
+    that requires grad has path dim <= 8 (sk_route_query(SK_OP_TRUNCATED_LONG_ADJOINT)) and a block's slab within ``workspace_bytes``:
+    (num_levels - 1) x (steps of the other side + 63 per tile of 256) KB, plus with more than 128 steps of its own
+    (bands + 2) x (num_levels - 1) x ceil64(steps of the other side) doubles.  The launch takes 8 blocks per CU only if all their slabs
+    fit: at the default 1 GiB a few hundred steps already lower the block count, so pass a larger ``workspace_bytes`` for speed.  Every
+    other call takes the restatement as a whole, as without the keyword, and ``sigma`` keeps its gradient either way.  The keyword does
+    not depend on ``routes.truncated_long``, which keeps governing the calls without a gradient.  The default is False -- every call then
+    does what it did before the keyword existed -- and flipping it is left to a later change."""
+
+    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None, static_kernel=None, long_adjoint=False, points_adjoint=False):
         self.num_levels, self.sigma, self.order, self.workspace_bytes = num_levels, sigma, order, workspace_bytes
         self.static_kernel = static_kernel
         self.points_adjoint = bool(points_adjoint)
+        self.long_adjoint = bool(long_adjoint)
 
     def _hip_serves(self, dx, dy, L, order, paired, sym):
         """the HIP function serves the call: a HIP device, no empty axis, the forward in scope on (dx, dy) or (dy, dx), and on every side
@@ -583,6 +622,26 @@ class TruncatedSigKernel:
         if grad and dx.requires_grad and not be.truncated_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
             return False
         if grad and dy.requires_grad and not sym and not be.truncated_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
+            return False
+        return True
+
+    def _long_adjoint_serves(self, dx, dy, L, order, paired, sym):
+        """long_adjoint=True applies (asked where _hip_serves declined): step tensors on a HIP device with a gradient pending, order 1, no
+        empty axis, the forward in the long mode's scope on (dx, dy) or (dy, dx), and every side that needs a gradient in the long-adjoint
+        mode's, a block's slab within the workspace"""
+        if not (self.long_adjoint and _on_hip(dx) and order == 1 and min(dx.shape[0], dx.shape[1], dy.shape[0], dy.shape[1]) > 0):
+            return False
+        if not (torch.is_grad_enabled() and (dx.requires_grad or dy.requires_grad)):
+            return False
+        be = _lib.get_backend()
+        if not (hasattr(be, "truncated_long") and hasattr(be, "truncated_long_adjoint") and hasattr(be, "truncated_long_adjoint_fits")):
+            return False
+        (A, M, D), (B, N), es = dx.shape, dy.shape[:2], dx.element_size()
+        if be.route(_lib.OP_TRUNCATED_LONG, 1, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
+            return False
+        if dx.requires_grad and not be.truncated_long_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
+            return False
+        if dy.requires_grad and not sym and not be.truncated_long_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
             return False
         return True
 
@@ -641,6 +700,9 @@ class TruncatedSigKernel:
         if self._hip_serves(dx, dy, L, order, paired, sym):
             dx = dx.contiguous()
             return _TruncatedLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, order, paired, sym, self.workspace_bytes)
+        if self._long_adjoint_serves(dx, dy, L, order, paired, sym):     # opt-in: steps beyond the adjoint mode's, a gradient pending
+            dx = dx.contiguous()
+            return _LongLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, 1, paired, sym, self.workspace_bytes)
         if _on_hip(dx) and _long_serves(_lib.get_backend(), dx, dy, None, order):     # opt-in: steps beyond the plain launch, no gradient pending
             lev = _long(_lib.get_backend(), dx.contiguous(), dy.contiguous(), L, None, paired, self.workspace_bytes)
             if lev is not None:
