@@ -63,7 +63,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*, sk_truncated_wide_adjoint*) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -142,6 +142,12 @@ const char *sk_cost_note(int which);
                                  SK_ROUTE_STREAM otherwise = autograd of the host layer's torch restatement.  Never swapped: the gradient goes
                                  to the rows, and the second batch's is the same query on (N, M).  The host layer asks only where
                                  SK_OP_TRUNCATED_ADJOINT's route declined, and only for TruncatedSigKernel(long_adjoint=True). */
+#define SK_OP_TRUNCATED_WIDE_ADJOINT 10 /* the gradient of SK_OP_TRUNCATED_ADJOINT at path dims 9 .. 16 (kind, dyadic, M, N as SK_OP_TRUNCATED:
+                                 steps): SK_ROUTE_FUSED = sk_truncated_wide_adjoint: inside SK_OP_TRUNCATED's FUSED scope, order 1 (kind 1, or
+                                 num_levels 1), 9 <= path dim <= 16, M <= 128 (and 16 x ceil16(N) <= 2048: N <= 128); SK_ROUTE_STREAM otherwise
+                                 -- path dims up to 8 included, which SK_OP_TRUNCATED_ADJOINT serves -- = autograd of the host layer's torch
+                                 restatement.  Never swapped: the second batch's gradient is the same query on (N, M).  The host layer asks
+                                 only where SK_OP_TRUNCATED_ADJOINT's route declined, and only for TruncatedSigKernel(wide_adjoint=True). */
 #define SK_ROUTE_STREAM 0
 #define SK_ROUTE_FUSED 1
 #define SK_ROUTE_FUSED_MB 2
@@ -590,6 +596,23 @@ int sk_truncated_long_f32(const double *Xr, const double *Yt, int64_t A, int64_t
 int sk_truncated_long_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
                                    int64_t *plan);
 int sk_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                              int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
+                              int paired);
+/* The gradient of sk_truncated_adjoint (below: w, n_chunks, the staging, the slab and the reproducibility are its) at path dims 9 .. 16, order 1,
+ * at most 128 steps on either side: the same two sweeps per pair with rows and accumulators of 16 coordinates, by k_trunc_sig<4, 1> in its
+ * wide-adjoint mode.  The chunks' parts go to Tpart [n_chunks][A][M][16]; the caller adds the chunks and keeps the first D of the 16 columns.
+ *   sk_truncated_wide_adjoint_plan  plan[0..2] = n_chunks, blocks, slab bytes of the shape, the slab within workspace_bytes (the block count
+ *                                   is lowered until it fits); SK_ERR_UNSUPPORTED when one block's slab, (num_levels - 1) (N + W - 1) KB with
+ *                                   W the lanes of a pair's group, does not.  paired: the groups widen until G x 16 x ceil16(N) doubles fit
+ *                                   the wave's 16 KB of LDS, so W can exceed ceil(M / 2).  Host only.
+ *   sk_truncated_wide_adjoint       Xr, Yt, Mrows, Ncp, fd as sk_truncated_gram_* (fd = 16 required: SK_ERR_BAD_ARG otherwise, as for
+ *                                   Ncp < N, a paired call with A != B, or n_chunks outside 1 .. B (paired: 1)); slab / slab_bytes: device
+ *                                   scratch, may be NULL / 0 at num_levels = 1.  Scope and arguments are checked before the device is touched.
+ * Scope: sk_route_query(SK_OP_TRUNCATED_WIDE_ADJOINT, 1, D, M, N, num_levels, ...) == SK_ROUTE_FUSED -- order 1, 9 <= D <= 16; else
+ * SK_ERR_UNSUPPORTED. */
+int sk_truncated_wide_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
+                                   int64_t *plan);
+int sk_truncated_wide_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                               int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
                               int paired);
 /* The GRADIENT of the level terms with respect to the first batch, by the same kernel in its adjoint mode (no counterpart in the reference,

@@ -19,6 +19,7 @@ OP_FORWARD, OP_ADJOINT, OP_ADJOINT_SYM, OP_PREFIX, OP_TRUNCATED, OP_TRUNCATED_AD
 OP_TRUNCATED_RBF_ADJOINT = 7
 OP_TRUNCATED_LONG = 8
 OP_TRUNCATED_LONG_ADJOINT = 9
+OP_TRUNCATED_WIDE_ADJOINT = 10
 ROUTE_STREAM, ROUTE_FUSED, ROUTE_FUSED_MB, ROUTE_FUSED_MB_SWAP, ROUTE_FUSED_SWAP = 0, 1, 2, 3, 4
 ROUTE_NO_STREAM = 1
 ROUTE_NO_SWAP = 2
@@ -106,6 +107,8 @@ SIGNATURES = {
     "sk_truncated_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
     "sk_truncated_long_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
     "sk_truncated_long_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
+    "sk_truncated_wide_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
+    "sk_truncated_wide_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
     "sk_truncated_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _sz, _vp, _int]),
     "sk_truncated_points_adjoint_plan": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _sz, _vp]),
     "sk_truncated_points_adjoint": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _i64, _vp, _sz,
@@ -837,6 +840,20 @@ class HipBackend:
         within `workspace_bytes` (default 1 GiB; the block count is lowered from 8 per CU until they fit, so long paths want more).  None
         outside the scope (sk_route_query(SK_OP_TRUNCATED_LONG_ADJOINT) != FUSED: order 1, dim <= 8) or when one block's slab does not fit."""
         return self._adjoint(OP_TRUNCATED_LONG_ADJOINT, "sk_truncated_long_adjoint_plan", "sk_truncated_long_adjoint", (), X, Y, w, num_levels,
+                             paired, workspace_bytes)
+
+    def truncated_wide_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
+        """whether truncated_wide_adjoint serves the shape: SK_OP_TRUNCATED_WIDE_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""
+        return self._adjoint_fits(OP_TRUNCATED_WIDE_ADJOINT, "sk_truncated_wide_adjoint_plan", A, B, M, N, D, num_levels, paired,
+                                  workspace_bytes, elem_size)
+
+    def truncated_wide_adjoint(self, X, Y, w, num_levels, paired=False, workspace_bytes=None):
+        """truncated_adjoint's gradient at path dims 9 .. 16, by k_trunc_sig<4, 1> in its wide-adjoint mode (sk_truncated_wide_adjoint):
+        X, Y, w and the result (A, M, D) in fp64 as there, staged at 16 coordinates; the chunks' parts are chunks x A x M x 16 doubles and a
+        block's slab (num_levels - 1) x (N + lanes - 1) KB, all blocks' within `workspace_bytes` (default 1 GiB; the block count is lowered
+        until they fit).  None outside the scope (sk_route_query(SK_OP_TRUNCATED_WIDE_ADJOINT) != FUSED: order 1, 9 <= dim <= 16, at most
+        128 steps on either side) or when one block's slab does not fit."""
+        return self._adjoint(OP_TRUNCATED_WIDE_ADJOINT, "sk_truncated_wide_adjoint_plan", "sk_truncated_wide_adjoint", (), X, Y, w, num_levels,
                              paired, workspace_bytes)
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):

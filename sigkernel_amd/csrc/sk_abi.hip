@@ -259,8 +259,8 @@ int device_cu_count() {
 extern "C" {
 
 // (340 still: sk_truncated_levels_{,paired_}{f64,f32}, sk_truncated_adjoint and its plan, sk_truncated_points_{f64,f32} and SK_OP_TRUNCATED_RBF,
-// sk_truncated_long_{f64,f32}, its plan and SK_OP_TRUNCATED_LONG, sk_truncated_long_adjoint, its plan and SK_OP_TRUNCATED_LONG_ADJOINT are
-// additions, no exported signature changed)
+// sk_truncated_long_{f64,f32}, its plan and SK_OP_TRUNCATED_LONG, sk_truncated_long_adjoint, its plan and SK_OP_TRUNCATED_LONG_ADJOINT,
+// sk_truncated_wide_adjoint, its plan and SK_OP_TRUNCATED_WIDE_ADJOINT are additions, no exported signature changed)
 // 340: sk_static_increments_* serve any path dim (D > 32: k_static_wide_mfma); sk_static_adjoint_* kind 1 with D > 32 writes the first
 // pass H [P][M][ldh] of the rbf chain rule instead of dL/dX
 // 330 (round 6): sk_linear_adjoint_fused_f64 takes ypart / ypart_doubles / ycols_out (the second-argument sums, route FUSED_SWAP)
@@ -578,6 +578,24 @@ int sk_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A, int
         return SK_ERR_BAD_ARG;
     if (A == 0 || B == 0) return SK_OK;
     return launch_truncated_long_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, w, Tpart, n_chunks, slab, slab_bytes,
+                                         (hipStream_t)stream, paired);
+}
+int sk_truncated_wide_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
+                                   int64_t *plan) {
+    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
+    size_t slab = 0;
+    const int rc = truncated_wide_adjoint_plan(A, B, M, N, D, num_levels, paired, workspace_bytes, plan, plan + 1, &slab);
+    if (rc == SK_OK) plan[2] = (int64_t)slab;
+    return rc;
+}
+int sk_truncated_wide_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                              int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
+                              int paired) {
+    if (D < 1 || !Xr || !Yt || !w || !Tpart || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D ||
+        (slab_bytes && !slab) || (paired && A != B))
+        return SK_ERR_BAD_ARG;
+    if (A == 0 || B == 0) return SK_OK;
+    return launch_truncated_wide_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, w, Tpart, n_chunks, slab, slab_bytes,
                                          (hipStream_t)stream, paired);
 }
 int sk_truncated_points_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,

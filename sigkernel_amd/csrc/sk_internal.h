@@ -237,6 +237,16 @@ int launch_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A,
                                   int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
                                   int paired);
 bool truncated_long_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_LONG_ADJOINT rule of sk_route_query
+// The WIDE-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (order 1, dims 9 .. 16, at most 128 steps): launch_truncated_adjoint's gradient at fd = 16 --
+// Tpart [n_chunks][A][M][16]; w, n_chunks, the slab of (L - 1) x (N + W - 1) KB a block and the plan as there.  In paired mode the lane groups
+// widen until their y blocks of 16 x Ncp doubles fit the wave's LDS.  SK_ERR_UNSUPPORTED outside the scope (dims up to 8 included: the
+// adjoint mode serves them) or when one block's slab does not fit.
+int truncated_wide_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                                int64_t *blocks, size_t *slab_bytes);
+int launch_truncated_wide_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                  int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
+                                  int paired);
+bool truncated_wide_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_WIDE_ADJOINT rule of sk_route_query
 
 // ---- sk_loss.hip: the glue of the loss wrappers (compute_mmd / scoring rules) as single launches ----
 template <typename T>

@@ -207,6 +207,12 @@ int route_query(int op, int kind, int D, int M, int N, int d, int naive, int ele
         if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
         return truncated_long_adjoint_in_scope(D, M, N, d, kind) ? SK_ROUTE_FUSED : SK_ROUTE_STREAM;
     }
+    if (op == SK_OP_TRUNCATED_WIDE_ADJOINT) {
+        // the gradient of SK_OP_TRUNCATED_ADJOINT at path dims 9 .. 16: FUSED = the wide-adjoint mode of k_trunc_sig<4, 1>
+        // (truncated_wide_adjoint_in_scope is the rule), STREAM = autograd of the torch restatement.  Never swapped: the gradient goes to the rows.
+        if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
+        return truncated_wide_adjoint_in_scope(D, M, N, d, kind) ? SK_ROUTE_FUSED : SK_ROUTE_STREAM;
+    }
     if ((kind != 0 && kind != 1) || D < 1 || D > 16 || M < 2 || N < 2 || d < 0 || d > 2) return SK_ROUTE_STREAM;
     if (elem_size != 8 && elem_size != 4) return SK_ROUTE_STREAM;
     const int Mc = M - 1, Nc = N - 1;

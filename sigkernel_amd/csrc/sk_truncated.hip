@@ -46,6 +46,9 @@
 // LONG-ADJOINT mode (TruncParams::adjoint = 5, launch-time and wave-uniform; order 1, fd = 8; Gram and paired): the adjoint mode's gradient on
 // paths of any length -- trunc_long_adjoint below: the reverse recursion split as the long mode splits the forward, the forward carries kept
 // per band, a reverse carry handed up between the bands; hosted by the <TR_OMAX, 1> instance beside the long mode.
+// WIDE-ADJOINT mode (TruncParams::adjoint = 6, launch-time and wave-uniform; order 1, fd = 16; Gram and paired): the adjoint mode's gradient at
+// path dims 9 .. 16 on at most 128 steps -- trunc_wide_adjoint below: trunc_adjoint's two phases with rows and dX of 16 coordinates, the
+// column of y read from LDS in halves; hosted by the <TR_OMAX, 1> instance beside the other modes.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
 // order (1: one plane per level, or TR_OMAX) and the rows per lane.
 #include "sk_wave_common.h"
@@ -74,6 +77,7 @@ struct TruncParams {
                         // 5: the LONG-ADJOINT mode, 1 on any number of steps (trunc_long_adjoint; slab per block: the factors of one band,
                         // [N + tiles (W - 1)][L - 1][128], then with more than one band the forward carries [bands][ceil64(N)][L - 1] and the
                         // two halves of the reverse carry [2][ceil64(N)][L - 1])
+                        // 6: the WIDE-ADJOINT mode, 1 at fd = 16 (trunc_wide_adjoint; slab and w as 1, Tpart [n_chunks][A][M][16])
     int64_t n_chunks;   // Gram: the B pairs of a row tile go to this many positions; paired: 1
     const double *w;    // [L][A][B], paired [L][A]: the weight of level m + 1 of every pair
     double *Tpart;      // [n_chunks][A][M][8]: the chunks' parts of dX, summed by the caller
@@ -1139,6 +1143,184 @@ __device__ __forceinline__ void trunc_long_adjoint(const TruncParams &prm, doubl
     }
 }
 
+// WIDE-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 6, launch-time and wave-uniform; order 1, two rows per lane, fd = 16;
+// Gram and paired): trunc_adjoint's gradient at path dims 9 .. 16, on at most 128 steps.  Pairs, chunks, liveness, the two phases, the slab and
+// its indexing, the hand-ups and Tpart (rows of 16 doubles here) are trunc_adjoint's, and so is the arithmetic, operation for operation (a
+// batch padded with zero coordinates gives trunc_adjoint's bits).  What differs is what a lane keeps in registers: xr[2][16] and dX[2][16]
+// are 128 of its 256, so
+//   * the column of y is never there whole: it is read from LDS in two HALVES of eight coordinates, each gone before the next one comes --
+//     both halves for g of the two rows, and both halves again for the dX update AFTER the level recursion, when its state is dead: 32 LDS
+//     reads a step where a register copy would have 16, beside some 120 fp64 operations;
+//   * both phases run LEVEL BY LEVEL with the lane's two rows side by side (rows couple only through a level's hand-down / hand-up, so the
+//     level order can be the outer loop): a level's two prefix factors are stored the moment they exist (phase 1) or loaded inside the level
+//     (phase 2), and no array of factors or hand-ups exists.
+// Written as trunc_adjoint is -- factors and hand-ups fetched at the top of a step, one row's recursion after the other -- the instance
+// needed 282 registers, one wave per SIMD for all its modes; as below it stays at 249.
+__device__ __forceinline__ void trunc_wide_adjoint(const TruncParams &prm, double *ylds) {
+    constexpr int NS = TR_LMAX - 1;
+    const int lane = threadIdx.x;
+    const int W = 1 << prm.logW, G = WAVE >> prm.logW;
+    const int lam = lane & (W - 1), grp = lane >> prm.logW;
+    const int N = prm.N, Ncp = prm.Ncp, L = prm.L;
+    const int steps = N + W - 1;
+    const bool paired = prm.paired != 0;
+    const int64_t plane = paired ? prm.A : prm.A * prm.B;
+    double2 *slab = reinterpret_cast<double2 *>(prm.slab + (int64_t)blockIdx.x * (L - 1) * steps * 128) + lane;
+    for (int64_t pos = blockIdx.x; pos < prm.n_pos; pos += gridDim.x) {
+        int64_t a, b0, b1, chunk = 0;
+        int nblk = 1;
+        if (paired) {
+            b0 = pos * G;
+            b1 = b0 + 1;
+            a = b0 + grp;
+            nblk = prm.A - b0 < G ? (int)(prm.A - b0) : G;
+        } else {
+            const int64_t at = pos / prm.n_chunks;
+            chunk = pos - at * prm.n_chunks;
+            b0 = chunk * prm.B / prm.n_chunks;
+            b1 = (chunk + 1) * prm.B / prm.n_chunks;
+            a = at * G + grp;
+        }
+        const bool live = a < prm.A;
+        const double *yl = ylds + ((paired && live) ? grp * 16 * Ncp : 0);
+        double xr[2][16], dX[2][16];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int row = lam * 2 + r;
+            const bool ok = live && row < prm.M;
+            const double *xp = prm.Xr + ((ok ? a : 0) * (int64_t)prm.Mrows + (ok ? row : 0)) * 16;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                xr[r][k] = ok ? xp[k] : 0.0;
+                dX[r][k] = 0.0;
+            }
+        }
+        for (int64_t b = b0; b < b1; ++b) {
+            __syncthreads();
+            {
+                const double *yb = prm.Yt + b * (int64_t)16 * Ncp;
+                for (int k = lane; k < nblk * 16 * Ncp; k += WAVE) ylds[k] = yb[k];
+            }
+            double w[TR_LMAX];
+#pragma unroll
+            for (int m = 0; m < TR_LMAX; ++m) w[m] = (live && m < L) ? prm.w[m * plane + (paired ? a : a * prm.B + b)] : 0.0;
+            __syncthreads();
+            {   // phase 1
+                double rowS[2][NS], qio[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) qio[s] = rowS[0][s] = rowS[1][s] = 0.0;
+                for (int t = 0; t < steps; ++t) {
+                    const int j = t - lam;
+                    const bool act = (unsigned)j < (unsigned)N;
+                    const int jc = act ? j : 0;
+                    double g[2] = {0.0, 0.0};
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        double yv[8];
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) yv[k] = yl[(h * 8 + k) * Ncp + jc];
+                        asm volatile("s_waitcnt lgkmcnt(0)"
+                                     : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) g[r] = fma(xr[r][h * 8 + k], yv[k], g[r]);
+                    }
+                    // level by level, row 0 before row 1: a level's two factors are stored as soon as they exist
+                    double prev[2] = {act ? g[0] : 0.0, act ? g[1] : 0.0};
+                    const double g0 = prev[0], g1 = prev[1];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s)
+                        if (s < L - 1) {
+                            const double v = dpp_shr1_zero(qio[s]);
+                            const double p0 = lam == 0 ? 0.0 : v;
+                            const double p1 = p0 + rowS[0][s];
+                            slab[((int64_t)s * steps + t) * 64] = make_double2(p0, p1);
+                            qio[s] = p1 + rowS[1][s];
+                            rowS[0][s] += prev[0];
+                            rowS[1][s] += prev[1];
+                            prev[0] = g0 * p0;
+                            prev[1] = g1 * p1;
+                        }
+                }
+            }
+            {   // phase 2
+                double rowT[2][NS], sio[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) sio[s] = rowT[0][s] = rowT[1][s] = 0.0;
+                for (int t = steps - 1; t >= 0; --t) {
+                    const int j = t - lam;
+                    const bool act = (unsigned)j < (unsigned)N;
+                    const int jc = act ? j : 0;
+                    double g[2] = {0.0, 0.0};
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        double yv[8];
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) yv[k] = yl[(h * 8 + k) * Ncp + jc];
+                        asm volatile("s_waitcnt lgkmcnt(0)"
+                                     : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) g[r] = fma(xr[r][h * 8 + k], yv[k], g[r]);
+                    }
+                    // level by level downwards, row 1 before row 0: a level's factors and its hand-up live only while the level is computed
+                    const double g0 = act ? g[0] : 0.0, g1 = act ? g[1] : 0.0;
+                    double rb0 = 0.0, rb1 = 0.0, dG[2] = {0.0, 0.0};
+#pragma unroll
+                    for (int m = TR_LMAX; m >= 2; --m)
+                        if (m <= L) {
+                            const int s = m - 2;
+                            rb0 = m == L ? w[m - 1] : rb0;
+                            rb1 = m == L ? w[m - 1] : rb1;
+                            const double2 pf = slab[((int64_t)s * steps + t) * 64];
+                            dG[0] = fma(rb0, pf.x, dG[0]);
+                            dG[1] = fma(rb1, pf.y, dG[1]);
+                            const double v = dpp_shl1(sio[s], 0.0);
+                            const double s1 = lam == W - 1 ? 0.0 : v;
+                            const double s0 = s1 + rowT[1][s];
+                            sio[s] = s0 + rowT[0][s];
+                            rowT[1][s] += g1 * rb1;
+                            rowT[0][s] += g0 * rb0;
+                            rb1 = w[s] + s1;
+                            rb0 = w[s] + s0;
+                        }
+                    dG[0] = act ? dG[0] + (L == 1 ? w[0] : rb0) : 0.0;
+                    dG[1] = act ? dG[1] + (L == 1 ? w[0] : rb1) : 0.0;
+                    // the column again, a half at a time: the column index is tied to the recursion's results, so the reads cannot be
+                    // scheduled above it and no coordinate of y is in a register while the levels' factors and hand-ups are
+                    int jd = jc;
+                    asm volatile("" : "+v"(jd) : "v"(dG[0]), "v"(dG[1]));
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        double yv[8];
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) yv[k] = yl[(h * 8 + k) * Ncp + jd];
+                        asm volatile("s_waitcnt lgkmcnt(0)"
+                                     : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(yv[4]), "+v"(yv[5]), "+v"(yv[6]), "+v"(yv[7]));
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) dX[r][h * 8 + k] = fma(dG[r], yv[k], dX[r][h * 8 + k]);
+                    }
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int row = lam * 2 + r;
+                if (row < prm.M) {
+                    double *tp = prm.Tpart + ((chunk * prm.A + a) * prm.M + row) * 16;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) tp[k] = dX[r][k];
+                }
+            }
+        }
+    }
+}
+
 template <int OM, int RC>
 __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     extern __shared__ __attribute__((aligned(16))) double ylds[];   // [fd][Ncp]; paired: [G][fd][Ncp], one block per lane group
@@ -1158,11 +1340,12 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
         }
     }
     if constexpr (OM > 1) {
-        if (prm.adjoint) {      // 2, the POINTS mode, 3, its adjoint, 4, the LONG mode, and 5, its adjoint: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
-            if (prm.adjoint == 3) trunc_points_adjoint(prm, ylds);
+        if (prm.adjoint) {      // 2, the POINTS mode, 3, its adjoint, 4, the LONG mode, 5, its adjoint, and 6, the WIDE-ADJOINT mode: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
+            if (prm.adjoint == 6) trunc_wide_adjoint(prm, ylds);        // (first: of the three placements tried the one the other modes pay least for, profiles/truncated_wide_adjoint.txt)
+            else if (prm.adjoint == 3) trunc_points_adjoint(prm, ylds);
             else if (prm.adjoint == 4) trunc_long(prm, ylds);
             else if (prm.adjoint == 2) trunc_points(prm, ylds);
-            else trunc_long_adjoint(prm, ylds);         // (last: of the placements tried the one that moves the general loop least)
+            else trunc_long_adjoint(prm, ylds);        // (last: of the placements tried the one that moves the general loop least)
             return;
         }
     }
@@ -1438,12 +1621,13 @@ struct AdjointPlan {
     size_t block_bytes;     // a block's slab: planes x (N + W - 1) steps x 1 KB; planes = L - 1 prefix factors, and g in the points-adjoint mode
 };
 // The split of an adjoint launch.  Gram: the B pairs of a row tile in as many chunks as fill the resident blocks (at most B; lengths
-// differ by one at most).  The block count is lowered until blocks x slab fits `workspace`; false when one block does not.
-bool plan_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int planes, int paired, size_t workspace, AdjointPlan *pl) {
+// differ by one at most).  The block count is lowered until blocks x slab fits `workspace`; false when one block does not.  fd: the staging
+// width of a y block, which the paired widening counts (16: the wide-adjoint mode).
+bool plan_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int planes, int paired, size_t workspace, AdjointPlan *pl, int fd = 8) {
     const int lanes = (M + 1) / 2;
     int logW = 0;
     while ((1 << logW) < lanes) ++logW;
-    while (paired && (int64_t)(WAVE >> logW) * 8 * Ncp > TR_LDS_DOUBLES) ++logW;
+    while (paired && (int64_t)(WAVE >> logW) * fd * Ncp > TR_LDS_DOUBLES) ++logW;
     const int G = WAVE >> logW;
     const int64_t tiles = (A + G - 1) / G, resident = (int64_t)device_cu_count() * 8;
     pl->logW = logW;
@@ -1540,6 +1724,51 @@ int launch_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t 
     prm.logW = pl.logW;
     const int G = WAVE >> pl.logW;
     prm.n_pos = (A + G - 1) / G * n_chunks;
+    int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
+    const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
+    SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
+    return check_launch();
+}
+
+// THE scope of the wide-adjoint mode (the SK_OP_TRUNCATED_WIDE_ADJOINT rule of sk_route_query): the adjoint mode's at path dims 9 .. 16 -- the
+// rows and the dX accumulators of 16 coordinates in registers, the column of y read from LDS in halves (trunc_wide_adjoint).  Dims up to 8
+// are the adjoint mode's own and answer false here.
+bool truncated_wide_adjoint_in_scope(int D, int M, int N, int L, int order) {
+    return truncated_in_scope(D, M, N, L, order) && trunc_order(L, order) == 1 && D >= 9 && M <= 128;
+}
+
+int truncated_wide_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                                int64_t *blocks, size_t *slab_bytes) {
+    if (!truncated_wide_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    AdjointPlan pl;
+    if (!plan_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L - 1, paired, workspace, &pl, 16)) return SK_ERR_UNSUPPORTED;
+    *n_chunks = pl.n_chunks;
+    *blocks = pl.blocks;
+    *slab_bytes = (size_t)pl.blocks * pl.block_bytes;
+    return SK_OK;
+}
+
+int launch_truncated_wide_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                                  int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
+                                  int paired) {
+    if (!truncated_wide_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    if (fd != 16 || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
+    if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
+    AdjointPlan pl;
+    if (!plan_adjoint(A, B, M, N, Ncp, L - 1, paired, slab ? slab_bytes : 0, &pl, fd)) return SK_ERR_UNSUPPORTED;
+    TruncParams prm;
+    prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
+    prm.A = A; prm.B = B;
+    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
+    prm.order = 1; prm.out_f32 = 0;
+    prm.paired = paired != 0;
+    prm.levels = 0;
+    prm.param = 0.0;
+    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
+    prm.adjoint = 6; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
+    prm.logW = pl.logW;
+    const int G = WAVE >> pl.logW;
+    prm.n_pos = (A + G - 1) / G * n_chunks;     // the caller's chunk count (Tpart is sized by it); the plan's block count for the slab
     int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
     const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
     SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);

@@ -452,11 +452,13 @@ def _pair_slices(P, M, N, D, workspace_bytes):
 def _adjoint(be, X, Y, w, L, paired, workspace_bytes, param=None):
     """d / dX of sum_pairs sum_m w[m - 1, pair] k_m(pair) by the kernel's adjoint mode, in X's dtype; paired batches in _chunked's runs.
     `param`: X and Y hold POINTS and the k_m are those of the lift through RBFKernel(param) -- the points-adjoint mode; the string
-    "long": steps of any number -- the long-adjoint mode"""
+    "long": steps of any number -- the long-adjoint mode; the string "wide": path dims 9 .. 16 -- the wide-adjoint mode"""
     if param is None:
         call = lambda x, y, v, p: be.truncated_adjoint(x, y, v, L, p, workspace_bytes)
     elif param == "long":
         call = lambda x, y, v, p: be.truncated_long_adjoint(x, y, v, L, p, workspace_bytes)
+    elif param == "wide":
+        call = lambda x, y, v, p: be.truncated_wide_adjoint(x, y, v, L, p, workspace_bytes)
     else:
         call = lambda x, y, v, p: be.truncated_points_adjoint(x, y, v, L, param, p, workspace_bytes)
     if not paired:
@@ -552,6 +554,28 @@ class _LongLevels(torch.autograd.Function):
         return _levels_backward(ctx, grad, "long")
 
 
+class _WideLevels(torch.autograd.Function):
+    """_TruncatedLevels for STEP tensors of path dim 9 .. 16, order 1: forward = the levels mode (one launch, on (Y, X), transposed, when
+    only the second batch fits the lanes), backward = the wide-adjoint mode, one launch per batch that needs a gradient and ONE with
+    w + w^T for a symmetric call.  The caller has asked the route table for every side (TruncatedSigKernel._wide_adjoint_serves)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, L, order, paired, sym, workspace_bytes):
+        be = _lib.get_backend()
+        call = lambda x, y: be.truncated_levels(x, y, L, 1, paired=paired)
+        lev = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
+        if lev is None:
+            raise RuntimeError("the levels mode of k_trunc_sig declined a shape its route query accepted")
+        ctx.save_for_backward(X, Y)
+        ctx.mode = (L, paired, sym, workspace_bytes)
+        return lev
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        return _levels_backward(ctx, grad, "wide")
+
+
 class TruncatedSigKernel:
     """The truncated signature kernel behind SigKernel's interface: ``X`` and ``Y`` are PATHS ``(batch, length, dim)`` -- differenced here
     with torch ops, so a gradient reaches whatever produced them -- and the kernel is truncated_sig_kernel's on the steps, ``num_levels``
@@ -597,13 +621,26 @@ class TruncatedSigKernel:
     fit: at the default 1 GiB a few hundred steps already lower the block count, so pass a larger ``workspace_bytes`` for speed.  Every
     other call takes the restatement as a whole, as without the keyword, and ``sigma`` keeps its gradient either way.  The keyword does
     not depend on ``routes.truncated_long``, which keeps governing the calls without a gradient.  The default is False -- every call then
-    does what it did before the keyword existed -- and flipping it is left to a later change."""
+    does what it did before the keyword existed -- and flipping it is left to a later change.
 
-    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None, static_kernel=None, long_adjoint=False, points_adjoint=False):
+    ``wide_adjoint=True`` keeps the PLAIN kernel on the HIP route with a gradient pending at path dims 9 to 16 -- what lead-lag plus
+    add-time makes of four to seven channels: the forward is the levels launch every call without a gradient already takes there and the
+    backward the kernel's wide-adjoint mode -- the adjoint mode's two sweeps with rows and accumulators of 16 coordinates, the column of
+    y read from LDS in halves -- one launch per batch that requires grad (one in all for ``sym=True``), bit-reproducible, nothing of size
+    pairs x M x N allocated.  It takes effect at order 1 on a HIP device where the route above declined, the forward is in the kernel's
+    scope (sk_route_query(SK_OP_TRUNCATED)) and every batch that requires grad has path dim 9 to 16, at most 128 steps, at most 128 steps
+    on the other side (sk_route_query(SK_OP_TRUNCATED_WIDE_ADJOINT)) and a block's slab of (num_levels - 1) x (steps of the other side +
+    lanes - 1) KB within ``workspace_bytes``.  Every other call takes the restatement as a whole, as without the keyword -- at path dim
+    <= 8 the route above has taken the call before the keyword is looked at -- and ``sigma`` keeps its gradient either way.  The default
+    is False -- every call then does what it did before the keyword existed -- and flipping it is left to a later change."""
+
+    def __init__(self, num_levels, sigma=1., order=1, workspace_bytes=None, static_kernel=None, long_adjoint=False, wide_adjoint=False,
+                 points_adjoint=False):
         self.num_levels, self.sigma, self.order, self.workspace_bytes = num_levels, sigma, order, workspace_bytes
         self.static_kernel = static_kernel
         self.points_adjoint = bool(points_adjoint)
         self.long_adjoint = bool(long_adjoint)
+        self.wide_adjoint = bool(wide_adjoint)
 
     def _hip_serves(self, dx, dy, L, order, paired, sym):
         """the HIP function serves the call: a HIP device, no empty axis, the forward in scope on (dx, dy) or (dy, dx), and on every side
@@ -642,6 +679,26 @@ class TruncatedSigKernel:
         if dx.requires_grad and not be.truncated_long_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
             return False
         if dy.requires_grad and not sym and not be.truncated_long_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
+            return False
+        return True
+
+    def _wide_adjoint_serves(self, dx, dy, L, order, paired, sym):
+        """wide_adjoint=True applies (asked where _hip_serves declined): step tensors on a HIP device with a gradient pending, order 1, no
+        empty axis, the forward in the kernel's scope on (dx, dy) or (dy, dx), and every side that needs a gradient in the wide-adjoint
+        mode's, a block's slab within the workspace"""
+        if not (self.wide_adjoint and _on_hip(dx) and order == 1 and min(dx.shape[0], dx.shape[1], dy.shape[0], dy.shape[1]) > 0):
+            return False
+        if not (torch.is_grad_enabled() and (dx.requires_grad or dy.requires_grad)):
+            return False
+        be = _lib.get_backend()
+        if not (hasattr(be, "truncated_levels") and hasattr(be, "truncated_wide_adjoint") and hasattr(be, "truncated_wide_adjoint_fits")):
+            return False
+        (A, M, D), (B, N), es = dx.shape, dy.shape[:2], dx.element_size()
+        if be.route(_lib.OP_TRUNCATED, 1, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
+            return False
+        if dx.requires_grad and not be.truncated_wide_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
+            return False
+        if dy.requires_grad and not sym and not be.truncated_wide_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
             return False
         return True
 
@@ -700,6 +757,9 @@ class TruncatedSigKernel:
         if self._hip_serves(dx, dy, L, order, paired, sym):
             dx = dx.contiguous()
             return _TruncatedLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, order, paired, sym, self.workspace_bytes)
+        if self._wide_adjoint_serves(dx, dy, L, order, paired, sym):     # opt-in: path dims 9 .. 16, a gradient pending
+            dx = dx.contiguous()
+            return _WideLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, 1, paired, sym, self.workspace_bytes)
         if self._long_adjoint_serves(dx, dy, L, order, paired, sym):     # opt-in: steps beyond the adjoint mode's, a gradient pending
             dx = dx.contiguous()
             return _LongLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, 1, paired, sym, self.workspace_bytes)
