@@ -400,6 +400,15 @@ def _truncated_staging(D, N):
     return (8 if D <= 8 else 16), (N + 15) // 16 * 16
 
 
+# the adjoint modes of k_trunc_sig behind HipBackend.truncated_{,points_,long_,wide_}adjoint{,_fits}: (route op, plan entry point, launch entry point)
+_TRUNCATED_ADJOINTS = {
+    "plain": (OP_TRUNCATED_ADJOINT, "sk_truncated_adjoint_plan", "sk_truncated_adjoint"),
+    "points": (OP_TRUNCATED_RBF_ADJOINT, "sk_truncated_points_adjoint_plan", "sk_truncated_points_adjoint"),
+    "long": (OP_TRUNCATED_LONG_ADJOINT, "sk_truncated_long_adjoint_plan", "sk_truncated_long_adjoint"),
+    "wide": (OP_TRUNCATED_WIDE_ADJOINT, "sk_truncated_wide_adjoint_plan", "sk_truncated_wide_adjoint"),
+}
+
+
 class _WorstResidual:
     """The worst self-check residual of a fused-adjoint launch (NaN-propagating, as torch.max is), reduced only when somebody asks
     for it -- `float(r)` or `r.tensor()`: it is a diagnostic, and a backward pass should not pay a reduction kernel for it.  The
@@ -756,8 +765,9 @@ class HipBackend:
         _check(rc, "sk_truncated_long")
         return out
 
-    def _adjoint_fits(self, op, plan_name, A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size):
-        """route `op` says FUSED and one block's slab fits `workspace_bytes`, by the plan entry point `plan_name`"""
+    def _adjoint_fits(self, mode, A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size):
+        """the route op of _TRUNCATED_ADJOINTS[mode] says FUSED and one block's slab fits `workspace_bytes`, by its plan entry point"""
+        op, plan_name, _ = _TRUNCATED_ADJOINTS[mode]
         if self.route(op, 1, D, M, N, num_levels, False, elem_size) != ROUTE_FUSED:
             return False
         plan = (ctypes.c_int64 * 4)()       # (the long adjoint's plan has a fourth entry)
@@ -770,17 +780,18 @@ class HipBackend:
 
     def truncated_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
         """whether truncated_adjoint serves the shape: SK_OP_TRUNCATED_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""
-        return self._adjoint_fits(OP_TRUNCATED_ADJOINT, "sk_truncated_adjoint_plan", A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size)
+        return self._adjoint_fits("plain", A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size)
 
     def truncated_points_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
         """whether truncated_points_adjoint serves the shape (M, N in POINTS): SK_OP_TRUNCATED_RBF_ADJOINT says FUSED and one block's slab of
         num_levels x (N + lanes - 1) KB fits `workspace_bytes`"""
-        return self._adjoint_fits(OP_TRUNCATED_RBF_ADJOINT, "sk_truncated_points_adjoint_plan", A, B, M, N, D, num_levels, paired,
-                                  workspace_bytes, elem_size)
+        return self._adjoint_fits("points", A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size)
 
-    def _adjoint(self, op, plan_name, launch_name, mode_args, X, Y, w, num_levels, paired, workspace_bytes):
-        """the one adjoint call of k_trunc_sig behind truncated_adjoint and truncated_points_adjoint: route `op`, the plan, the staging, the
-        launch (`mode_args` go between num_levels and w) and the sum over the chunks' parts; None outside the scope or the workspace"""
+    def _adjoint(self, mode, mode_args, X, Y, w, num_levels, paired, workspace_bytes):
+        """the one adjoint call of k_trunc_sig behind the four truncated_*adjoint methods: the route op of _TRUNCATED_ADJOINTS[mode], the
+        plan, the staging, the launch (`mode_args` go between num_levels and w) and the sum over the chunks' parts; None outside the scope
+        or the workspace"""
+        op, plan_name, launch_name = _TRUNCATED_ADJOINTS[mode]
         _dev(X, "X")
         _dev(Y, "Y")
         (A, M, D), (B, N), L = X.shape, Y.shape[:2], int(num_levels)
@@ -814,8 +825,7 @@ class HipBackend:
         the scope (sk_route_query(SK_OP_TRUNCATED_RBF_ADJOINT) != FUSED) or when one block's slab does not fit `workspace_bytes`."""
         if not float(param) > 0:
             return None
-        return self._adjoint(OP_TRUNCATED_RBF_ADJOINT, "sk_truncated_points_adjoint_plan", "sk_truncated_points_adjoint", (1.0 / float(param),),
-                             X, Y, w, num_levels, paired, workspace_bytes)
+        return self._adjoint("points", (1.0 / float(param),), X, Y, w, num_levels, paired, workspace_bytes)
 
     def truncated_adjoint(self, X, Y, w, num_levels, paired=False, workspace_bytes=None):
         """The gradient of ``sum_pairs sum_m w[m - 1, pair] k_m(pair)`` with respect to X, by k_trunc_sig<1, 2> in its adjoint mode
@@ -824,13 +834,11 @@ class HipBackend:
         torch adds the chunks; between its two sweeps of a pair a block keeps the prefix factors in a slab of (num_levels - 1) x
         (N + lanes - 1) KB, all blocks' within `workspace_bytes` (default 1 GiB; the block count is lowered until they fit).  None
         outside the scope (sk_route_query(SK_OP_TRUNCATED_ADJOINT) != FUSED: order 1, dim <= 8) or when one block's slab does not fit."""
-        return self._adjoint(OP_TRUNCATED_ADJOINT, "sk_truncated_adjoint_plan", "sk_truncated_adjoint", (), X, Y, w, num_levels, paired,
-                             workspace_bytes)
+        return self._adjoint("plain", (), X, Y, w, num_levels, paired, workspace_bytes)
 
     def truncated_long_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
         """whether truncated_long_adjoint serves the shape: SK_OP_TRUNCATED_LONG_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""
-        return self._adjoint_fits(OP_TRUNCATED_LONG_ADJOINT, "sk_truncated_long_adjoint_plan", A, B, M, N, D, num_levels, paired,
-                                  workspace_bytes, elem_size)
+        return self._adjoint_fits("long", A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size)
 
     def truncated_long_adjoint(self, X, Y, w, num_levels, paired=False, workspace_bytes=None):
         """truncated_adjoint's gradient on paths of ANY length, by k_trunc_sig<4, 1> in its long-adjoint mode (sk_truncated_long_adjoint):
@@ -839,13 +847,11 @@ class HipBackend:
         (N + tiles x (lanes - 1)) KB, and with more than one band (bands + 2) x (num_levels - 1) x ceil64(N) doubles of carries, all blocks'
         within `workspace_bytes` (default 1 GiB; the block count is lowered from 8 per CU until they fit, so long paths want more).  None
         outside the scope (sk_route_query(SK_OP_TRUNCATED_LONG_ADJOINT) != FUSED: order 1, dim <= 8) or when one block's slab does not fit."""
-        return self._adjoint(OP_TRUNCATED_LONG_ADJOINT, "sk_truncated_long_adjoint_plan", "sk_truncated_long_adjoint", (), X, Y, w, num_levels,
-                             paired, workspace_bytes)
+        return self._adjoint("long", (), X, Y, w, num_levels, paired, workspace_bytes)
 
     def truncated_wide_adjoint_fits(self, A, B, M, N, D, num_levels, paired=False, workspace_bytes=None, elem_size=8):
         """whether truncated_wide_adjoint serves the shape: SK_OP_TRUNCATED_WIDE_ADJOINT says FUSED and one block's slab fits `workspace_bytes`"""
-        return self._adjoint_fits(OP_TRUNCATED_WIDE_ADJOINT, "sk_truncated_wide_adjoint_plan", A, B, M, N, D, num_levels, paired,
-                                  workspace_bytes, elem_size)
+        return self._adjoint_fits("wide", A, B, M, N, D, num_levels, paired, workspace_bytes, elem_size)
 
     def truncated_wide_adjoint(self, X, Y, w, num_levels, paired=False, workspace_bytes=None):
         """truncated_adjoint's gradient at path dims 9 .. 16, by k_trunc_sig<4, 1> in its wide-adjoint mode (sk_truncated_wide_adjoint):
@@ -853,8 +859,7 @@ class HipBackend:
         block's slab (num_levels - 1) x (N + lanes - 1) KB, all blocks' within `workspace_bytes` (default 1 GiB; the block count is lowered
         until they fit).  None outside the scope (sk_route_query(SK_OP_TRUNCATED_WIDE_ADJOINT) != FUSED: order 1, 9 <= dim <= 16, at most
         128 steps on either side) or when one block's slab does not fit."""
-        return self._adjoint(OP_TRUNCATED_WIDE_ADJOINT, "sk_truncated_wide_adjoint_plan", "sk_truncated_wide_adjoint", (), X, Y, w, num_levels,
-                             paired, workspace_bytes)
+        return self._adjoint("wide", (), X, Y, w, num_levels, paired, workspace_bytes)
 
     def loss_forward(self, kind, param, X, Y, dyadic, naive, with_yy, keep_edges):
         """The loss wrappers' forward in THREE launches (csrc/sk_loss.hip): [X; Y] staged in both layouts straight from the two

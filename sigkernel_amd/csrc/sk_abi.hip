@@ -189,6 +189,36 @@ int truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrow
                                 param);
 }
 
+// the four sk_truncated_*adjoint_plan entry points: plan[0..2] = the chunk count, the blocks, the launch's slab bytes; block_entry:
+// plan[3] = ONE block's slab bytes (the long adjoint's plan has that fourth entry, the others leave it alone)
+int truncated_adjoint_plan_abi(int mode, int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
+                               int64_t *plan, bool block_entry) {
+    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
+    size_t block = 0;
+    const int rc = truncated_adjoint_plan(mode, A, B, M, N, D, num_levels, paired, workspace_bytes, plan, plan + 1, &block);
+    if (rc == SK_OK) {
+        plan[2] = plan[1] * (int64_t)block;
+        if (block_entry) plan[3] = (int64_t)block;
+    }
+    return rc;
+}
+
+// the four sk_truncated_*adjoint entry points; argument checks before any HIP call.  What they do differently is an argument each:
+// pairs_must_match: paired with A != B is SK_ERR_BAD_ARG (else paired ignores B, as the forward entry points do); slab_required: a slab
+// and its byte count must be there (else only a byte count without a slab is refused); param_required: param must be positive (else it is
+// not read)
+int truncated_adjoint_abi(int mode, const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                          int num_levels, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes,
+                          void *stream, int paired, bool pairs_must_match, bool slab_required, bool param_required) {
+    if (paired && !pairs_must_match) B = A;
+    if (D < 1 || !Xr || !Yt || !w || !Tpart || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D ||
+        (slab_required ? !slab || !slab_bytes : slab_bytes && !slab) || (paired && A != B) || (param_required && !(param > 0.0)))
+        return SK_ERR_BAD_ARG;
+    if (A == 0 || B == 0) return SK_OK;
+    return launch_truncated_adjoint(mode, Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, param, w, Tpart, n_chunks, slab, slab_bytes,
+                                    (hipStream_t)stream, paired);
+}
+
 }  // namespace
 
 // ---- the one place that reads the environment: SK_* tuning knobs, parsed when the library is loaded ------------------------
@@ -541,81 +571,43 @@ int sk_truncated_long_f32(const double *Xr, const double *Yt, int64_t A, int64_t
     return truncated<float>(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, order, sigma, out, stream, paired, levels, 0, 0.0, true, slab, slab_bytes);
 }
 int sk_truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes, int64_t *plan) {
-    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
-    size_t slab = 0;
-    const int rc = truncated_adjoint_plan(A, B, M, N, D, num_levels, paired, workspace_bytes, plan, plan + 1, &slab);
-    if (rc == SK_OK) plan[2] = (int64_t)slab;
-    return rc;
+    return truncated_adjoint_plan_abi(TR_ADJOINT, A, B, M, N, D, num_levels, paired, workspace_bytes, plan, false);
 }
 int sk_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                          int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
                          int paired) {
-    if (paired) B = A;
-    if (D < 1 || !Xr || !Yt || !w || !Tpart || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D ||
-        (slab_bytes && !slab))
-        return SK_ERR_BAD_ARG;
-    if (A == 0 || B == 0) return SK_OK;
-    return launch_truncated_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, w, Tpart, n_chunks, slab, slab_bytes,
-                                    (hipStream_t)stream, paired);
+    return truncated_adjoint_abi(TR_ADJOINT, Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, 0.0, w, Tpart, n_chunks, slab, slab_bytes, stream,
+                                 paired, false, false, false);
 }
 int sk_truncated_long_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
                                    int64_t *plan) {
-    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
-    size_t block = 0;
-    const int rc = truncated_long_adjoint_plan(A, B, M, N, D, num_levels, paired, workspace_bytes, plan, plan + 1, &block);
-    if (rc == SK_OK) {
-        plan[2] = plan[1] * (int64_t)block;
-        plan[3] = (int64_t)block;
-    }
-    return rc;
+    return truncated_adjoint_plan_abi(TR_LONG_ADJOINT, A, B, M, N, D, num_levels, paired, workspace_bytes, plan, true);
 }
 int sk_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                               int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
                               int paired) {
-    if (paired) B = A;
-    if (D < 1 || !Xr || !Yt || !w || !Tpart || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D ||
-        (slab_bytes && !slab))
-        return SK_ERR_BAD_ARG;
-    if (A == 0 || B == 0) return SK_OK;
-    return launch_truncated_long_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, w, Tpart, n_chunks, slab, slab_bytes,
-                                         (hipStream_t)stream, paired);
+    return truncated_adjoint_abi(TR_LONG_ADJOINT, Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, 0.0, w, Tpart, n_chunks, slab, slab_bytes,
+                                 stream, paired, false, false, false);
 }
 int sk_truncated_wide_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
                                    int64_t *plan) {
-    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
-    size_t slab = 0;
-    const int rc = truncated_wide_adjoint_plan(A, B, M, N, D, num_levels, paired, workspace_bytes, plan, plan + 1, &slab);
-    if (rc == SK_OK) plan[2] = (int64_t)slab;
-    return rc;
+    return truncated_adjoint_plan_abi(TR_WIDE_ADJOINT, A, B, M, N, D, num_levels, paired, workspace_bytes, plan, false);
 }
 int sk_truncated_wide_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                               int num_levels, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, void *stream,
                               int paired) {
-    if (D < 1 || !Xr || !Yt || !w || !Tpart || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D ||
-        (slab_bytes && !slab) || (paired && A != B))
-        return SK_ERR_BAD_ARG;
-    if (A == 0 || B == 0) return SK_OK;
-    return launch_truncated_wide_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, w, Tpart, n_chunks, slab, slab_bytes,
-                                         (hipStream_t)stream, paired);
+    return truncated_adjoint_abi(TR_WIDE_ADJOINT, Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, 0.0, w, Tpart, n_chunks, slab, slab_bytes,
+                                 stream, paired, true, false, false);
 }
 int sk_truncated_points_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int num_levels, int paired, size_t workspace_bytes,
                                      int64_t *plan) {
-    if (!plan || A < 1 || B < 1 || M < 1 || N < 1 || D < 1 || num_levels < 1) return SK_ERR_BAD_ARG;
-    size_t slab = 0;
-    const int rc = truncated_points_adjoint_plan(A, B, M, N, D, num_levels, paired, workspace_bytes, plan, plan + 1, &slab);
-    if (rc == SK_OK) plan[2] = (int64_t)slab;
-    return rc;
+    return truncated_adjoint_plan_abi(TR_POINTS_ADJOINT, A, B, M, N, D, num_levels, paired, workspace_bytes, plan, false);
 }
 int sk_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
                                 int num_levels, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab,
                                 size_t slab_bytes, void *stream, int paired) {
-    if (paired) B = A;
-    if (D < 1 || !Xr || !Yt || !w || !Tpart || A < 0 || B < 0 || M < 1 || N < 1 || num_levels < 1 || Mrows < M || Ncp < N || fd < D ||
-        !(param > 0.0) || !slab || !slab_bytes)
-        return SK_ERR_BAD_ARG;
-    if (A == 0 || B == 0) return SK_OK;
-    return launch_truncated_points_adjoint(Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, param, w, Tpart, n_chunks, slab, slab_bytes,
-                                           (hipStream_t)stream, paired);
+    return truncated_adjoint_abi(TR_POINTS_ADJOINT, Xr, Yt, A, B, Mrows, M, N, Ncp, D, fd, num_levels, param, w, Tpart, n_chunks, slab,
+                                 slab_bytes, stream, paired, false, true, true);
 }
 int sk_solve_prefix_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, void *queue, void *stream) {

@@ -197,24 +197,6 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
                      int order, const double *sigma, TO *out, hipStream_t s, int paired = 0, int levels = 0, int kind = 0, double param = 0.0);
 bool truncated_in_scope(int D, int M, int N, int L, int order);   // the kernel's scope = the SK_OP_TRUNCATED rule of sk_route_query
 bool truncated_points_in_scope(int D, int M, int N, int L, int order);   // ... of its points mode = the SK_OP_TRUNCATED_RBF rule
-// The ADJOINT mode of k_trunc_sig<1, 2> (order 1, dim <= 8): Tpart [n_chunks][A][M][8] takes the chunks' parts of the gradient of
-// sum_pairs sum_m w[m - 1][pair] k_m(pair) with respect to the rows of x; w [L][A][B] (paired [L][A]) on the device.  slab: slab_bytes of
-// device memory for the prefix factors a block keeps between its two phases (none at L = 1).  The plan gives the chunk count, the
-// blocks and the slab bytes of a shape within `workspace` bytes; SK_ERR_UNSUPPORTED outside the scope or when one block's slab does not fit.
-int truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks, int64_t *blocks,
-                           size_t *slab_bytes);
-int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
-                             const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s, int paired);
-bool truncated_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_ADJOINT rule of sk_route_query
-// The POINTS-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (order 1, dim <= 8): the same gradient for the kernel lifted through the RBF static
-// kernel, with respect to the POINTS of x -- M and N count points, param = 1 / sigma of the RBF kernel, Tpart [n_chunks][A][M][8], w as
-// above.  A block's slab holds one plane more than the plain adjoint's: the node's g beside its L - 1 prefix factors.
-int truncated_points_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
-                                  int64_t *blocks, size_t *slab_bytes);
-int launch_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
-                                    int L, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes,
-                                    hipStream_t s, int paired);
-bool truncated_points_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_RBF_ADJOINT rule of sk_route_query
 // The LONG mode of k_trunc_sig<TR_OMAX, 1> (order 1, forward only): any number of steps on either side -- the rows in bands of 128 with the
 // last row's hand-down carried through `slab`, the columns in tiles of the y block.  paired, levels, sigma, out as launch_truncated's at
 // kind 0.  The plan gives the blocks and ONE block's slab bytes, (L - 1) x ceil64(N) doubles (0 with one band or one level), the blocks
@@ -226,27 +208,32 @@ int launch_truncated_long(const double *Xr, const double *Yt, int64_t A, int64_t
 bool truncated_long_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_LONG rule of sk_route_query
 int truncated_long_logw(int M, int Ncp, int fd, int paired);           // log2 of the lanes of a pair's group in that mode
 int64_t truncated_long_steps(int D, int M, int N);                     // sk_route.hip: the lane-steps of a pair in that mode
-// The LONG-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (order 1, dim <= 8): launch_truncated_adjoint's gradient on any number of steps -- the
-// reverse sweep in the long mode's bands and tiles.  Tpart, w and n_chunks as there.  A block's slab: the prefix factors of ONE band,
-// (L - 1) x (N + tiles (W - 1)) KB, and with more than one band (bands + 2) x (L - 1) x ceil64(N) doubles of forward and reverse carries.
+// What a launch of k_trunc_sig does (TruncParams::mode, launch-time and wave-uniform).  The forward modes are launch_truncated's (kind 0 / 1)
+// and launch_truncated_long's; the four ADJOINT modes are the argument of the plan and the launcher below.
+enum TruncMode : int { TR_FORWARD = 0, TR_ADJOINT = 1, TR_POINTS = 2, TR_POINTS_ADJOINT = 3, TR_LONG = 4, TR_LONG_ADJOINT = 5, TR_WIDE_ADJOINT = 6 };
+// The adjoint modes (order 1): Tpart [n_chunks][A][M][fd] takes the chunks' parts of the gradient of sum_pairs sum_m w[m - 1][pair] k_m(pair)
+// with respect to the rows of x; w [L][A][B] (paired [L][A]) on the device.  slab: slab_bytes of device memory for what a block keeps between
+// its sweeps of a pair (none at L = 1, except in the points-adjoint mode).
+//   TR_ADJOINT         k_trunc_sig<1, 2>; dim <= 8, at most 128 steps, fd = 8.  A block's slab: the prefix factors, (L - 1) x (N + W - 1) KB.
+//   TR_POINTS_ADJOINT  k_trunc_sig<TR_OMAX, 1>, as the modes below; the same gradient for the kernel lifted through the RBF static kernel, with
+//                      respect to the POINTS of x -- M and N count points, param = 1 / sigma of the RBF kernel (read by this mode only).  One
+//                      slab plane more: the node's g beside its L - 1 prefix factors.
+//   TR_LONG_ADJOINT    dim <= 8, any number of steps -- the reverse sweep in the long mode's bands and tiles.  A block's slab: the prefix
+//                      factors of ONE band, (L - 1) x (N + tiles (W - 1)) KB, and with more than one band (bands + 2) x (L - 1) x ceil64(N)
+//                      doubles of forward and reverse carries.
+//   TR_WIDE_ADJOINT    dims 9 .. 16, at most 128 steps, fd = 16; slab as TR_ADJOINT's.  In paired mode the lane groups widen until their y
+//                      blocks of 16 x Ncp doubles fit the wave's LDS.  Dims up to 8 are outside its scope: TR_ADJOINT serves them.
 // The plan gives the chunk count, the blocks -- lowered from 8 per CU until their slabs fit `workspace` -- and ONE block's slab bytes;
-// SK_ERR_UNSUPPORTED outside the scope or when one block's slab does not fit.
-int truncated_long_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
-                                int64_t *blocks, size_t *block_bytes);
-int launch_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
-                                  int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
-                                  int paired);
-bool truncated_long_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_LONG_ADJOINT rule of sk_route_query
-// The WIDE-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (order 1, dims 9 .. 16, at most 128 steps): launch_truncated_adjoint's gradient at fd = 16 --
-// Tpart [n_chunks][A][M][16]; w, n_chunks, the slab of (L - 1) x (N + W - 1) KB a block and the plan as there.  In paired mode the lane groups
-// widen until their y blocks of 16 x Ncp doubles fit the wave's LDS.  SK_ERR_UNSUPPORTED outside the scope (dims up to 8 included: the
-// adjoint mode serves them) or when one block's slab does not fit.
-int truncated_wide_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
-                                int64_t *blocks, size_t *slab_bytes);
-int launch_truncated_wide_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
-                                  int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
-                                  int paired);
-bool truncated_wide_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_WIDE_ADJOINT rule of sk_route_query
+// SK_ERR_UNSUPPORTED outside the mode's scope or when one block's slab does not fit, SK_ERR_BAD_ARG for a mode that is no adjoint mode.
+int truncated_adjoint_plan(int mode, int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                           int64_t *blocks, size_t *block_bytes);
+int launch_truncated_adjoint(int mode, const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                             int L, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes,
+                             hipStream_t s, int paired);
+bool truncated_adjoint_in_scope(int D, int M, int N, int L, int order);          // = the SK_OP_TRUNCATED_ADJOINT rule of sk_route_query
+bool truncated_points_adjoint_in_scope(int D, int M, int N, int L, int order);   // = the SK_OP_TRUNCATED_RBF_ADJOINT rule
+bool truncated_long_adjoint_in_scope(int D, int M, int N, int L, int order);     // = the SK_OP_TRUNCATED_LONG_ADJOINT rule
+bool truncated_wide_adjoint_in_scope(int D, int M, int N, int L, int order);     // = the SK_OP_TRUNCATED_WIDE_ADJOINT rule
 
 // ---- sk_loss.hip: the glue of the loss wrappers (compute_mmd / scoring rules) as single launches ----
 template <typename T>

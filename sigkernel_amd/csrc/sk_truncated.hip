@@ -30,23 +30,23 @@
 // instead of their weighted sum, out[m][pair].  The step loop is the plain launch's, run with the weights (0, .., 0, 1): acc is then
 // level L, and the totals of the levels below are the running row sums rowS the loop keeps anyway.  The mode is an epilogue: a sum over
 // the lane's rows and the group's butterfly per level, and L + 1 stores per pair where the plain launch has one.
-// ADJOINT mode (TruncParams::adjoint, launch-time and wave-uniform, the <1, 2> instance only: order 1, fd = 8): the gradient of a weighted
+// ADJOINT mode (TruncParams::mode = TR_ADJOINT, launch-time and wave-uniform, the <1, 2> instance only: order 1, fd = 8): the gradient of a weighted
 // sum of the pairs' level terms with respect to the rows of x, in Gram and paired mode -- trunc_adjoint below, with loops of its own; the
 // forward launches run the step loop they ran.
-// POINTS mode (TruncParams::adjoint = 2, launch-time and wave-uniform; order 1; Gram, paired and levels): the kernel of Kiraly and Oberhauser
+// POINTS mode (TruncParams::mode = TR_POINTS, launch-time and wave-uniform; order 1; Gram, paired and levels): the kernel of Kiraly and Oberhauser
 // lifted through the RBF static kernel -- x and y staged as POINTS, G the second difference of exp(-|x - y|^2 param) on the grid of points,
 // evaluated in the sweep: trunc_points below, with a loop of its own, compiled into the <TR_OMAX, 1> instance; the forward launches run
 // the step loop they ran.
-// POINTS-ADJOINT mode (TruncParams::adjoint = 3, launch-time and wave-uniform; order 1, fd = 8; Gram and paired): the gradient of a weighted
+// POINTS-ADJOINT mode (TruncParams::mode = TR_POINTS_ADJOINT, launch-time and wave-uniform; order 1, fd = 8; Gram and paired): the gradient of a weighted
 // sum of the LIFTED kernel's level terms with respect to the points of x -- trunc_points_adjoint below, the two phases of trunc_adjoint on
 // the grid of points with the chain rule through kap; hosted by the <TR_OMAX, 1> instance beside trunc_points.
-// LONG mode (TruncParams::adjoint = 4, launch-time and wave-uniform; order 1, fd = 8 or 16; Gram, paired and levels; forward only): paths of
+// LONG mode (TruncParams::mode = TR_LONG, launch-time and wave-uniform; order 1, fd = 8 or 16; Gram, paired and levels; forward only): paths of
 // any length -- trunc_long below: the rows in bands of 128 with the hand-down of a band's last row carried through HBM, the columns in tiles of
 // the y block with the row sums kept in registers; hosted by the <TR_OMAX, 1> instance beside the points modes.
-// LONG-ADJOINT mode (TruncParams::adjoint = 5, launch-time and wave-uniform; order 1, fd = 8; Gram and paired): the adjoint mode's gradient on
+// LONG-ADJOINT mode (TruncParams::mode = TR_LONG_ADJOINT, launch-time and wave-uniform; order 1, fd = 8; Gram and paired): the adjoint mode's gradient on
 // paths of any length -- trunc_long_adjoint below: the reverse recursion split as the long mode splits the forward, the forward carries kept
 // per band, a reverse carry handed up between the bands; hosted by the <TR_OMAX, 1> instance beside the long mode.
-// WIDE-ADJOINT mode (TruncParams::adjoint = 6, launch-time and wave-uniform; order 1, fd = 16; Gram and paired): the adjoint mode's gradient at
+// WIDE-ADJOINT mode (TruncParams::mode = TR_WIDE_ADJOINT, launch-time and wave-uniform; order 1, fd = 16; Gram and paired): the adjoint mode's gradient at
 // path dims 9 .. 16 on at most 128 steps -- trunc_wide_adjoint below: trunc_adjoint's two phases with rows and dX of 16 coordinates, the
 // column of y read from LDS in halves; hosted by the <TR_OMAX, 1> instance beside the other modes.
 // The level loop is unrolled to TR_LMAX with wave-uniform guards (launch-time level count and order); the template holds the LARGEST
@@ -70,23 +70,24 @@ struct TruncParams {
     int levels;         // 0: one weighted value per pair; 1: the pair's L + 1 level terms, one plane of `out` per level
     double sigma[TR_LMAX + 1];
     // ADJOINT mode (order 1, fd = 8: trunc_adjoint below).  `out` is not used.
-    int adjoint;        // 0: a forward launch; 1: dX of sum_pairs sum_m w[m][pair] k_m; 2: the POINTS mode, a forward launch on points (below);
-                        // 3: the POINTS-ADJOINT mode, 1 for the lifted kernel (slab: L planes, the last one g)
-                        // 4: the LONG mode, a forward launch on any number of steps (trunc_long; slab: [blocks][L - 1][ceil64(N)], the carry
-                        // between a pair's row bands)
-                        // 5: the LONG-ADJOINT mode, 1 on any number of steps (trunc_long_adjoint; slab per block: the factors of one band,
+    int mode;           // a TruncMode (sk_internal.h).  TR_FORWARD: a forward launch; TR_ADJOINT: dX of sum_pairs sum_m w[m][pair] k_m;
+                        // TR_POINTS: the POINTS mode, a forward launch on points (below);
+                        // TR_POINTS_ADJOINT: TR_ADJOINT for the lifted kernel (slab: L planes, the last one g)
+                        // TR_LONG: the LONG mode, a forward launch on any number of steps (trunc_long; slab: [blocks][L - 1][ceil64(N)], the
+                        // carry between a pair's row bands)
+                        // TR_LONG_ADJOINT: TR_ADJOINT on any number of steps (trunc_long_adjoint; slab per block: the factors of one band,
                         // [N + tiles (W - 1)][L - 1][128], then with more than one band the forward carries [bands][ceil64(N)][L - 1] and the
                         // two halves of the reverse carry [2][ceil64(N)][L - 1])
-                        // 6: the WIDE-ADJOINT mode, 1 at fd = 16 (trunc_wide_adjoint; slab and w as 1, Tpart [n_chunks][A][M][16])
+                        // TR_WIDE_ADJOINT: TR_ADJOINT at fd = 16 (trunc_wide_adjoint; slab and w as there, Tpart [n_chunks][A][M][16])
     int64_t n_chunks;   // Gram: the B pairs of a row tile go to this many positions; paired: 1
     const double *w;    // [L][A][B], paired [L][A]: the weight of level m + 1 of every pair
     double *Tpart;      // [n_chunks][A][M][8]: the chunks' parts of dX, summed by the caller
     double *slab;       // [blocks][L - 1][N + W - 1][128]: a block's prefix factors between its two phases
     // POINTS mode (order 1: trunc_points below); behind everything else, so that no field the other modes read moves
-    double param;       // adjoint == 2: one over the RBF kernel's sigma
+    double param;       // TR_POINTS and its adjoint: one over the RBF kernel's sigma
 };
 
-// ADJOINT mode of k_trunc_sig<1, 2> (TruncParams::adjoint, launch-time and wave-uniform): the gradient with respect to the rows of x of
+// ADJOINT mode of k_trunc_sig<1, 2> (TruncParams::mode = TR_ADJOINT, launch-time and wave-uniform): the gradient with respect to the rows of x of
 //     sum_pairs sum_{m = 1 .. L} w_m(pair) k_m(pair),      k_m = sum_nodes R^m,  R^1 = G,  R^{m+1} = G P^m,  P^m = exclusive 2-D prefix of R^m.
 // With Rb^L = w_L and Rb^m = w_m + (exclusive 2-D SUFFIX of G Rb^{m+1}):  dG = sum_m Rb^m P^{m-1} (P^0 = 1),  dx_i = sum_j dG[i][j] y_j.
 // Rb needs G and w only, so the reverse sweep is the forward one mirrored; what it needs from the forward are the L - 1 prefix factors
@@ -257,7 +258,7 @@ __device__ __forceinline__ void trunc_adjoint(const TruncParams &prm, double *yl
     }
 }
 
-// POINTS mode (TruncParams::adjoint = 2, launch-time and wave-uniform; order 1, two rows per lane, fd = 8 or 16; Gram, paired and levels):
+// POINTS mode (TruncParams::mode = TR_POINTS, launch-time and wave-uniform; order 1, two rows per lane, fd = 8 or 16; Gram, paired and levels):
 // the forward sweep on the M x N grid of POINTS with G the second difference of kap(x, y) = exp(-|x - y|^2 param).  The pair order, the
 // staging, the skew, the hand-downs and both epilogues are the order-1 forward launches'; the loop is this mode's own, and it is compiled
 // into k_trunc_sig<TR_OMAX, 1>, not into <1, 2> whose rows-per-lane it shares: the function does not depend on the template arguments, and
@@ -417,7 +418,7 @@ __device__ __forceinline__ void trunc_points(const TruncParams &prm, double *yld
     }
 }
 
-// POINTS-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 3, launch-time and wave-uniform; order 1, two rows per lane, fd = 8):
+// POINTS-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::mode = TR_POINTS_ADJOINT, launch-time and wave-uniform; order 1, two rows per lane, fd = 8):
 // the gradient with respect to the POINTS of x of  sum_pairs sum_m w_m(pair) k_m(pair)  for the lifted kernel of trunc_points.  With dG the
 // gradient with respect to g on the nodes (i, c >= 1) -- trunc_adjoint's reverse recursion, word for word -- and zero everywhere else,
 //     H(i, c) = dG(i, c) - dG(i, c + 1) - dG(i + 1, c) + dG(i + 1, c + 1)             is the gradient with respect to kap(i, c), and
@@ -634,7 +635,7 @@ __device__ __forceinline__ double lane_read(double v, int l) {
 
 typedef double trunc_d2 __attribute__((ext_vector_type(2)));       // 16 bytes of LDS as one asm operand
 
-// LONG mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 4, launch-time and wave-uniform; order 1, two rows per lane, fd = 8 or 16; Gram,
+// LONG mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::mode = TR_LONG, launch-time and wave-uniform; order 1, two rows per lane, fd = 8 or 16; Gram,
 // paired and levels; forward only): ANY number of steps on either side.  The node's recursion is the order-1 step loop's (phase 1 of
 // trunc_adjoint with the sums kept); an order-1 level is G times the exclusive 2-D prefix of the level below, and that prefix splits exactly:
 //   ROW BANDS  the rows go 2 W at a time (bands exist only beyond 128 rows: W = 64, one pair per wave; up to 128 rows the lane groups are
@@ -827,7 +828,7 @@ __device__ __forceinline__ void trunc_long(const TruncParams &prm, double *ylds)
     }
 }
 
-// LONG-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 5, launch-time and wave-uniform; order 1, two rows per lane, fd = 8; Gram
+// LONG-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::mode = TR_LONG_ADJOINT, launch-time and wave-uniform; order 1, two rows per lane, fd = 8; Gram
 // and paired): trunc_adjoint's gradient -- dX of sum_pairs sum_m w_m(pair) k_m(pair) -- on ANY number of steps.  The reverse recursion is the
 // forward one mirrored, so it splits as trunc_long splits the forward.  Per pair a block runs 2 bands - 1 JOBS:
 //   bands - 1 CARRY jobs (bands 0 .. bands - 2; none with one band): trunc_long's band/tile loop without its sums.  What the last row of band
@@ -1143,7 +1144,7 @@ __device__ __forceinline__ void trunc_long_adjoint(const TruncParams &prm, doubl
     }
 }
 
-// WIDE-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::adjoint = 6, launch-time and wave-uniform; order 1, two rows per lane, fd = 16;
+// WIDE-ADJOINT mode of k_trunc_sig<TR_OMAX, 1> (TruncParams::mode = TR_WIDE_ADJOINT, launch-time and wave-uniform; order 1, two rows per lane, fd = 16;
 // Gram and paired): trunc_adjoint's gradient at path dims 9 .. 16, on at most 128 steps.  Pairs, chunks, liveness, the two phases, the slab and
 // its indexing, the hand-ups and Tpart (rows of 16 doubles here) are trunc_adjoint's, and so is the arithmetic, operation for operation (a
 // batch padded with zero coordinates gives trunc_adjoint's bits).  What differs is what a lane keeps in registers: xr[2][16] and dX[2][16]
@@ -1334,18 +1335,18 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
     const int steps = N + W - 1;
     const bool paired = prm.paired != 0;
     if constexpr (OM == 1 && RC == 2) {
-        if (prm.adjoint) {      // its own two loops: the forward launches' step loop below is as it was
+        if (prm.mode != TR_FORWARD) {      // TR_ADJOINT, its own two loops: the forward launches' step loop below is as it was
             trunc_adjoint(prm, ylds);
             return;
         }
     }
     if constexpr (OM > 1) {
-        if (prm.adjoint) {      // 2, the POINTS mode, 3, its adjoint, 4, the LONG mode, 5, its adjoint, and 6, the WIDE-ADJOINT mode: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
-            if (prm.adjoint == 6) trunc_wide_adjoint(prm, ylds);        // (first: of the three placements tried the one the other modes pay least for, profiles/truncated_wide_adjoint.txt)
-            else if (prm.adjoint == 3) trunc_points_adjoint(prm, ylds);
-            else if (prm.adjoint == 4) trunc_long(prm, ylds);
-            else if (prm.adjoint == 2) trunc_points(prm, ylds);
-            else trunc_long_adjoint(prm, ylds);        // (last: of the placements tried the one that moves the general loop least)
+        if (prm.mode != TR_FORWARD) {      // the POINTS mode, its adjoint, the LONG mode, its adjoint, and the WIDE-ADJOINT mode: hosted by THIS instance (see trunc_points), so that <1, 2> stays the code it was
+            if (prm.mode == TR_WIDE_ADJOINT) trunc_wide_adjoint(prm, ylds);        // (first: of the three placements tried the one the other modes pay least for, profiles/truncated_wide_adjoint.txt)
+            else if (prm.mode == TR_POINTS_ADJOINT) trunc_points_adjoint(prm, ylds);
+            else if (prm.mode == TR_LONG) trunc_long(prm, ylds);
+            else if (prm.mode == TR_POINTS) trunc_points(prm, ylds);
+            else trunc_long_adjoint(prm, ylds);        // (TR_LONG_ADJOINT, last: of the placements tried the one that moves the general loop least)
             return;
         }
     }
@@ -1551,6 +1552,35 @@ __global__ __launch_bounds__(WAVE) void k_trunc_sig(const TruncParams prm) {
 inline int trunc_fd(int D) { return D <= 8 ? 8 : 16; }
 inline int trunc_order(int L, int order) { return (order < 1 || order > L) ? L : order; }
 
+// log2 of the lanes of a pair's group: the power of two that holds `lanes`.  paired: every lane group of a wave keeps a y block of its own
+// -- fewer, wider groups until they fit (one group always does)
+inline int trunc_logw(int lanes, int fd, int Ncp, int paired) {
+    int logW = 0;
+    while ((1 << logW) < lanes) ++logW;
+    while (paired && (int64_t)(WAVE >> logW) * fd * Ncp > TR_LDS_DOUBLES) ++logW;
+    return logW;
+}
+
+// THE one place a launch's TruncParams is filled, whatever the mode: the shape and the flags; sigma[] -- one-hot at L in levels mode, else
+// the caller's L + 1 weights, all zero where there are none (the adjoint modes); the adjoint modes' pointers.  logW and n_pos come from the
+// launcher's plan.
+TruncParams trunc_params(int mode, const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int fd, int L,
+                         int order, int paired, double param, void *out, bool out_f32, int levels, const double *sigma, int64_t n_chunks,
+                         const double *w, double *Tpart, double *slab) {
+    TruncParams prm;
+    prm.Xr = Xr; prm.Yt = Yt; prm.out = out;
+    prm.A = A; prm.B = B; prm.n_pos = 0;
+    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
+    prm.order = order; prm.logW = 0;
+    prm.out_f32 = out_f32;
+    prm.paired = paired != 0;
+    prm.levels = levels != 0;
+    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = levels ? (m == L ? 1.0 : 0.0) : (sigma && m <= L ? sigma[m] : 0.0);
+    prm.mode = mode; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
+    prm.param = param;
+    return prm;
+}
+
 }  // namespace
 
 // THE scope of the kernel (the SK_OP_TRUNCATED rule of sk_route_query): rows of the FIRST batch per pair M, columns N, path dim D.
@@ -1571,6 +1601,39 @@ bool truncated_points_in_scope(int D, int M, int N, int L, int order) {
     return M >= 2 && N >= 2 && trunc_order(L, order) == 1 && truncated_in_scope(D, M, N, L, order);
 }
 
+// THE scope of the long mode (the SK_OP_TRUNCATED_LONG rule of sk_route_query): order 1 and what the staging and the unrolled level loop
+// hold; the steps of either side are bounded only by the indices (2^20: a slab plane, a row of Yt).  Every order-1 shape of
+// truncated_in_scope is inside.
+bool truncated_long_in_scope(int D, int M, int N, int L, int order) {
+    if (D < 1 || D > 16 || L < 1 || L > TR_LMAX || M < 1 || N < 1 || M > (1 << 20) || N > (1 << 20)) return false;
+    return trunc_order(L, order) == 1;
+}
+
+// THE scope of the adjoint mode (the SK_OP_TRUNCATED_ADJOINT rule of sk_route_query): order 1, and a path dim of at most 8 -- xr, yv, the
+// dX accumulators and both phases' per-level state then stay within the 256 registers two waves per SIMD leave a lane.
+bool truncated_adjoint_in_scope(int D, int M, int N, int L, int order) {
+    return truncated_in_scope(D, M, N, L, order) && trunc_order(L, order) == 1 && D <= 8 && M <= 128;
+}
+
+// THE scope of the points-adjoint mode (the SK_OP_TRUNCATED_RBF_ADJOINT rule of sk_route_query; M and N are POINTS): the points mode's with
+// a path dim of at most 8, for the reason the adjoint mode has -- xr, the dX accumulators and either phase's per-level state within 256 registers.
+bool truncated_points_adjoint_in_scope(int D, int M, int N, int L, int order) {
+    return truncated_points_in_scope(D, M, N, L, order) && D <= 8;
+}
+
+// THE scope of the wide-adjoint mode (the SK_OP_TRUNCATED_WIDE_ADJOINT rule of sk_route_query): the adjoint mode's at path dims 9 .. 16 -- the
+// rows and the dX accumulators of 16 coordinates in registers, the column of y read from LDS in halves (trunc_wide_adjoint).  Dims up to 8
+// are the adjoint mode's own and answer false here.
+bool truncated_wide_adjoint_in_scope(int D, int M, int N, int L, int order) {
+    return truncated_in_scope(D, M, N, L, order) && trunc_order(L, order) == 1 && D >= 9 && M <= 128;
+}
+
+// THE scope of the long-adjoint mode (the SK_OP_TRUNCATED_LONG_ADJOINT rule of sk_route_query): the long mode's with a path dim of at most 8,
+// for the reason the adjoint mode has.  Every shape of truncated_adjoint_in_scope is inside.
+bool truncated_long_adjoint_in_scope(int D, int M, int N, int L, int order) {
+    return truncated_long_in_scope(D, M, N, L, order) && D <= 8;
+}
+
 // paired != 0: the A = B pairs (x_p, y_p), out [A].  levels != 0: sigma is not read, out [L + 1][A][B] (paired: [L + 1][A]).
 // kind 1: M and N count POINTS, param = 1 / sigma of the RBF static kernel
 template <typename TO>
@@ -1579,25 +1642,11 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
     if (kind != 0 && kind != 1) return SK_ERR_BAD_ARG;
     if (!(kind ? truncated_points_in_scope(D, M, N, L, order) : truncated_in_scope(D, M, N, L, order))) return SK_ERR_UNSUPPORTED;
     if (fd != trunc_fd(D) || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
-    TruncParams prm;
-    prm.Xr = Xr; prm.Yt = Yt; prm.out = out;
-    prm.A = A; prm.B = B;
-    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
-    prm.order = trunc_order(L, order);
-    prm.out_f32 = sizeof(TO) == 4;
-    prm.paired = paired != 0;
-    prm.levels = levels != 0;
-    prm.param = kind ? param : 0.0;
-    prm.adjoint = kind ? 2 : 0; prm.n_chunks = 1; prm.w = nullptr; prm.Tpart = nullptr; prm.slab = nullptr;
-    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = levels ? (m == L ? 1.0 : 0.0) : (m <= L ? sigma[m] : 0.0);
+    TruncParams prm = trunc_params(kind ? TR_POINTS : TR_FORWARD, Xr, Yt, A, B, Mrows, M, N, Ncp, fd, L, trunc_order(L, order), paired,
+                                   kind ? param : 0.0, out, sizeof(TO) == 4, levels, sigma, 1, nullptr, nullptr, nullptr);
     const int RC = prm.order == 1 ? 2 : 1;
-    const int lanes = (M + RC - 1) / RC;
-    int logW = 0;
-    while ((1 << logW) < lanes) ++logW;
-    // paired: every lane group of a wave keeps a y block of its own -- fewer, wider groups until they fit (one group always does)
-    while (paired && (int64_t)(WAVE >> logW) * fd * Ncp > TR_LDS_DOUBLES) ++logW;
-    prm.logW = logW;
-    const int G = WAVE >> logW;
+    prm.logW = trunc_logw((M + RC - 1) / RC, fd, Ncp, paired);
+    const int G = WAVE >> prm.logW;
     prm.n_pos = paired ? (A + G - 1) / G : (A + G - 1) / G * B;
     int64_t blocks = (int64_t)device_cu_count() * 8;
     if (blocks > prm.n_pos) blocks = prm.n_pos;
@@ -1608,190 +1657,11 @@ int launch_truncated(const double *Xr, const double *Yt, int64_t A, int64_t B, i
     return check_launch();
 }
 
-// THE scope of the adjoint mode (the SK_OP_TRUNCATED_ADJOINT rule of sk_route_query): order 1, and a path dim of at most 8 -- xr, yv, the
-// dX accumulators and both phases' per-level state then stay within the 256 registers two waves per SIMD leave a lane.
-bool truncated_adjoint_in_scope(int D, int M, int N, int L, int order) {
-    return truncated_in_scope(D, M, N, L, order) && trunc_order(L, order) == 1 && D <= 8 && M <= 128;
-}
-
-namespace {
-struct AdjointPlan {
-    int logW;
-    int64_t n_pos, n_chunks, blocks;
-    size_t block_bytes;     // a block's slab: planes x (N + W - 1) steps x 1 KB; planes = L - 1 prefix factors, and g in the points-adjoint mode
-};
-// The split of an adjoint launch.  Gram: the B pairs of a row tile in as many chunks as fill the resident blocks (at most B; lengths
-// differ by one at most).  The block count is lowered until blocks x slab fits `workspace`; false when one block does not.  fd: the staging
-// width of a y block, which the paired widening counts (16: the wide-adjoint mode).
-bool plan_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int planes, int paired, size_t workspace, AdjointPlan *pl, int fd = 8) {
-    const int lanes = (M + 1) / 2;
-    int logW = 0;
-    while ((1 << logW) < lanes) ++logW;
-    while (paired && (int64_t)(WAVE >> logW) * fd * Ncp > TR_LDS_DOUBLES) ++logW;
-    const int G = WAVE >> logW;
-    const int64_t tiles = (A + G - 1) / G, resident = (int64_t)device_cu_count() * 8;
-    pl->logW = logW;
-    pl->n_chunks = 1;
-    if (!paired) {
-        pl->n_chunks = resident / tiles;
-        if (pl->n_chunks > B) pl->n_chunks = B;
-        if (pl->n_chunks < 1) pl->n_chunks = 1;
-    }
-    pl->n_pos = tiles * pl->n_chunks;
-    pl->blocks = pl->n_pos < resident ? pl->n_pos : resident;
-    pl->block_bytes = (size_t)planes * (size_t)(N + (1 << logW) - 1) * 1024;
-    if (pl->block_bytes) {
-        const int64_t fit = (int64_t)(workspace / pl->block_bytes);
-        if (fit < 1) return false;
-        if (pl->blocks > fit) pl->blocks = fit;
-    }
-    return true;
-}
-}  // namespace
-
-int truncated_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
-                           int64_t *blocks, size_t *slab_bytes) {
-    if (!truncated_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
-    AdjointPlan pl;
-    if (!plan_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L - 1, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
-    *n_chunks = pl.n_chunks;
-    *blocks = pl.blocks;
-    *slab_bytes = (size_t)pl.blocks * pl.block_bytes;
-    return SK_OK;
-}
-
-int launch_truncated_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd, int L,
-                             const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s, int paired) {
-    if (!truncated_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
-    if (fd != 8 || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
-    if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
-    AdjointPlan pl;
-    if (!plan_adjoint(A, B, M, N, Ncp, L - 1, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
-    TruncParams prm;
-    prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
-    prm.A = A; prm.B = B;
-    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
-    prm.order = 1; prm.out_f32 = 0;
-    prm.paired = paired != 0;
-    prm.levels = 0;
-    prm.param = 0.0;
-    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
-    prm.adjoint = 1; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
-    prm.logW = pl.logW;
-    const int G = WAVE >> pl.logW;
-    prm.n_pos = (A + G - 1) / G * n_chunks;     // the caller's chunk count (Tpart is sized by it); the plan's block count for the slab
-    int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
-    const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
-    SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
-    return check_launch();
-}
-
-// THE scope of the points-adjoint mode (the SK_OP_TRUNCATED_RBF_ADJOINT rule of sk_route_query; M and N are POINTS): the points mode's with
-// a path dim of at most 8, for the reason the adjoint mode has -- xr, the dX accumulators and either phase's per-level state within 256 registers.
-bool truncated_points_adjoint_in_scope(int D, int M, int N, int L, int order) {
-    return truncated_points_in_scope(D, M, N, L, order) && D <= 8;
-}
-
-int truncated_points_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
-                                  int64_t *blocks, size_t *slab_bytes) {
-    if (!truncated_points_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
-    AdjointPlan pl;
-    if (!plan_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
-    *n_chunks = pl.n_chunks;
-    *blocks = pl.blocks;
-    *slab_bytes = (size_t)pl.blocks * pl.block_bytes;
-    return SK_OK;
-}
-
-int launch_truncated_points_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
-                                    int L, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes,
-                                    hipStream_t s, int paired) {
-    if (!truncated_points_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
-    if (fd != 8 || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B) || !(param > 0.0)) return SK_ERR_BAD_ARG;
-    if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
-    AdjointPlan pl;
-    if (!plan_adjoint(A, B, M, N, Ncp, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
-    TruncParams prm;
-    prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
-    prm.A = A; prm.B = B;
-    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
-    prm.order = 1; prm.out_f32 = 0;
-    prm.paired = paired != 0;
-    prm.levels = 0;
-    prm.param = param;
-    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
-    prm.adjoint = 3; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
-    prm.logW = pl.logW;
-    const int G = WAVE >> pl.logW;
-    prm.n_pos = (A + G - 1) / G * n_chunks;
-    int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
-    const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
-    SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
-    return check_launch();
-}
-
-// THE scope of the wide-adjoint mode (the SK_OP_TRUNCATED_WIDE_ADJOINT rule of sk_route_query): the adjoint mode's at path dims 9 .. 16 -- the
-// rows and the dX accumulators of 16 coordinates in registers, the column of y read from LDS in halves (trunc_wide_adjoint).  Dims up to 8
-// are the adjoint mode's own and answer false here.
-bool truncated_wide_adjoint_in_scope(int D, int M, int N, int L, int order) {
-    return truncated_in_scope(D, M, N, L, order) && trunc_order(L, order) == 1 && D >= 9 && M <= 128;
-}
-
-int truncated_wide_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
-                                int64_t *blocks, size_t *slab_bytes) {
-    if (!truncated_wide_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
-    AdjointPlan pl;
-    if (!plan_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L - 1, paired, workspace, &pl, 16)) return SK_ERR_UNSUPPORTED;
-    *n_chunks = pl.n_chunks;
-    *blocks = pl.blocks;
-    *slab_bytes = (size_t)pl.blocks * pl.block_bytes;
-    return SK_OK;
-}
-
-int launch_truncated_wide_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
-                                  int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
-                                  int paired) {
-    if (!truncated_wide_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
-    if (fd != 16 || Ncp < N || (int64_t)fd * Ncp > TR_LDS_DOUBLES || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
-    if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
-    AdjointPlan pl;
-    if (!plan_adjoint(A, B, M, N, Ncp, L - 1, paired, slab ? slab_bytes : 0, &pl, fd)) return SK_ERR_UNSUPPORTED;
-    TruncParams prm;
-    prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
-    prm.A = A; prm.B = B;
-    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
-    prm.order = 1; prm.out_f32 = 0;
-    prm.paired = paired != 0;
-    prm.levels = 0;
-    prm.param = 0.0;
-    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
-    prm.adjoint = 6; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
-    prm.logW = pl.logW;
-    const int G = WAVE >> pl.logW;
-    prm.n_pos = (A + G - 1) / G * n_chunks;     // the caller's chunk count (Tpart is sized by it); the plan's block count for the slab
-    int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
-    const size_t lds = sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
-    SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
-    return check_launch();
-}
-
-// THE scope of the long mode (the SK_OP_TRUNCATED_LONG rule of sk_route_query): order 1 and what the staging and the unrolled level loop
-// hold; the steps of either side are bounded only by the indices (2^20: a slab plane, a row of Yt).  Every order-1 shape of
-// truncated_in_scope is inside.
-bool truncated_long_in_scope(int D, int M, int N, int L, int order) {
-    if (D < 1 || D > 16 || L < 1 || L > TR_LMAX || M < 1 || N < 1 || M > (1 << 20) || N > (1 << 20)) return false;
-    return trunc_order(L, order) == 1;
-}
-
 // lanes of a pair's group in the long mode: 64 beyond 128 rows; paired: every group keeps its own tile of y, so fewer, wider groups until
 // G tiles of Tc = min(Ncp, 2048 / fd) columns fit the wave's 16 KB
 int truncated_long_logw(int M, int Ncp, int fd, int paired) {
-    const int lanes = M > 128 ? 64 : (M + 1) / 2;
-    int logW = 0;
-    while ((1 << logW) < lanes) ++logW;
     const int Tc = Ncp < TR_LDS_DOUBLES / fd ? Ncp : TR_LDS_DOUBLES / fd;
-    while (paired && (int64_t)(WAVE >> logW) * fd * Tc > TR_LDS_DOUBLES) ++logW;
-    return logW;
+    return trunc_logw(M > 128 ? 64 : (M + 1) / 2, fd, Tc, paired);
 }
 
 namespace {
@@ -1833,17 +1703,8 @@ int launch_truncated_long(const double *Xr, const double *Yt, int64_t A, int64_t
     if (fd != trunc_fd(D) || Ncp < N || Ncp % 16 || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
     LongPlan pl;
     if (!plan_long(A, B, M, N, Ncp, fd, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
-    TruncParams prm;
-    prm.Xr = Xr; prm.Yt = Yt; prm.out = out;
-    prm.A = A; prm.B = B;
-    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
-    prm.order = 1;
-    prm.out_f32 = sizeof(TO) == 4;
-    prm.paired = paired != 0;
-    prm.levels = levels != 0;
-    prm.param = 0.0;
-    prm.adjoint = 4; prm.n_chunks = 1; prm.w = nullptr; prm.Tpart = nullptr; prm.slab = slab;
-    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = levels ? (m == L ? 1.0 : 0.0) : (m <= L ? sigma[m] : 0.0);
+    TruncParams prm = trunc_params(TR_LONG, Xr, Yt, A, B, Mrows, M, N, Ncp, fd, L, 1, paired, 0.0, out, sizeof(TO) == 4, levels, sigma, 1,
+                                   nullptr, nullptr, slab);
     prm.logW = pl.logW;
     prm.n_pos = pl.n_pos;
     const int G = WAVE >> pl.logW;
@@ -1853,23 +1714,41 @@ int launch_truncated_long(const double *Xr, const double *Yt, int64_t A, int64_t
     return check_launch();
 }
 
-// THE scope of the long-adjoint mode (the SK_OP_TRUNCATED_LONG_ADJOINT rule of sk_route_query): the long mode's with a path dim of at most 8,
-// for the reason the adjoint mode has.  Every shape of truncated_adjoint_in_scope is inside.
-bool truncated_long_adjoint_in_scope(int D, int M, int N, int L, int order) {
-    return truncated_long_in_scope(D, M, N, L, order) && D <= 8;
+namespace {
+// THE adjoint modes, one row each: everything the host does differently for them.  The device functions stay four (register pressure, DESIGN
+// section 4); the plan and the launcher below are one.
+struct AdjointMode {
+    int mode;                                   // TruncParams::mode
+    bool (*in_scope)(int, int, int, int, int);  // the mode's scope = its rule of sk_route_query
+    int fd;                                     // the staging width it accepts: 8, or 16 (rows and dX of 16 coordinates, Tpart [..][16])
+    int g_plane;                                // slab planes beside the L - 1 prefix factors: 1 in the points-adjoint mode, the node's g
+    bool is_long;                               // any number of steps: the long mode's lane groups and y tiles, a slab of one band's factors and the carries
+    bool needs_param;                           // param = 1 / sigma of the RBF kernel, positive; the others do not read it
+};
+const AdjointMode ADJOINT_MODES[] = {
+    {TR_ADJOINT, truncated_adjoint_in_scope, 8, 0, false, false},
+    {TR_POINTS_ADJOINT, truncated_points_adjoint_in_scope, 8, 1, false, true},
+    {TR_LONG_ADJOINT, truncated_long_adjoint_in_scope, 8, 0, true, false},
+    {TR_WIDE_ADJOINT, truncated_wide_adjoint_in_scope, 16, 0, false, false},
+};
+const AdjointMode *adjoint_mode(int mode) {
+    for (const AdjointMode &am : ADJOINT_MODES)
+        if (am.mode == mode) return &am;
+    return nullptr;
 }
 
-namespace {
-struct LongAdjointPlan {
+struct AdjointPlan {
     int logW;
     int64_t n_pos, n_chunks, blocks;
-    size_t block_bytes;     // a block's slab: the factors of one band, (L - 1) x (N + tiles (W - 1)) KB, and with more than one band the
-                            // forward carries and the two reverse-carry halves, (bands + 2) x (L - 1) x ceil64(N) doubles
+    size_t block_bytes;     // ONE block's slab.  (L - 1 + g_plane) planes x (N + W - 1) steps x 1 KB; long: the factors of one band,
+                            // (L - 1) x (N + tiles (W - 1)) KB, and with more than one band the forward carries and the two reverse-carry
+                            // halves, (bands + 2) x (L - 1) x ceil64(N) doubles
 };
-// The split of a long-adjoint launch: plan_adjoint's chunks on the long mode's lane groups.  The block count is lowered until blocks x slab
-// fits `workspace`; false when one block does not.
-bool plan_long_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int L, int paired, size_t workspace, LongAdjointPlan *pl) {
-    pl->logW = truncated_long_logw(M, Ncp, 8, paired);
+// The split of an adjoint launch.  Gram: the B pairs of a row tile in as many chunks as fill the resident blocks (at most B; lengths
+// differ by one at most).  The block count is lowered until blocks x slab fits `workspace`; false when one block does not.  The lane
+// groups are the forward's at the mode's staging width (which the paired widening counts), the long mode's where the mode is long.
+bool plan_adjoint(const AdjointMode &am, int64_t A, int64_t B, int M, int N, int Ncp, int L, int paired, size_t workspace, AdjointPlan *pl) {
+    pl->logW = am.is_long ? truncated_long_logw(M, Ncp, am.fd, paired) : trunc_logw((M + 1) / 2, am.fd, Ncp, paired);
     const int W = 1 << pl->logW, G = WAVE >> pl->logW;
     const int64_t rtiles = (A + G - 1) / G, resident = (int64_t)device_cu_count() * 8;
     pl->n_chunks = 1;
@@ -1880,9 +1759,13 @@ bool plan_long_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int L, int p
     }
     pl->n_pos = rtiles * pl->n_chunks;
     pl->blocks = pl->n_pos < resident ? pl->n_pos : resident;
-    const int Tc = Ncp < TR_LDS_DOUBLES / 8 ? Ncp : TR_LDS_DOUBLES / 8;
-    const int64_t ctiles = (N + Tc - 1) / Tc, bands = (M + 2 * W - 1) / (2 * W), Ns = (N + 63) / 64 * 64;
-    pl->block_bytes = (size_t)(L - 1) * ((size_t)(N + ctiles * (W - 1)) * 1024 + (bands > 1 ? (size_t)(bands + 2) * Ns * sizeof(double) : 0));
+    if (am.is_long) {
+        const int Tc = Ncp < TR_LDS_DOUBLES / 8 ? Ncp : TR_LDS_DOUBLES / 8;
+        const int64_t ctiles = (N + Tc - 1) / Tc, bands = (M + 2 * W - 1) / (2 * W), Ns = (N + 63) / 64 * 64;
+        pl->block_bytes = (size_t)(L - 1) * ((size_t)(N + ctiles * (W - 1)) * 1024 + (bands > 1 ? (size_t)(bands + 2) * Ns * sizeof(double) : 0));
+    } else {
+        pl->block_bytes = (size_t)(L - 1 + am.g_plane) * (size_t)(N + W - 1) * 1024;
+    }
     if (pl->block_bytes) {
         const int64_t fit = (int64_t)(workspace / pl->block_bytes);
         if (fit < 1) return false;
@@ -1892,42 +1775,44 @@ bool plan_long_adjoint(int64_t A, int64_t B, int M, int N, int Ncp, int L, int p
 }
 }  // namespace
 
-int truncated_long_adjoint_plan(int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
-                                int64_t *blocks, size_t *block_bytes) {
-    if (!truncated_long_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
-    LongAdjointPlan pl;
-    if (!plan_long_adjoint(A, paired ? A : B, M, N, (N + 15) / 16 * 16, L, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
+int truncated_adjoint_plan(int mode, int64_t A, int64_t B, int M, int N, int D, int L, int paired, size_t workspace, int64_t *n_chunks,
+                           int64_t *blocks, size_t *block_bytes) {
+    const AdjointMode *am = adjoint_mode(mode);
+    if (!am) return SK_ERR_BAD_ARG;
+    if (!am->in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    AdjointPlan pl;
+    if (!plan_adjoint(*am, A, paired ? A : B, M, N, (N + 15) / 16 * 16, L, paired, workspace, &pl)) return SK_ERR_UNSUPPORTED;
     *n_chunks = pl.n_chunks;
     *blocks = pl.blocks;
     *block_bytes = pl.block_bytes;
     return SK_OK;
 }
 
-int launch_truncated_long_adjoint(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
-                                  int L, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes, hipStream_t s,
-                                  int paired) {
-    if (!truncated_long_adjoint_in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
-    if (fd != 8 || Ncp < N || Ncp % 16 || Mrows < M || (paired && A != B)) return SK_ERR_BAD_ARG;
+int launch_truncated_adjoint(int mode, const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int M, int N, int Ncp, int D, int fd,
+                             int L, double param, const double *w, double *Tpart, int64_t n_chunks, double *slab, size_t slab_bytes,
+                             hipStream_t s, int paired) {
+    const AdjointMode *am = adjoint_mode(mode);
+    if (!am) return SK_ERR_BAD_ARG;
+    if (!am->in_scope(D, M, N, L, 1)) return SK_ERR_UNSUPPORTED;
+    // the y block of a wave holds Ncp columns; the long mode tiles them, so any multiple of 16 goes
+    if (fd != am->fd || Ncp < N || (am->is_long ? Ncp % 16 != 0 : (int64_t)fd * Ncp > TR_LDS_DOUBLES) || Mrows < M || (paired && A != B) ||
+        (am->needs_param && !(param > 0.0)))
+        return SK_ERR_BAD_ARG;
     if (n_chunks < 1 || n_chunks > (paired ? 1 : B)) return SK_ERR_BAD_ARG;
-    LongAdjointPlan pl;
-    if (!plan_long_adjoint(A, B, M, N, Ncp, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
-    TruncParams prm;
-    prm.Xr = Xr; prm.Yt = Yt; prm.out = nullptr;
-    prm.A = A; prm.B = B;
-    prm.Mrows = Mrows; prm.Ncp = Ncp; prm.fd = fd; prm.M = M; prm.N = N; prm.L = L;
-    prm.order = 1; prm.out_f32 = 0;
-    prm.paired = paired != 0;
-    prm.levels = 0;
-    prm.param = 0.0;
-    for (int m = 0; m <= TR_LMAX; ++m) prm.sigma[m] = 0.0;
-    prm.adjoint = 5; prm.n_chunks = n_chunks; prm.w = w; prm.Tpart = Tpart; prm.slab = slab;
+    AdjointPlan pl;
+    if (!plan_adjoint(*am, A, B, M, N, Ncp, L, paired, slab ? slab_bytes : 0, &pl)) return SK_ERR_UNSUPPORTED;
+    TruncParams prm = trunc_params(mode, Xr, Yt, A, B, Mrows, M, N, Ncp, fd, L, 1, paired, am->needs_param ? param : 0.0, nullptr, false, 0,
+                                   nullptr, n_chunks, w, Tpart, slab);
     prm.logW = pl.logW;
     const int G = WAVE >> pl.logW;
     prm.n_pos = (A + G - 1) / G * n_chunks;     // the caller's chunk count (Tpart is sized by it); the plan's block count for the slab
-    int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
-    // the y tiles at their constant stride; the reverse carry of 64 steps, eight doubles a step
-    const size_t lds = sizeof(double) * ((size_t)TR_LDS_DOUBLES + (size_t)WAVE * TR_LMAX);
-    SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
+    const int64_t blocks = pl.blocks < prm.n_pos ? pl.blocks : prm.n_pos;
+    // long: the y tiles at their constant stride; the reverse carry of 64 steps, eight doubles a step
+    const size_t lds = am->is_long ? sizeof(double) * ((size_t)TR_LDS_DOUBLES + (size_t)WAVE * TR_LMAX)
+                                   : sizeof(double) * (size_t)fd * Ncp * (paired ? G : 1);
+    // the adjoint mode is the <1, 2> instance's own; every other mode is hosted by <TR_OMAX, 1> (see trunc_points)
+    if (mode == TR_ADJOINT) SK_LAUNCH((k_trunc_sig<1, 2>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
+    else SK_LAUNCH((k_trunc_sig<TR_OMAX, 1>), dim3((unsigned)blocks), dim3(WAVE), lds, s, prm);
     return check_launch();
 }
 

@@ -40,18 +40,24 @@ truncation below L, every choice of weights and every rescaling of the paths is 
 
 Each thing is stated once.  ``_level_sums`` is the recursion on a given G and ``_restatement`` its tiling, behind all three torch routes
 (``_step_gram``: G of steps; ``_lifted_gram``: G of points under a static kernel, TruncatedSigKernel's); the three public
-functions share ``_prepare`` (stage, check), ``_routed`` (try (X, Y), then (Y, X)) and ``_chunked`` (paired launches within the workspace);
-the ctypes call and the staging rule are the backend's (``_lib.HipBackend._truncated``, ``_lib._truncated_staging``).
+functions share ``_prepare`` (stage, check) and ``_launched``: ``_routed`` (try (X, Y), then (Y, X)) on ``_chunked`` (paired launches within
+the workspace, in ``_pair_slices`` runs); the ctypes call and the staging rule are the backend's (``_lib.HipBackend._truncated``,
+``_lib._truncated_staging``).
 
 ``TruncatedSigKernel`` is the SigKernel-shaped front (paths in, ``compute_Gram`` / ``compute_kernel`` / ``compute_mmd``) and the one place where
-a gradient stays on the HIP route: ``_TruncatedLevels`` is an autograd function on the level terms whose forward is the levels mode and
-whose backward is the kernel's adjoint mode (``HipBackend.truncated_adjoint``: order 1, dim <= 8).  The three functions above keep their
+a gradient stays on the HIP route: ``_RouteLevels`` is THE autograd function on the level terms, along one of four ``_AdjointRoute`` records,
+and ``TruncatedSigKernel._route_serves`` THE predicate that says whether a route serves a call.  ``_PLAIN``: forward the levels mode,
+backward the kernel's adjoint mode (``HipBackend.truncated_adjoint``: order 1, dim <= 8).  The three functions above keep their
 rule -- a gradient pending means the torch restatement.  Its ``static_kernel`` is the one place where G is something other than inner
-products of steps: an RBFKernel is the kernel's points mode -- forward only, unless ``points_adjoint=True`` asks for ``_LiftedLevels``, whose
+products of steps: an RBFKernel is the kernel's points mode -- forward only, unless ``points_adjoint=True`` asks for ``_POINTS``, whose
 backward is the kernel's points-adjoint mode (``HipBackend.truncated_points_adjoint``) -- anything else the restatement on ``_lifted_gram``.
-Beyond the adjoint mode's 128 steps a gradient takes the restatement too, unless ``long_adjoint=True`` asks for ``_LongLevels``: the long
-mode's levels launch forward, the kernel's long-adjoint mode backward (``HipBackend.truncated_long_adjoint``: order 1, dim <= 8, any steps).
+Beyond the adjoint mode's 128 steps a gradient takes the restatement too, unless ``long_adjoint=True`` asks for ``_LONG``: the long
+mode's levels launch forward, the kernel's long-adjoint mode backward (``HipBackend.truncated_long_adjoint``: order 1, dim <= 8, any steps);
+at path dims 9 .. 16, unless ``wide_adjoint=True`` asks for ``_WIDE``: the levels mode forward, the wide-adjoint mode backward
+(``HipBackend.truncated_wide_adjoint``).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -199,18 +205,22 @@ def truncated_route(D, M, N, num_levels, order, elem_size):
     return int(_lib.load().sk_route_query(_lib.OP_TRUNCATED, int(order), int(D), int(M), int(N), int(num_levels), 0, int(elem_size), 0))
 
 
-def _chunked(call, workspace_bytes, axis):
-    """`call(X, Y)` of a paired backend method, on as many pairs at a time as `workspace_bytes` of fp64 staging hold (all of them, usually)
-    and the parts joined along `axis`; None where `call` says None"""
+def _pair_slices(P, M, N, D, workspace_bytes):
+    """THE pairs-per-run rule: the pairs of a paired batch in runs whose fp64 staging (8 or 16 doubles per step) stays within
+    `workspace_bytes` -- all of them in one run, usually"""
     budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
+    fd, Ncp = _lib._truncated_staging(D, N)
+    pairs = int(max(1, min(P, budget // (8 * fd * (M + Ncp)))))
+    return [slice(p, p + pairs) for p in range(0, P, pairs)]
 
+
+def _chunked(call, workspace_bytes, axis):
+    """`call(X, Y)` of a paired backend method, on _pair_slices' runs of the pairs and the parts joined along `axis`; None where `call`
+    says None"""
     def run(X, Y):
-        P, M, D = X.shape
-        fd, Ncp = _lib._truncated_staging(D, Y.shape[1])
-        pairs = int(max(1, min(P, budget // (8 * fd * (M + Ncp)))))
         parts = []
-        for p in range(0, P, pairs):
-            k = call(X[p:p + pairs], Y[p:p + pairs])
+        for sl in _pair_slices(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], workspace_bytes):
+            k = call(X[sl], Y[sl])
             if k is None:
                 return None
             parts.append(k)
@@ -228,6 +238,12 @@ def _routed(call, X, Y, gram):
         if K is not None and gram:
             K = K.transpose(-2, -1).contiguous()
     return K
+
+
+def _launched(call, X, Y, paired, workspace_bytes, axis=1):
+    """THE launch of a backend method `call(x, y)` on the detached batches: a paired batch in _chunked's runs joined along `axis` (1: level
+    terms, 0: values), either orientation (_routed, a Gram result transposed back).  None where the method declines both."""
+    return _routed(_chunked(call, workspace_bytes, axis) if paired else call, X.detach(), Y.detach(), not paired)
 
 
 def _stage(X, Y):
@@ -270,7 +286,7 @@ def _long(be, X, Y, num_levels, weights, paired, workspace_bytes):
     """HipBackend.truncated_long on (X, Y), or on (Y, X) where the route query says that sweep is the shorter one; paired batches in
     _chunked's runs; `weights` None: the level terms.  None where it declines (one block's slab beyond the workspace)."""
     call = lambda x, y: be.truncated_long(x, y, num_levels, weights, paired, workspace_bytes)
-    return _routed(_chunked(call, workspace_bytes, 0 if weights is not None else 1) if paired else call, X.detach(), Y.detach(), not paired)
+    return _launched(call, X, Y, paired, workspace_bytes, 0 if weights is not None else 1)
 
 
 def truncated_sig_kernel_paired(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=None):
@@ -288,8 +304,7 @@ def truncated_sig_kernel_paired(X, Y, num_levels, sigma=1., order=-1, workspace_
     k = None
     if _hip_serves(be, "truncated_paired", X, Y, sigma):
         weights = sig.detach().double().cpu().tolist()
-        call = lambda x, y: be.truncated_paired(x, y, num_levels, weights, order)
-        k = _routed(_chunked(call, workspace_bytes, 0), X.detach(), Y.detach(), False)
+        k = _launched(lambda x, y: be.truncated_paired(x, y, num_levels, weights, order), X, Y, True, workspace_bytes, 0)
     if k is None and _long_serves(be, X, Y, sigma, order):
         k = _long(be, X, Y, num_levels, sig.detach().double().cpu().tolist(), True, workspace_bytes)
     if k is None:
@@ -324,7 +339,7 @@ def truncated_sig_kernel(X, Y, num_levels, sigma=1., order=-1, workspace_bytes=N
     K = None
     if _hip_serves(be, "truncated_gram", X, Y, sigma):
         weights = sig.detach().double().cpu().tolist()
-        K = _routed(lambda x, y: be.truncated_gram(x, y, num_levels, weights, order), X.detach(), Y.detach(), True)
+        K = _launched(lambda x, y: be.truncated_gram(x, y, num_levels, weights, order), X, Y, False, workspace_bytes)
     if K is None and _long_serves(be, X, Y, sigma, order):
         K = _long(be, X, Y, num_levels, sig.detach().double().cpu().tolist(), False, workspace_bytes)
     if K is None:
@@ -349,8 +364,7 @@ def truncated_sig_kernel_levels(X, Y, num_levels, order=-1, paired=False, worksp
     X, Y, num_levels, order, as_numpy, be = _prepare(X, Y, num_levels, order, paired)
     K = None
     if _hip_serves(be, "truncated_levels", X, Y, None):
-        call = lambda x, y: be.truncated_levels(x, y, num_levels, order, paired=paired)
-        K = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
+        K = _launched(lambda x, y: be.truncated_levels(x, y, num_levels, order, paired=paired), X, Y, paired, workspace_bytes)
     if K is None and _long_serves(be, X, Y, None, order):
         K = _long(be, X, Y, num_levels, None, paired, workspace_bytes)
     if K is None:
@@ -441,26 +455,37 @@ def _on_hip(t):
     return t.is_cuda
 
 
-def _pair_slices(P, M, N, D, workspace_bytes):
-    """the pairs of a paired batch in runs whose fp64 staging stays within `workspace_bytes` (_chunked's rule)"""
-    budget = _DEFAULT_WORKSPACE if workspace_bytes is None else int(workspace_bytes)
-    fd, Ncp = _lib._truncated_staging(D, N)
-    pairs = int(max(1, min(P, budget // (8 * fd * (M + Ncp)))))
-    return [slice(p, p + pairs) for p in range(0, P, pairs)]
+class _AdjointRoute(collections.namedtuple("_AdjointRoute", "switch op needs fits adjoint forward")):
+    """One way TruncatedSigKernel keeps a gradient on the HIP kernel: `switch` the keyword (attribute) that turns it on, None for the
+    route every object has; `op` the route op of its FORWARD; `needs` the backend attributes that must exist; `fits` / `adjoint` the
+    backend's scope-and-workspace predicate and adjoint method; `forward` how the level terms are launched -- "levels": truncated_levels on
+    steps, "points": truncated_levels at kind 1 with the RBF parameter, "long": truncated_long."""
+    __slots__ = ()
 
 
-def _adjoint(be, X, Y, w, L, paired, workspace_bytes, param=None):
-    """d / dX of sum_pairs sum_m w[m - 1, pair] k_m(pair) by the kernel's adjoint mode, in X's dtype; paired batches in _chunked's runs.
-    `param`: X and Y hold POINTS and the k_m are those of the lift through RBFKernel(param) -- the points-adjoint mode; the string
-    "long": steps of any number -- the long-adjoint mode; the string "wide": path dims 9 .. 16 -- the wide-adjoint mode"""
-    if param is None:
-        call = lambda x, y, v, p: be.truncated_adjoint(x, y, v, L, p, workspace_bytes)
-    elif param == "long":
-        call = lambda x, y, v, p: be.truncated_long_adjoint(x, y, v, L, p, workspace_bytes)
-    elif param == "wide":
-        call = lambda x, y, v, p: be.truncated_wide_adjoint(x, y, v, L, p, workspace_bytes)
-    else:
-        call = lambda x, y, v, p: be.truncated_points_adjoint(x, y, v, L, param, p, workspace_bytes)
+_PLAIN = _AdjointRoute(None, _lib.OP_TRUNCATED, ("truncated_levels", "truncated_adjoint_fits"),
+                       "truncated_adjoint_fits", "truncated_adjoint", "levels")                     # order 1, dim <= 8, at most 128 steps
+_WIDE = _AdjointRoute("wide_adjoint", _lib.OP_TRUNCATED, ("truncated_levels", "truncated_wide_adjoint", "truncated_wide_adjoint_fits"),
+                      "truncated_wide_adjoint_fits", "truncated_wide_adjoint", "levels")             # path dims 9 .. 16
+_LONG = _AdjointRoute("long_adjoint", _lib.OP_TRUNCATED_LONG, ("truncated_long", "truncated_long_adjoint", "truncated_long_adjoint_fits"),
+                      "truncated_long_adjoint_fits", "truncated_long_adjoint", "long")               # any number of steps
+_POINTS = _AdjointRoute("points_adjoint", _lib.OP_TRUNCATED_RBF, ("truncated_levels", "truncated_points_adjoint_fits"),
+                        "truncated_points_adjoint_fits", "truncated_points_adjoint", "points")       # POINT tensors under RBFKernel(param)
+
+
+def _route_levels(be, route, X, Y, L, order, param, paired, workspace_bytes):
+    """the level terms by the route's forward launch, (L + 1, A, B) / paired (L + 1, P); None where the backend declines both orientations"""
+    if route.forward == "long":
+        return _long(be, X, Y, L, None, paired, workspace_bytes)
+    kw = dict(kind=1, param=param) if route.forward == "points" else {}
+    return _launched(lambda x, y: be.truncated_levels(x, y, L, order, paired=paired, **kw), X, Y, paired, workspace_bytes)
+
+
+def _adjoint(be, route, X, Y, w, L, param, paired, workspace_bytes):
+    """d / dX of sum_pairs sum_m w[m - 1, pair] k_m(pair) by the route's adjoint mode of the kernel, in X's dtype; paired batches in
+    _pair_slices' runs.  The points route: X and Y hold POINTS and the k_m are those of the lift through RBFKernel(param)."""
+    args = (param,) if route.forward == "points" else ()
+    call = lambda x, y, v, p: getattr(be, route.adjoint)(x, y, v, L, *args, p, workspace_bytes)
     if not paired:
         parts = [call(X, Y, w, False)]
     else:
@@ -470,110 +495,40 @@ def _adjoint(be, X, Y, w, L, paired, workspace_bytes, param=None):
     return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)).to(X.dtype)
 
 
-def _levels_backward(ctx, grad, param=None):
-    """the backward of both autograd functions below: one adjoint launch per batch that needs a gradient, w = grad_levels[1:]"""
-    X, Y = ctx.saved_tensors
-    L, paired, sym, workspace_bytes = ctx.mode
-    be = _lib.get_backend()
-    w = grad[1:].double()
-    dX = dY = None
-    if sym:
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            dX = _adjoint(be, X, X, w + w.transpose(1, 2), L, False, workspace_bytes, param)
-    else:
-        if ctx.needs_input_grad[0]:
-            dX = _adjoint(be, X, Y, w.contiguous(), L, paired, workspace_bytes, param)
-        if ctx.needs_input_grad[1]:
-            dY = _adjoint(be, Y, X, (w if paired else w.transpose(1, 2)).contiguous(), L, paired, workspace_bytes, param)
-    return dX, dY, None, None, None, None, None
-
-
-class _TruncatedLevels(torch.autograd.Function):
-    """The level terms of STEP tensors on a HIP device -- (L + 1, A, B), paired (L + 1, P) -- with the HIP kernel on both sides (a gradient: order 1):
-    forward = the levels mode (one launch), backward = the adjoint mode with w = grad_levels[1:], one launch per batch that needs a
-    gradient: dY is the adjoint on (Y, X) with w transposed, and a symmetric call (Y is X) is ONE launch with w + w^T, since
-    k_m(x, y) = k_m(y, x).  The caller has asked the route table for every side it needs (TruncatedSigKernel._hip_serves)."""
+class _RouteLevels(torch.autograd.Function):
+    """The level terms of tensors on a HIP device -- (L + 1, A, B), paired (L + 1, P) -- with the HIP kernel on both sides (a gradient:
+    order 1), along an _AdjointRoute: forward = the route's levels launch (on (Y, X), transposed, where only that orientation serves),
+    backward = its adjoint mode with w = grad_levels[1:], one launch per batch that needs a gradient: dY is the adjoint on (Y, X) with w
+    transposed, and a symmetric call (Y is X) is ONE launch with w + w^T, since k_m(x, y) = k_m(y, x).  The caller has asked the route
+    table for every side it needs (TruncatedSigKernel._route_serves)."""
 
     @staticmethod
-    def forward(ctx, X, Y, L, order, paired, sym, workspace_bytes):
+    def forward(ctx, X, Y, route, L, order, param, paired, sym, workspace_bytes):
+        lev = _route_levels(_lib.get_backend(), route, X, Y, L, order, param, paired, workspace_bytes)
+        if lev is None:
+            raise RuntimeError("the %s launch of k_trunc_sig declined a shape its route query accepted" % route.forward)
+        ctx.save_for_backward(X, Y)
+        ctx.mode = (route, L, param, paired, sym, workspace_bytes)
+        return lev
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        X, Y = ctx.saved_tensors
+        route, L, param, paired, sym, workspace_bytes = ctx.mode
         be = _lib.get_backend()
-        call = lambda x, y: be.truncated_levels(x, y, L, order, paired=paired)
-        lev = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
-        if lev is None:
-            raise RuntimeError("the levels mode of k_trunc_sig declined a shape its route query accepted")
-        ctx.save_for_backward(X, Y)
-        ctx.mode = (L, paired, sym, workspace_bytes)
-        return lev
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        return _levels_backward(ctx, grad)
-
-
-class _LiftedLevels(torch.autograd.Function):
-    """_TruncatedLevels for POINT tensors under RBFKernel(param), order 1: forward = the points mode's levels launch (on (Y, X), transposed,
-    when only the second batch fits the lanes), backward = the points-adjoint mode, one launch per batch that needs a gradient and ONE with
-    w + w^T for a symmetric call.  The caller has asked the route table for every side (TruncatedSigKernel._points_adjoint_serves)."""
-
-    @staticmethod
-    def forward(ctx, X, Y, L, param, paired, sym, workspace_bytes):
-        be = _lib.get_backend()
-        call = lambda x, y: be.truncated_levels(x, y, L, 1, paired=paired, kind=1, param=param)
-        lev = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
-        if lev is None:
-            raise RuntimeError("the points mode of k_trunc_sig declined a shape its route query accepted")
-        ctx.save_for_backward(X, Y)
-        ctx.mode = (L, paired, sym, workspace_bytes)
-        ctx.param = param
-        return lev
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        return _levels_backward(ctx, grad, ctx.param)
-
-
-class _LongLevels(torch.autograd.Function):
-    """_TruncatedLevels for STEP tensors beyond the plain launch, order 1: forward = the long mode's levels launch (_long: on (Y, X),
-    transposed, where that sweep is the shorter one), backward = the long-adjoint mode, one launch per batch that needs a gradient and ONE
-    with w + w^T for a symmetric call.  The caller has asked the route table for every side (TruncatedSigKernel._long_adjoint_serves)."""
-
-    @staticmethod
-    def forward(ctx, X, Y, L, order, paired, sym, workspace_bytes):
-        lev = _long(_lib.get_backend(), X, Y, L, None, paired, workspace_bytes)
-        if lev is None:
-            raise RuntimeError("the long mode of k_trunc_sig declined a shape its route query accepted")
-        ctx.save_for_backward(X, Y)
-        ctx.mode = (L, paired, sym, workspace_bytes)
-        return lev
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        return _levels_backward(ctx, grad, "long")
-
-
-class _WideLevels(torch.autograd.Function):
-    """_TruncatedLevels for STEP tensors of path dim 9 .. 16, order 1: forward = the levels mode (one launch, on (Y, X), transposed, when
-    only the second batch fits the lanes), backward = the wide-adjoint mode, one launch per batch that needs a gradient and ONE with
-    w + w^T for a symmetric call.  The caller has asked the route table for every side (TruncatedSigKernel._wide_adjoint_serves)."""
-
-    @staticmethod
-    def forward(ctx, X, Y, L, order, paired, sym, workspace_bytes):
-        be = _lib.get_backend()
-        call = lambda x, y: be.truncated_levels(x, y, L, 1, paired=paired)
-        lev = _routed(_chunked(call, workspace_bytes, 1) if paired else call, X.detach(), Y.detach(), not paired)
-        if lev is None:
-            raise RuntimeError("the levels mode of k_trunc_sig declined a shape its route query accepted")
-        ctx.save_for_backward(X, Y)
-        ctx.mode = (L, paired, sym, workspace_bytes)
-        return lev
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        return _levels_backward(ctx, grad, "wide")
+        adjoint = lambda x, y, w, p: _adjoint(be, route, x, y, w, L, param, p, workspace_bytes)
+        w = grad[1:].double()
+        dX = dY = None
+        if sym:
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+                dX = adjoint(X, X, w + w.transpose(1, 2), False)
+        else:
+            if ctx.needs_input_grad[0]:
+                dX = adjoint(X, Y, w.contiguous(), paired)
+            if ctx.needs_input_grad[1]:
+                dY = adjoint(Y, X, (w if paired else w.transpose(1, 2)).contiguous(), paired)
+        return (dX, dY) + (None,) * 7
 
 
 class TruncatedSigKernel:
@@ -642,100 +597,45 @@ class TruncatedSigKernel:
         self.long_adjoint = bool(long_adjoint)
         self.wide_adjoint = bool(wide_adjoint)
 
-    def _hip_serves(self, dx, dy, L, order, paired, sym):
-        """the HIP function serves the call: a HIP device, no empty axis, the forward in scope on (dx, dy) or (dy, dx), and on every side
-        that needs a gradient order 1 and the adjoint in scope, its slab within the workspace"""
+    def _route_serves(self, route, dx, dy, L, order, paired, sym):
+        """the HIP kernel serves the call along `route` (step tensors; the points route: POINT tensors): a HIP device, no empty axis, a
+        backend that has what the route needs, the route's forward in scope on (dx, dy) or (dy, dx), and on every side that needs a
+        gradient order 1 and the route's adjoint in scope, a block's slab within the workspace.  The plain route also serves calls with no
+        gradient pending, at any order; an opt-in route applies only with its keyword, at order 1, with a gradient pending."""
+        pending = torch.is_grad_enabled() and (dx.requires_grad or dy.requires_grad)
+        if route.switch is not None and not (getattr(self, route.switch) and order == 1 and pending):
+            return False
         if not _on_hip(dx) or min(dx.shape[0], dx.shape[1], dy.shape[0], dy.shape[1]) == 0:
             return False
         be = _lib.get_backend()
-        if not (hasattr(be, "truncated_levels") and hasattr(be, "truncated_adjoint_fits")):
+        if not all(hasattr(be, name) for name in route.needs):
             return False
         (A, M, D), (B, N), es = dx.shape, dy.shape[:2], dx.element_size()
-        if be.route(_lib.OP_TRUNCATED, order, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
+        if be.route(route.op, order, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
             return False
-        grad = torch.is_grad_enabled()
-        if grad and order != 1 and (dx.requires_grad or dy.requires_grad):
+        if pending and order != 1:
             return False
-        if grad and dx.requires_grad and not be.truncated_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
+        fits = getattr(be, route.fits)
+        if pending and dx.requires_grad and not fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
             return False
-        if grad and dy.requires_grad and not sym and not be.truncated_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
+        if pending and dy.requires_grad and not sym and not fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
             return False
         return True
 
-    def _long_adjoint_serves(self, dx, dy, L, order, paired, sym):
-        """long_adjoint=True applies (asked where _hip_serves declined): step tensors on a HIP device with a gradient pending, order 1, no
-        empty axis, the forward in the long mode's scope on (dx, dy) or (dy, dx), and every side that needs a gradient in the long-adjoint
-        mode's, a block's slab within the workspace"""
-        if not (self.long_adjoint and _on_hip(dx) and order == 1 and min(dx.shape[0], dx.shape[1], dy.shape[0], dy.shape[1]) > 0):
-            return False
-        if not (torch.is_grad_enabled() and (dx.requires_grad or dy.requires_grad)):
-            return False
-        be = _lib.get_backend()
-        if not (hasattr(be, "truncated_long") and hasattr(be, "truncated_long_adjoint") and hasattr(be, "truncated_long_adjoint_fits")):
-            return False
-        (A, M, D), (B, N), es = dx.shape, dy.shape[:2], dx.element_size()
-        if be.route(_lib.OP_TRUNCATED_LONG, 1, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
-            return False
-        if dx.requires_grad and not be.truncated_long_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
-            return False
-        if dy.requires_grad and not sym and not be.truncated_long_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
-            return False
-        return True
-
-    def _wide_adjoint_serves(self, dx, dy, L, order, paired, sym):
-        """wide_adjoint=True applies (asked where _hip_serves declined): step tensors on a HIP device with a gradient pending, order 1, no
-        empty axis, the forward in the kernel's scope on (dx, dy) or (dy, dx), and every side that needs a gradient in the wide-adjoint
-        mode's, a block's slab within the workspace"""
-        if not (self.wide_adjoint and _on_hip(dx) and order == 1 and min(dx.shape[0], dx.shape[1], dy.shape[0], dy.shape[1]) > 0):
-            return False
-        if not (torch.is_grad_enabled() and (dx.requires_grad or dy.requires_grad)):
-            return False
-        be = _lib.get_backend()
-        if not (hasattr(be, "truncated_levels") and hasattr(be, "truncated_wide_adjoint") and hasattr(be, "truncated_wide_adjoint_fits")):
-            return False
-        (A, M, D), (B, N), es = dx.shape, dy.shape[:2], dx.element_size()
-        if be.route(_lib.OP_TRUNCATED, 1, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
-            return False
-        if dx.requires_grad and not be.truncated_wide_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
-            return False
-        if dy.requires_grad and not sym and not be.truncated_wide_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
-            return False
-        return True
-
-    def _points_adjoint_serves(self, X, Y, L, order, paired, sym):
-        """points_adjoint=True applies: point tensors on a HIP device with a gradient pending, order 1, no empty batch, the forward in the
-        points mode's scope on (X, Y) or (Y, X), and every side that needs a gradient in the points-adjoint mode's, its slab in the workspace"""
-        if not (self.points_adjoint and _on_hip(X) and order == 1 and min(X.shape[0], Y.shape[0]) > 0):
-            return False
-        if not (torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad)):
-            return False
-        be = _lib.get_backend()
-        if not (hasattr(be, "truncated_levels") and hasattr(be, "truncated_points_adjoint_fits")):
-            return False
-        (A, M, D), (B, N), es = X.shape, Y.shape[:2], X.element_size()
-        if be.route(_lib.OP_TRUNCATED_RBF, 1, D, M, N, L, False, es) == _lib.ROUTE_STREAM:
-            return False
-        if X.requires_grad and not be.truncated_points_adjoint_fits(A, B, M, N, D, L, paired, self.workspace_bytes, es):
-            return False
-        if Y.requires_grad and not sym and not be.truncated_points_adjoint_fits(B, A, N, M, D, L, paired, self.workspace_bytes, es):
-            return False
-        return True
 
     def _lifted_levels(self, X, Y, static_kernel, L, order, paired, sym=False):
         """the level terms of the POINTS X, Y under `static_kernel`: the HIP kernel's points mode for an RBFKernel where it serves (a HIP
         device, sk_route_query(SK_OP_TRUNCATED_RBF) on (X, Y) or (Y, X), and no gradient pending -- or points_adjoint=True and
-        _points_adjoint_serves: _LiftedLevels), else the restatement on the lifted G"""
+        the _POINTS route serves: _RouteLevels), else the restatement on the lifted G"""
         param = static_kernel.sigma if type(static_kernel) is RBFKernel else None
-        if param is not None and not isinstance(param, torch.Tensor) and float(param) > 0 and self._points_adjoint_serves(X, Y, L, order, paired, sym):
+        if param is not None and not isinstance(param, torch.Tensor) and float(param) > 0 and self._route_serves(_POINTS, X, Y, L, order, paired, sym):
             Xc = X.contiguous()
-            return _LiftedLevels.apply(Xc, Xc if Y is X else Y.contiguous(), L, float(param), paired, sym, self.workspace_bytes)
+            return _RouteLevels.apply(Xc, Xc if Y is X else Y.contiguous(), _POINTS, L, order, float(param), paired, sym, self.workspace_bytes)
         if param is not None and _on_hip(X) and not _needs_grad(X, Y, param) and min(X.shape[0], Y.shape[0]) > 0:
             be = _lib.get_backend()
             if hasattr(be, "truncated_levels") and be.route(_lib.OP_TRUNCATED_RBF, order, X.shape[2], X.shape[1], Y.shape[1], L, False,
                                                             X.element_size()) != _lib.ROUTE_STREAM:
-                call = lambda x, y: be.truncated_levels(x, y, L, order, paired=paired, kind=1, param=float(param))
-                lev = _routed(_chunked(call, self.workspace_bytes, 1) if paired else call, X.detach().contiguous(),
-                              Y.detach().contiguous(), not paired)
+                lev = _route_levels(be, _POINTS, X.contiguous(), Y.contiguous(), L, order, float(param), paired, self.workspace_bytes)
                 if lev is not None:
                     return lev
         return _truncated_levels_torch(X, Y, L, order, paired, self.workspace_bytes, _lifted_gram(static_kernel))
@@ -754,15 +654,11 @@ class TruncatedSigKernel:
             return self._lifted_levels(X, Y, static_kernel, L, order, paired, sym)
         dx = X[:, 1:] - X[:, :-1]
         dy = dx if Y is X else Y[:, 1:] - Y[:, :-1]
-        if self._hip_serves(dx, dy, L, order, paired, sym):
-            dx = dx.contiguous()
-            return _TruncatedLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, order, paired, sym, self.workspace_bytes)
-        if self._wide_adjoint_serves(dx, dy, L, order, paired, sym):     # opt-in: path dims 9 .. 16, a gradient pending
-            dx = dx.contiguous()
-            return _WideLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, 1, paired, sym, self.workspace_bytes)
-        if self._long_adjoint_serves(dx, dy, L, order, paired, sym):     # opt-in: steps beyond the adjoint mode's, a gradient pending
-            dx = dx.contiguous()
-            return _LongLevels.apply(dx, dx if dy is dx else dy.contiguous(), L, 1, paired, sym, self.workspace_bytes)
+        # the route every object has; opt-in with a gradient pending: path dims 9 .. 16, then steps beyond the adjoint mode's
+        for route in (_PLAIN, _WIDE, _LONG):
+            if self._route_serves(route, dx, dy, L, order, paired, sym):
+                dx = dx.contiguous()
+                return _RouteLevels.apply(dx, dx if dy is dx else dy.contiguous(), route, L, order, None, paired, sym, self.workspace_bytes)
         if _on_hip(dx) and _long_serves(_lib.get_backend(), dx, dy, None, order):     # opt-in: steps beyond the plain launch, no gradient pending
             lev = _long(_lib.get_backend(), dx.contiguous(), dy.contiguous(), L, None, paired, self.workspace_bytes)
             if lev is not None:
