@@ -21,35 +21,43 @@ def _free_port():
     return port
 
 
-def _worker(rank, world, port, name, out_dir):
+def _worker(rank, world, port, name, out_dir, patterns=(None,)):
+    """patterns: fill bytes -- the rank makes its calls once under each, inside tests/poison.py's poisoned(byte), and writes
+    rank<r>.p<byte>.npz (tests/test_poison_host.py); None: as they are, rank<r>.npz"""
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
+        import contextlib
         import sigkernel_amd
         from sigkernel_amd import _lib
         from fake_backend import OracleBackend
+        from poison import poisoned
         _lib.set_backend(OracleBackend())
-        c = golden(name)
-        X, Y, w = (torch.from_numpy(c[k]) for k in ("X", "Y", "w"))
-        sk = sigkernel_amd.SigKernel(make_kernel(c), int(c["dyadic"]), _naive_solver=bool(c["naive"]),
-                                     process_group=dist.group.WORLD)
-        Xg = X.clone().requires_grad_(True)
-        K = sk.compute_Gram(Xg, Y)
-        (K * w).sum().backward(retain_graph=True)
-        res = {"gram": K.detach().numpy(), "grad_w": Xg.grad.numpy().copy()}
-        # a second backward through the same graph must give the same gradient again (not zeros)
-        (g2,) = torch.autograd.grad((K * w).sum(), Xg)
-        res["grad_w_again"] = g2.numpy()
-        if "mmd" in c:
-            Xg = X.clone().requires_grad_(True)
-            mmd = sk.compute_mmd(Xg, Y)
-            mmd.backward()
-            res["mmd"] = mmd.detach().numpy()
-            res["grad_mmd"] = Xg.grad.numpy()
-        np.savez(os.path.join(out_dir, "rank%d.npz" % rank), **res)
+        for pattern in patterns:
+            with contextlib.nullcontext() if pattern is None else poisoned(pattern) as poison:
+                c = golden(name)
+                X, Y, w = (torch.from_numpy(c[k]) for k in ("X", "Y", "w"))
+                sk = sigkernel_amd.SigKernel(make_kernel(c), int(c["dyadic"]), _naive_solver=bool(c["naive"]),
+                                             process_group=dist.group.WORLD)
+                Xg = X.clone().requires_grad_(True)
+                K = sk.compute_Gram(Xg, Y)
+                (K * w).sum().backward(retain_graph=True)
+                res = {"gram": K.detach().numpy(), "grad_w": Xg.grad.numpy().copy()}
+                # a second backward through the same graph must give the same gradient again (not zeros)
+                (g2,) = torch.autograd.grad((K * w).sum(), Xg)
+                res["grad_w_again"] = g2.numpy()
+                if "mmd" in c:
+                    Xg = X.clone().requires_grad_(True)
+                    mmd = sk.compute_mmd(Xg, Y)
+                    mmd.backward()
+                    res["mmd"] = mmd.detach().numpy()
+                    res["grad_mmd"] = Xg.grad.numpy()
+                if poison is not None:
+                    res["intercepted"] = np.array(poison.count)
+                np.savez(os.path.join(out_dir, "rank%d%s.npz" % (rank, "" if pattern is None else ".p%02x" % pattern)), **res)
     finally:
         dist.destroy_process_group()
 
