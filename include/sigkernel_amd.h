@@ -170,6 +170,10 @@ size_t sk_launch_trace_dump(char *buf, size_t n, int reset);
 
 /* kappa_d = 4^-d / sqrt(12), see sk_solve_fwd_linear_*. */
 double sk_linear_prescale(int dyadic);
+/* The multiplier and shift by which the fused forward divides a pair index by the Gram's column count B (host arithmetic only, no
+ * device): floor(p / B) = (uint32_t)(((uint64_t)(2 p) * *mul) >> 32) >> *shift for every 0 <= p < 2^31.  SK_ERR_BAD_ARG unless
+ * 1 <= B < 2^31. */
+int sk_pair_div_magic(int64_t B, uint32_t *mul, int *shift);
 const char *sk_status_string(int status);
 /* Number of HIP devices visible, or a negative sk_status. */
 int sk_device_count(void);

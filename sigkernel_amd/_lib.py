@@ -57,6 +57,7 @@ SIGNATURES = {
     "sk_launch_trace": (_int, [_int]),
     "sk_launch_trace_dump": (ctypes.c_size_t, [ctypes.c_char_p, ctypes.c_size_t, _int]),
     "sk_linear_prescale": (ctypes.c_double, [_int]),
+    "sk_pair_div_magic": (_int, [_i64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]),
     "sk_status_string": (ctypes.c_char_p, [_int]),
     "sk_device_count": (_int, []),
     "sk_increments_f64": (_int, [_vp, _i64, _int, _int, _vp, _i64, _vp]),

@@ -155,6 +155,22 @@ inline int one_band_geometry(const OneBandShape &in, OneBandGeom &o) {
     return SK_OK;
 }
 
+// Division of a pair index by the Gram's column count B as a multiply and a shift (Granlund & Montgomery 1994, round-up form for
+// 31-bit dividends): with l = ceil(log2 B) and m = ceil(2^(31 + l) / B), 2^(31 + l) <= m B <= 2^(31 + l) + 2^l, hence
+//     floor(p / B) = floor(p m / 2^(31 + l)) = mulhi(2 p, m) >> l      for every 0 <= p < 2^31,
+// and m < 2^32 because B > 2^(l - 1).  The kernels form p < P <= 0x7ff00000 only.  Returns nonzero for a B outside [1, 2^31).
+inline int div_magic(uint32_t B, unsigned &m, int &shift) {
+    if (B < 1 || B >= 0x80000000u) return 1;
+    int l = 0;
+    while ((1ull << l) < B) ++l;
+    const unsigned long long num = 1ull << (31 + l);
+    const unsigned long long mm = (num + B - 1) / B;
+    if (mm >> 32) return 1;
+    m = (unsigned)mm;
+    shift = l;
+    return 0;
+}
+
 // The equal share of a launch of P stream positions on waves of G lane groups: as many waves as the positions need, at most max_waves.
 inline void even_share(int64_t P, int G, int64_t max_waves, int64_t &waves, int64_t &per) {
     waves = (P + G - 1) / G;

@@ -79,6 +79,10 @@ struct FusedParams {
     // a = G (q / B) + g, b = q % B (no such pair when a >= A), and everything above that says "G C0" / "w G C0" reads without the G.
     // Consulted in the prologue, the producers and the (rarely taken) store branch, never in the step loop.
     int shy_A;
+    // floor(p / B) for every pair index the kernel can form (p < 2^31) as a multiply and a shift (div_magic, sk_pair_stream.h);
+    // B <= 0: unused.  Consulted where a producer's stream position changes and in the store branch, never in the step loop.
+    unsigned div_m;
+    int div_s;
 };
 template <int N>
 __device__ __forceinline__ void lds_read_units(d2_t (&v)[N], unsigned addr);
@@ -312,23 +316,67 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
 
     // ---- producers (uniform control; per-lane source offsets) ------------------------------------------------
     // y slab s = virtual units [8s, 8s+8) of every lane group: dims k = lane/8, unit x = lane%8
-    // The producers run once per 8 macro-steps with wave-uniform control.  Their cursors advance incrementally (no division
-    // by NUp); the pair -> (a, b) split and its tables of the triangular layouts: pair_split (sk_pair_stream.h).
-    auto split_ab = [&](int64_t p, bool want_b) __attribute__((always_inline)) -> int64_t { return pair_split<true, FD>(prm, p, want_b); };
-    auto split_b = [&](int64_t p) -> int64_t { return split_ab(p, true); };
-    auto split_a = [&](int64_t p) -> int64_t { return split_ab(p, false); };
+    // The producers run once per XW (x) or 8 (y) macro-steps with wave-uniform control.  Their cursors advance incrementally (no
+    // division by NUp); the pair -> (a, b) split is split_ab below: pair_split of sk_pair_stream.h (which k_fwd_prefix and the
+    // multi-band forward keep as it is: their parameter blocks carry no multiplier) with its division by B as a multiply and a shift.
+    // p / B by the launcher's multiplier and shift (exact for p < 2^31: div_magic); both behind an opaque move, like shy_a
+    auto div_b = [&](unsigned p) __attribute__((always_inline)) -> unsigned {
+        unsigned m = prm.div_m;
+        int sh = prm.div_s;
+        asm volatile("" : "+s"(m), "+s"(sh));
+        return __umulhi(p << 1, m) >> sh;
+    };
+    // pair -> its row a or column b (what pair_split of sk_pair_stream.h does, with the division as a multiply-shift): wave-uniform
+    auto split_ab = [&](unsigned p, bool want_b) __attribute__((always_inline)) -> int {
+        if (prm.B <= 0) return (int)p;
+        if (prm.tri) {
+            const int *tab = reinterpret_cast<const int *>(prm.dYt + prm.B * (int64_t)FD * prm.Ncp);
+            return __builtin_amdgcn_readfirstlane(tab[2 * (int64_t)p + (want_b ? 1 : 0)]);
+        }
+        const unsigned q = div_b(p);
+        return (int)(want_b ? p - q * (unsigned)prm.B : q);
+    };
+    // WHAT A PRODUCER FETCHES CHANGES ONLY WHERE ITS STREAM POSITION DOES -- every NUp macro-steps -- while it visits every XW (x) or 8
+    // (y) of them.  So the look-up of a position (ensure, chunk, ring, bounds, split) runs ONCE, in the visit that opens it, and what it
+    // found is parked in the lanes of one VGPR, read back by the visits with one v_readlane each:
+    //   lanes 0..7:  the x row a of lane group g at stream position pi, at lane (pi mod NS) G + g.  NS = 8 / G = L / 8 positions are
+    //                kept, and the x producer reaches JMAX = ceil(L / NUp) <= NS of them back (the laps of lanes NUp and more behind);
+    //   lanes 8..15: the column b of y ring g at position y_pi, at lane 8 + g.
+    // (As scalars they would be live across the step loop, whose scalar file is full: see FusedParams::tri.)  All zero before the first
+    // position: row 0 and column 0, something valid to fetch for the positions before the stream's first, never consumed.
+    // PARK = false: the three edge-keeping instances that sit one register pair under the 128-VGPR line (127, 125, 125) have no
+    // register to hold across the step loop -- they look every position up in every visit, as all instances did before, and the lanes
+    // live inside a visit only.
+    constexpr bool PARK = !(EDGES && ((KIND == 0 && DY == 0 && ND == 4 && !FULLWAVE) || (KIND == 1 && DY == 2 && ND == 8 && FULLWAVE)));
+    int pos_ab = 0;
+    // (... nor for the lane offsets of the DMA sources, which the compiler would hoist out of the step loop: an opaque lane number)
+    auto dma_lane = [&]() __attribute__((always_inline)) -> int {
+        int l = lane;
+        if constexpr (!PARK) asm volatile("" : "+v"(l));
+        return l;
+    };
+    const int NS = L >> 3;
     int y_pi = 0, y_u0 = 0, y_slot = 0, y_par = 0;   // next y slab: pair-in-group, first unit (NUp % 8 == 0: no straddling),
     auto issue_y = [&]() __attribute__((always_inline)) {                            // ring slot, parity of the virtual slab number
-        ensure(y_pi);
         const int gy = shy_a() > 0 ? 1 : G;
-        for (int g = 0; g < gy; ++g) {   // (shared-y: one ring, filled in the g = 0 form; position % B is the pair's b)
-            const unsigned sp = stream_pair(g, y_pi);
-            const int64_t p = sp == NOPAIR ? 0 : (int64_t)sp;   // past the end: fetch something valid, never consumed
-            const int64_t b = split_b(p);
-            const int krow = (lane >> 3) ^ ((y_par + g) & 1);   // odd slabs (per group): dimension rows swapped in pairs
-            const double *src = prm.dYt + ((b * FD + krow) * (int64_t)prm.Ncp + (int64_t)(y_u0 + (lane & 7)) * 2);
-            if (ND == 8 || lane < 32)   // (ND = 4: dimension rows 0..3 = the lower half of the wave; LDS-DMA writes lane l's 16 bytes at base + 16 l)
-                __builtin_amdgcn_global_load_lds(src, (lds_void *)(lds + g * y_bytes + y_slot * Y_SLAB_PITCH), 16, 0, 0);
+        if constexpr (!PARK) pos_ab = 0;
+        const int ln = dma_lane();
+        if (!PARK || y_u0 == 0) {        // a new position: its column b, per ring (shared-y: one ring; position % B is the pair's b)
+            ensure(y_pi);
+            for (int g = 0; g < gy; ++g) {
+                const unsigned sp = stream_pair(g, y_pi);
+                const int b = split_ab(sp == NOPAIR ? 0u : sp, true);   // past the end: fetch something valid, never consumed
+                pos_ab = lane == 8 + g ? b : pos_ab;
+            }
+        }
+        for (int g = 0; g < gy; ++g) {
+            const int b = __builtin_amdgcn_readlane(pos_ab, 8 + g);
+            const int krow = (ln >> 3) ^ ((y_par + g) & 1);   // odd slabs (per group): dimension rows swapped in pairs
+            // (a wave-uniform base and a 32-bit lane offset: the launcher keeps 64 Ncp below 2^32)
+            const char *src = reinterpret_cast<const char *>(prm.dYt) + (int64_t)b * (FD * 8) * (int64_t)prm.Ncp;
+            const unsigned so = ((unsigned)krow * (unsigned)prm.Ncp + (unsigned)(y_u0 + (ln & 7)) * 2u) * 8u;
+            if (ND == 8 || ln < 32)   // (ND = 4: dimension rows 0..3 = the lower half of the wave; LDS-DMA writes lane l's 16 bytes at base + 16 l)
+                __builtin_amdgcn_global_load_lds(src + so, (lds_void *)(lds + g * y_bytes + y_slot * Y_SLAB_PITCH), 16, 0, 0);
         }
         y_slot = y_slot + 1 == NSLAB ? 0 : y_slot + 1;
         y_par ^= 1;
@@ -339,29 +387,44 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // t0/NUp - j, rows (lam0 + j*NUp .. +XW-1)*RC of its x
     int x_q0 = 0, x_lam0 = 0, x_slot = 0;   // next window: t0 / NUp, t0 % NUp, ring slot
     auto issue_x = [&]() __attribute__((always_inline)) {
-        ensure(x_q0);
-        for (int j = 0; j < JMAX; ++j) {
-            const int lamj = x_lam0 + j * NUp, pi = x_q0 - j;
-            if (lamj >= L) break;
-            // shared-y: position pi is row a = G (pi's position / B) + g for lane group g (no such row: fetch something valid, never
-            // stored) -- branch-free in the mode: a = gm a + gs g with (gm, gs, a_lim) = (G, 1, A) or (1, 0, "no limit")
+        if constexpr (!PARK) pos_ab = 0;
+        const int ln = dma_lane();
+        if (!PARK || x_lam0 == 0) {      // a new position: its rows, per lane group (not PARK: every position this visit reaches)
+            ensure(x_q0);
+            // shared-y: a = G (position / B) + g, one look-up for all groups; no such row / pair: 0 -- something valid, never stored
             const int sA = shy_a();
-            const int64_t gm = sA > 0 ? G : 1, gs = sA > 0 ? 1 : 0, a_lim = sA > 0 ? sA : 0x7fffffff;
-            for (int g = 0; g < G; ++g) {
-                const unsigned sp = stream_pair(g, pi);
-                const int64_t p = sp == NOPAIR ? 0 : (int64_t)sp;
-                int64_t a = split_a(p);
-                if constexpr (!EDGES && !FULLWAVE) {
-                    a = a * gm + gs * g;
-                    if (a >= a_lim) a = 0;
+            for (int jd = 0; jd < (PARK ? 1 : JMAX); ++jd) {
+                const int at = ((x_q0 - jd) & (NS - 1)) * G;
+                int qa = 0;
+                for (int g = 0; g < G; ++g) {
+                    if (sA <= 0 || g == 0) {
+                        const unsigned sp = stream_pair(g, x_q0 - jd);
+                        qa = split_ab(sp == NOPAIR ? 0u : sp, false);
+                    }
+                    int a = qa;
+                    if constexpr (!EDGES && !FULLWAVE) {
+                        if (sA > 0) {
+                            const int64_t ag = (int64_t)qa * G + g;
+                            a = ag >= sA ? 0 : (int)ag;
+                        }
+                    }
+                    pos_ab = lane == at + g ? a : pos_ab;
                 }
-                const char *src = reinterpret_cast<const char *>(prm.dXr + (a * prm.Mrows + (int64_t)lamj * RC) * FD);
+            }
+        }
+        for (int j = 0; j < JMAX; ++j) {
+            const int lamj = x_lam0 + j * NUp;
+            if (lamj >= L) break;
+            const int at = ((x_q0 - j) & (NS - 1)) * G;
+            for (int g = 0; g < G; ++g) {
+                const int a = __builtin_amdgcn_readlane(pos_ab, at + g);
+                const char *src = reinterpret_cast<const char *>(prm.dXr + ((int64_t)a * prm.Mrows + (int64_t)lamj * RC) * FD);
                 char *dst = lds + x_base0 + ((g * X_SLOTS + x_slot) * JMAX + j) * XSLAB;
 #pragma unroll
                 for (int c = 0; c < (XSLAB + 1023) / 1024; ++c)
-                    if (c * 1024 + lane * 16 < XSLAB) {
+                    if (c * 1024 + ln * 16 < XSLAB) {
                         // LDS-DMA lands lane l's 16 bytes at dst + 16 l; XROW = 32: the first two 16-byte pieces of every 64-byte row
-                        const int so = XROW == 64 ? c * 1024 + lane * 16 : (c * 32 + (lane >> 1)) * 64 + (lane & 1) * 16;
+                        const unsigned so = XROW == 64 ? c * 1024 + ln * 16 : (c * 32 + (ln >> 1)) * 64 + (ln & 1) * 16;
                         __builtin_amdgcn_global_load_lds(src + so, (lds_void *)(dst + c * 1024), 16, 0, 0);
                     }
             }
@@ -758,7 +821,10 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             unsigned pair_u = lane_pair(pv);
             const int sA = shy_a();
             if (sA > 0 && pair_u != NOPAIR) {   // position -> this lane group's pair: a = G (q / B) + grp, b = q % B, out index a B + b
-                const unsigned Bu = (unsigned)prm.B, qa = pair_u / Bu, a = qa * (unsigned)G + (unsigned)grp;
+                unsigned dm = prm.div_m;   // (per lane here: the multiply-shift of div_b on the vector unit)
+                int ds = prm.div_s;
+                asm volatile("" : "+s"(dm), "+s"(ds));
+                const unsigned Bu = (unsigned)prm.B, qa = __umulhi(pair_u << 1, dm) >> ds, a = qa * (unsigned)G + (unsigned)grp;
                 pair_u = a < (unsigned)sA ? a * Bu + (pair_u - qa * Bu) : NOPAIR;
             }
             const int64_t pair_v = (int64_t)pair_u;
@@ -1087,6 +1153,11 @@ int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B,
     prm.sel_f = ((g.Mc - 1) % RC) * 2 + (g.Nc - 1) % 2;
     prm.naive = g.naive;
     prm.shy_A = shy ? (int)A : 0;
+    prm.div_m = 0; prm.div_s = 0;
+    if (B > 0) {
+        if (B >= 0x7ff00000LL || div_magic((uint32_t)B, prm.div_m, prm.div_s)) return SK_ERR_UNSUPPORTED;
+    }
+    if ((int64_t)Ncp * 64 >= 0x100000000LL) return SK_ERR_UNSUPPORTED;   // (the y producer's lane offsets are 32-bit)
     switch (DY) {
         case 0: return launch_fused_dy<TO, 0, KIND>(prm, pl, s);
         case 1: return launch_fused_dy<TO, 1, KIND>(prm, pl, s);
@@ -1095,6 +1166,17 @@ int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B,
 }
 
 }  // namespace
+
+// (the launcher's own div_magic, for the host test of the multiply-shift)
+extern "C" int sk_pair_div_magic(int64_t B, uint32_t *mul, int *shift) {
+    if (!mul || !shift || B < 1 || B >= 0x80000000LL) return SK_ERR_BAD_ARG;
+    unsigned m = 0;
+    int sh = 0;
+    if (div_magic((uint32_t)B, m, sh)) return SK_ERR_BAD_ARG;
+    *mul = m;
+    *shift = sh;
+    return SK_OK;
+}
 
 template <typename TO>
 int launch_fwd_fused_linear(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
