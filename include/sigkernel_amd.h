@@ -58,6 +58,8 @@ typedef enum sk_status {
                                * sk_solve_fwd_edges_* wrote for these increments -- skip the forward sweep */
 #define SK_FLAG_FAST_ONLY 4 /* never fall back: SK_ERR_UNSUPPORTED if the tiled kernels do not
                                cover the shape/layout (used by tests and benchmarks)            */
+#define SK_FLAG_DISCRETE 16 /* sk_solve_adj_* only: W is the exact derivative of the returned value with respect to every coarse
+                             * increment -- the adjoint of the DISCRETE solver, not the reference's formula (see sk_solve_adj_*) */
 
 /* 340.  The number moves whenever an exported signature changes incompatibly: 310 -> 320 gave sk_solve_fwd_{linear,rbf}_sym_* their
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
@@ -730,12 +732,22 @@ int sk_solve_fwd_linear_edges_f64(const double *dXr, const double *dYt, int64_t 
  *   simple -- both grids stored in `workspace`, products summed in the reference's order: bit-identical to the
  *             reference formula evaluated by the CPU oracle (SK_FLAG_EXACT / SK_FLAG_SIMPLE, or any shape
  *             the fast path does not cover).  out_err is zero-filled.
+ *   SK_FLAG_DISCRETE -- not the reference's formula (which discretises the continuous adjoint PDE and differs from the derivative of
+ *             the computed number by O(h): tens of per cent of the path gradient at dyadic 0..2) but the exact adjoint of the solver's
+ *             own recurrence K[i+1][j+1] = (K[i+1][j] + K[i][j+1]) P(g_ij) - K[i][j] Q(g_ij):  with u[i][j] = dK[MM][NN] / dK[i+1][j+1],
+ *               u[MM-1][NN-1] = 1,  u[i][j] = P(g[i][j+1]) u[i][j+1] + P(g[i+1][j]) u[i+1][j] - Q(g[i+1][j+1]) u[i+1][j+1],
+ *               W[a][b] = 4^-d * sum over the fine cells of (a,b) of u[i][j] ((K[i+1][j] + K[i][j+1]) P'(g_ij) - K[i][j] Q'(g_ij)).
+ *             Always the stored-grid kernel (K and the cells' terms in `workspace`, the same size as for SK_FLAG_SIMPLE; summed in a
+ *             fixed order: bit-reproducible, no atomics); out_err is zero-filled; SK_FLAG_EDGES_GIVEN is ignored (`workspace` is
+ *             scratch, kept edges are of no use to it); with SK_FLAG_FAST_ONLY: SK_ERR_BAD_ARG.  Both schemes, fp64 and fp32
+ *             increments (fp64 state either way).
  *   workspace: sk_adj_workspace_bytes(...) bytes of device scratch.
  *   inc_c [P,Mc,ld]; out_final nullable [P]; W [P,Mc,ldw] (ldw = 0: dense); out_err nullable [P] doubles. */
 size_t sk_adj_workspace_bytes(int64_t P, int Mc, int Nc, int dyadic, int flags, int elem_size);
 /*   flags = SK_FLAG_FAST_ONLY: what the fast implementation alone needs (P (edges + 1) doubles; 0 when it does not cover
  *   the shape) -- the stored-grid figure grows with min(P, 1024) whole grids and is only needed for SK_FLAG_SIMPLE /
- *   SK_FLAG_EXACT calls or shapes the fast kernels do not cover. */
+ *   SK_FLAG_EXACT calls or shapes the fast kernels do not cover; SK_FLAG_DISCRETE: the stored-grid figure (any k >= 1 slots of
+ *   sk_adj_rescue_slot_bytes(Mc, Nc, dyadic) bytes serve: the blocks stride over the pairs). */
 
 /* Device-side rescue of the fast adjoint: re-solves with stored grids exactly the pairs whose self-check residual
  * err[p] (as written by sk_solve_adj_*) exceeds `tol`, overwriting their W (and out_final when non-NULL); a NaN residual is

@@ -29,6 +29,7 @@ FLAG_EXACT = 1
 FLAG_SIMPLE = 2
 FLAG_FAST_ONLY = 4
 FLAG_EDGES_GIVEN = 8
+FLAG_DISCRETE = 16
 # the nodes of the prefix grid a call keeps (SK_NODES_* of include/sigkernel_amd.h)
 PREFIX_NODES = {"all": 0, "diagonal": 1, "last_row": 2, "last_col": 3}
 
@@ -1495,12 +1496,16 @@ class HipBackend:
     # residual of the fast adjoint's self-check above which a pair is re-solved by the stored-grid kernel
     ADJ_RESIDUAL_TOL = 1e-8
 
-    def solve_adj(self, inc_c, dyadic, naive=False, flags=0, return_residual=False, edges=None):
+    def solve_adj(self, inc_c, dyadic, naive=False, flags=0, return_residual=False, edges=None, discrete=False):
         """inc_c [..., Mc, Nc] -> (final [...], W [..., Mc, Nc] = d final / d inc_c).
 
         The fast kernel recomputes K backwards instead of storing it and reports a per-pair residual; pairs whose
         residual exceeds ADJ_RESIDUAL_TOL (K exploding beyond ~1e4) are re-solved by the stored-grid kernel.
-        `edges` (from solve_fwd_keep_edges on the same increments) skips the forward sweep; `final` is then None."""
+        `edges` (from solve_fwd_keep_edges on the same increments) skips the forward sweep; `final` is then None.
+        discrete: W is the exact derivative of `final` -- the adjoint of the discrete solver (SK_FLAG_DISCRETE), not the
+        reference's formula; always the stored-grid kernel, any dyadic order; `edges` are ignored and the residuals are zeros."""
+        if discrete:
+            return self._solve_adj_discrete(inc_c, dyadic, naive, return_residual)
         if edges is not None:
             # edges kept by another kernel in its own layout (sk_solve_fwd_static_* keeps sk_rbf_adjoint_fused_mb_f64's): sweep forward here
             P_ = inc_c.numel() // (inc_c.shape[-2] * inc_c.shape[-1])
@@ -1574,6 +1579,28 @@ class HipBackend:
         if return_residual:
             return out, W, err
         return out, W
+
+    def _solve_adj_discrete(self, inc_c, dyadic, naive, return_residual):
+        inc_c, ld = _row_stride(inc_c, "inc_c")
+        Mc, Nc = inc_c.shape[-2:]
+        batch = inc_c.shape[:-2]
+        P = inc_c.numel() // (Mc * Nc)
+        dev = inc_c.device
+        out = torch.empty(batch, dtype=inc_c.dtype, device=dev)
+        ldw = _padded_ld(Nc, inc_c.element_size())
+        Wp = torch.empty(batch + (Mc, ldw), dtype=inc_c.dtype, device=dev)
+        err = torch.empty(batch, dtype=torch.float64, device=dev)
+        if P:
+            with _device(dev):
+                ws, nbytes = self._grid_scratch(P, Mc, Nc, dyadic, dev, 1024)
+                if not nbytes:
+                    raise RuntimeError("sigkernel_amd: the stored-grid kernel cannot hold a grid of %d fine rows: no exact gradient "
+                                       "for paths this long" % (Mc << int(dyadic)))
+                fn = getattr(load(), "sk_solve_adj_" + _suffix(inc_c))
+                _check(fn(_ptr(inc_c), ld, P, Mc, Nc, int(dyadic), SCHEME_NAIVE if naive else SCHEME_DEFAULT, FLAG_DISCRETE, _ptr(out),
+                          _ptr(Wp), ldw, _ptr(err), _ptr(ws), nbytes, _stream(inc_c)), "sk_solve_adj (discrete)")
+        W = Wp[..., :Nc]
+        return (out, W, err) if return_residual else (out, W)
 
     RESCUE_SLOTS = 64                   # flagged pairs re-solved concurrently by sk_adj_rescue_*
     GRID_SCRATCH_BYTES = 2 << 30        # cap on the stored-grid scratch (whole pairs of solution grids)

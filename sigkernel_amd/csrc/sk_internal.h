@@ -89,7 +89,8 @@ inline Geom make_geom(int64_t P, int Mc, int Nc, int dyadic, int scheme, int64_t
 template <typename T>
 int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, double *out_edges, hipStream_t s);
 template <typename T>
-int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes, hipStream_t s);
+int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes, hipStream_t s,
+                      bool discrete = false);   // discrete: the exact adjoint of the discrete solver (adj_pair_discrete)
 // K, K_gamma, K_gamma_gamma (directional derivatives) from three increment arrays of equal layout
 template <typename T>
 int launch_deriv_simple(const T *inc, const T *inc_d, const T *inc_dd, const Geom &g, T *out_k, T *out_kd, T *out_kdd,

@@ -90,5 +90,61 @@ __device__ void adj_pair(const T *__restrict__ inc, int64_t ld, int Mc, int Nc, 
     __syncthreads();
 }
 
+// Coefficients of the stencil K11 = (K10 + K01) P(g) - K00 Q(g) and their derivatives in g.
+__device__ __forceinline__ double stencil_p(double g, int naive) { return naive ? 1. + 0.5 * g : (1. + 0.5 * g) + (1. / 12.) * (g * g); }
+__device__ __forceinline__ double stencil_q(double g, int naive) { return naive ? 1. : 1. - (1. / 12.) * (g * g); }
+
+// Exact adjoint of the DISCRETE solver for one pair: W = d K[MM][NN] / d inc_c, the derivative of the number sweep_pair returns (adj_pair's
+// K * K~ is the continuous PDE's formula, an O(h) approximation of it).  With u[i][j] = d K[MM][NN] / d K[i+1][j+1] on the fine cells:
+//   u[MM-1][NN-1] = 1,   u[i][j] = P(g[i][j+1]) u[i][j+1] + P(g[i+1][j]) u[i+1][j] - Q(g[i+1][j+1]) u[i+1][j+1]   (cells outside the grid: dropped)
+//   W[a][b] = 4^-d sum over the fine cells of (a, b) of u[i][j] ((K[i+1][j] + K[i][j+1]) P'(g) - K[i][j] Q'(g))
+// Phase 1 stores the node grid K (sweep_pair), phase 2 sweeps u over the anti-diagonals from the far corner -- three live diagonals in
+// the same 3 (MM + 1) doubles of LDS, indexed by i -- and stores every cell's term to the slot's second grid (row stride NN), phase 3 sums
+// each coarse cell's r * r terms in i-major order: no atomics, the same bits on every run.  Every word of both grids that is read was
+// written for this pair, and a dropped term is never loaded.
+template <typename T>
+__device__ void adj_pair_discrete(const T *__restrict__ inc, int64_t ld, int Mc, int Nc, int d, int naive, double *lds, double *Kf,
+                                  double *Tm, T *__restrict__ out_final_p, T *__restrict__ Wp, int64_t ldw) {
+    const int lane = threadIdx.x;
+    const int MM = Mc << d, NN = Nc << d, r = 1 << d;
+    const double rs = 1.0 / (double)r;
+    const int64_t gw = NN + 1;
+    const double v = sweep_pair<T, double, false>(inc, ld, Mc, Nc, d, naive, lds, Kf, nullptr);
+    __syncthreads();
+    if (lane == 0 && out_final_p) *out_final_p = (T)v;
+    double *d0 = lds, *d1 = lds + (MM + 1), *d2 = lds + 2 * (MM + 1);   // diagonals t + 2, t + 1 and t of u
+    for (int t = MM + NN - 2; t >= 0; --t) {
+        const int ilo = max(0, t - (NN - 1)), ihi = min(MM - 1, t);
+        for (int i = ilo + lane; i <= ihi; i += WAVE) {
+            const int j = t - i;
+            const bool down = i + 1 < MM, right = j + 1 < NN;
+            const T *row = inc + (int64_t)(i >> d) * ld, *row1 = inc + (int64_t)((i + 1) >> d) * ld;
+            double u = (down || right) ? 0. : 1.;
+            if (right) u += stencil_p(((double)row[(j + 1) >> d] * rs) * rs, naive) * d1[i];
+            if (down) u += stencil_p(((double)row1[j >> d] * rs) * rs, naive) * d1[i + 1];
+            if (down && right) u -= stencil_q(((double)row1[(j + 1) >> d] * rs) * rs, naive) * d0[i + 1];
+            d2[i] = u;
+        }
+        // (a pass of its own: each lane reads back the u it wrote itself, and the two passes' registers do not add up)
+        for (int i = ilo + lane; i <= ihi; i += WAVE) {
+            const int j = t - i;
+            const double g = ((double)inc[(int64_t)(i >> d) * ld + (j >> d)] * rs) * rs;
+            const double *kf = Kf + ((int64_t)i * gw + j);
+            const double dp = naive ? 0.5 : 0.5 + (1. / 6.) * g, dq = naive ? 0. : -(1. / 6.) * g;
+            Tm[(int64_t)i * NN + j] = d2[i] * ((kf[gw] + kf[1]) * dp - kf[0] * dq);
+        }
+        __syncthreads();
+        double *s = d0; d0 = d1; d1 = d2; d2 = s;
+    }
+    for (int c = lane; c < Mc * Nc; c += WAVE) {
+        const int a = c / Nc, b = c - a * Nc;
+        double acc = 0.;
+        for (int ii = 0; ii < r; ++ii)
+            for (int jj = 0; jj < r; ++jj) acc += Tm[(int64_t)(a * r + ii) * NN + (b * r + jj)];
+        Wp[(int64_t)a * ldw + b] = (T)((acc * rs) * rs);
+    }
+    __syncthreads();
+}
+
 }  // namespace
 }  // namespace sk

@@ -6,7 +6,9 @@
 // reference's generated C (sigkernel/cython_backend.pyx:114-116), so its results are
 // bit-identical to the reference's CPU solver.  It serves SK_FLAG_EXACT / SK_FLAG_SIMPLE
 // requests, shapes the tiled kernels do not cover, full-grid output, and the robust adjoint
-// (stored grids) that backs up the fast adjoint when its self-check trips.
+// (stored grids) that backs up the fast adjoint when its self-check trips.  The same adjoint
+// kernel has a launch-time mode for SK_FLAG_DISCRETE: the exact adjoint of the discrete solver
+// (adj_pair_discrete, sk_pair_sweep.h) instead of the reference's formula.
 //
 // Reference behaviour replaced: sigkernel_cuda / sigkernel_Gram_cuda (cuda_backend.py:6-49,
 // :121-160) -- without their global-memory solution buffer, 1024-thread limit or
@@ -34,14 +36,25 @@ __global__ __launch_bounds__(WAVE) void k_fwd_simple(const T *__restrict__ inc_c
 }
 
 
+// `mode`: bit 0 the naive stencil, bit 1 (ADJ_DISCRETE, wave-uniform) the exact adjoint of the discrete solver (adj_pair_discrete)
+// instead of the reference's formula (adj_pair) -- a launch-time mode of the same two instances, in the argument that carried the stencil.
+constexpr int ADJ_DISCRETE = 2;
+
 template <typename T>
 __global__ __launch_bounds__(WAVE) void k_adj_simple(const T *__restrict__ inc_c, int64_t ld, int64_t P, int Mc, int Nc, int d,
-                                                     int naive, T *__restrict__ out_final, T *__restrict__ W,
+                                                     int mode, T *__restrict__ out_final, T *__restrict__ W,
                                                      int64_t ldw, double *__restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int64_t gs = (int64_t)((Mc << d) + 1) * ((Nc << d) + 1);
     double *Kf = ws + (int64_t)blockIdx.x * 2 * gs;
     double *Kr = Kf + gs;
+    const int naive = mode & 1;
+    if (mode & ADJ_DISCRETE) {
+        for (int64_t p = blockIdx.x; p < P; p += gridDim.x)
+            adj_pair_discrete<T>(inc_c + p * (int64_t)Mc * ld, ld, Mc, Nc, d, naive, lds, Kf, Kr, out_final ? out_final + p : nullptr,
+                                 W + p * (int64_t)Mc * ldw, ldw);
+        return;
+    }
     for (int64_t p = blockIdx.x; p < P; p += gridDim.x)
         adj_pair<T>(inc_c + p * (int64_t)Mc * ld, ld, Mc, Nc, d, naive, lds, Kf, Kr, out_final ? out_final + p : nullptr,
                     W + p * (int64_t)Mc * ldw, ldw);
@@ -186,7 +199,7 @@ int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, 
 
 template <typename T>
 int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes,
-                      hipStream_t s) {
+                      hipStream_t s, bool discrete) {
     const size_t lds = simple_lds_bytes(g);
     if (lds > 160 * 1024) return SK_ERR_UNSUPPORTED;
     const int64_t gs = (int64_t)(g.MM + 1) * (g.NN + 1);
@@ -194,11 +207,11 @@ int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t
     if (!ws || ws_bytes < per_block) return SK_ERR_WORKSPACE;
     int64_t blocks = (int64_t)(ws_bytes / per_block);
     if (blocks > g.P) blocks = g.P;
-    if (blocks > 1024) blocks = 1024;
+    if (blocks > 1024) blocks = 1024;      // (4096 blocks were measured for the discrete mode: no gain, profiles/exact_gradient.txt)
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)k_adj_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     SK_LAUNCH(k_adj_simple<T>, dim3((int)blocks), dim3(WAVE), lds, s, inc_c, g.ld, g.P, g.Mc, g.Nc, g.dyadic,
-                       g.naive, out_final, W, ldw, (double *)ws);
+                       g.naive | (discrete ? ADJ_DISCRETE : 0), out_final, W, ldw, (double *)ws);
     return check_launch();
 }
 
@@ -230,8 +243,8 @@ template int launch_adj_rescue<float>(const float *, const Geom &, const double 
 template int launch_fwd_simple<double>(const double *, const Geom &, double *, double *, double *, hipStream_t);
 template int launch_fwd_simple<float>(const float *, const Geom &, float *, float *, double *, hipStream_t);
 template int launch_adj_simple<double>(const double *, const Geom &, double *, double *, int64_t, void *, size_t,
-                                       hipStream_t);
-template int launch_adj_simple<float>(const float *, const Geom &, float *, float *, int64_t, void *, size_t, hipStream_t);
+                                       hipStream_t, bool);
+template int launch_adj_simple<float>(const float *, const Geom &, float *, float *, int64_t, void *, size_t, hipStream_t, bool);
 
 template <typename T>
 int launch_deriv_simple(const T *inc, const T *inc_d, const T *inc_dd, const Geom &g, T *out_k, T *out_kd, T *out_kdd,

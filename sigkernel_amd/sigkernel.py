@@ -755,6 +755,101 @@ class _SigKernelGram(torch.autograd.Function):
         return grad_X, None, None, None, None, None, None
 
 
+def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need_y):
+    """(dL/dX, dL/dY) of one tile under exact_gradient=True (None where not needed): increments -> sk_solve_adj_* with SK_FLAG_DISCRETE
+    (W = the exact derivative of the solver's value with respect to every coarse increment) -> the chain rule through the static
+    kernel for BOTH arguments, from the same W.
+
+    Linear / RBF: sk_static_adjoint for X; for Y sk_static_adjoint2 (Gram) or, where that has no kernel (paired batches, linear paths
+    wider than 8 dims), sk_static_adjoint on the swapped pairs with W transposed (both static kernels are symmetric).
+    Generic (any duck-typed static kernel): sk_increments_adjoint + ONE vector-Jacobian product through the static kernel for both."""
+    fused = _fused_static(static_kernel, gram)
+    inc = None
+    if fused is not None and hasattr(be, "static_adjoint"):
+        inc = be.static_increments(fused[0], fused[1], Xt, Yt, gram)
+    if inc is not None:
+        kind, param = fused
+        _, W = be.solve_adj(inc, dyadic, naive, discrete=True)
+        del inc
+        gx = be.static_adjoint(kind, param, Xt, Yt, W, go, gram) if need_x else None
+        gy = None
+        if need_y:
+            if gram and hasattr(be, "static_adjoint2"):
+                gy = be.static_adjoint2(kind, param, Xt, Yt, W, go, 0)
+            if gy is None:
+                Wt = (W.transpose(0, 1) if gram else W).transpose(-1, -2).contiguous()     # the pair (b, a), cells (j, i)
+                gy = be.static_adjoint(kind, param, Yt, Xt, Wt, go.t().contiguous() if gram else go, gram)
+        return gx, gy
+    Xg, Yg = Xt.clone().requires_grad_(need_x), Yt.clone().requires_grad_(need_y)
+    with torch.enable_grad():
+        G = static_kernel.Gram_matrix(Xg, Yg) if gram else static_kernel.batch_kernel(Xg, Yg)
+    _, W = be.solve_adj(be.increments(G.detach().contiguous()), dyadic, naive, discrete=True)
+    dG = be.increments_adjoint(W, go)
+    del W
+    wrt = [t for t, need in ((Xg, need_x), (Yg, need_y)) if need]
+    grads = list(torch.autograd.grad(G, wrt, dG, allow_unused=True))
+    gx = (grads.pop(0) if need_x else None)
+    gy = (grads.pop(0) if need_y else None)
+    return (torch.zeros_like(Xt) if need_x and gx is None else gx), (torch.zeros_like(Yt) if need_y and gy is None else gy)
+
+
+def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspace_bytes, need_x, need_y):
+    """(dL/dX, dL/dY) of a Gram block (go (A, B)) or a paired batch (go (A,)) under exact_gradient=True, over row tiles sized like
+    _rows_gradient's streaming tiles, with the stored-grid scratch of the discrete adjoint (min(pairs, 1024) slots of two fine grids,
+    at most _lib.HipBackend.GRID_SCRATCH_BYTES) taken out of the budget first -- though never more than half of it.  fp32 paths are
+    up-cast: the whole backward runs in fp64 and the gradients are rounded to fp32 at the end."""
+    if Xd.dtype != torch.float64:
+        gx, gy = _exact_gradient(be, static_kernel, Xd.double(), Yd.double(), go.double(), dyadic, naive, gram, workspace_bytes,
+                                 need_x, need_y)
+        return (None if gx is None else gx.to(Xd.dtype)), (None if gy is None else gy.to(Yd.dtype))
+    A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
+    Bp = Yd.shape[0] if gram else 1
+    budget = _budget(Xd.device, workspace_bytes)
+    slot = 16 * (((M - 1) << dyadic) + 1) * (((N - 1) << dyadic) + 1)
+    scratch = min(min(1024, A * Bp) * slot, getattr(be, "GRID_SCRATCH_BYTES", 2 << 30))
+    fused = _fused_static(static_kernel, gram) is not None
+    per_row = (3 if fused else 8) * Bp * M * N * Xd.element_size()
+    gx = torch.empty_like(Xd) if need_x else None
+    gy = torch.zeros_like(Yd) if (need_y and gram) else (torch.empty_like(Yd) if need_y else None)
+    for a0, a1 in _tiles(A, per_row, max(budget - scratch, budget // 2)):
+        tx, ty = _exact_tile(be, static_kernel, Xd[a0:a1].contiguous(), Yd if gram else Yd[a0:a1].contiguous(), go[a0:a1].contiguous(),
+                             dyadic, naive, gram, need_x, need_y)
+        if need_x:
+            gx[a0:a1] = tx
+        if need_y and gram:
+            gy += ty            # every row tile meets every path of Y
+        elif need_y:
+            gy[a0:a1] = ty
+    return gx, gy
+
+
+class _SigKernelExact(torch.autograd.Function):
+    """compute_kernel / compute_Gram under SigKernel(exact_gradient=True): the values of _SigKernel / _SigKernelGram on whatever route
+    they take without a gradient pending (nothing is kept for backward), and in backward the TRUE gradient of those values -- the
+    adjoint of the discrete solver (sk_solve_adj_* with SK_FLAG_DISCRETE), for both arguments.  No 2x rule: when X is Y, autograd adds
+    the two contributions."""
+
+    @staticmethod
+    def forward(ctx, X, Y, static_kernel, dyadic_order, gram, sym, _naive_solver, workspace_bytes):
+        ctx.save_for_backward(X, Y)
+        ctx.args = (static_kernel, dyadic_order, gram, _naive_solver, workspace_bytes)
+        if gram:
+            return _SigKernelGram.forward(_NoGradCtx(), X, Y, static_kernel, dyadic_order, sym, _naive_solver, workspace_bytes)
+        return _SigKernel.forward(_NoGradCtx(), X, Y, static_kernel, dyadic_order, _naive_solver, workspace_bytes)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        X, Y = ctx.saved_tensors
+        static_kernel, d, gram, naive, workspace_bytes = ctx.args
+        need_x, need_y = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        if X.shape[1] < 2 or Y.shape[1] < 2 or X.shape[0] == 0 or Y.shape[0] == 0:   # single points / empty batches: k = 1 whatever the paths
+            gx, gy = (torch.zeros_like(X) if need_x else None), (torch.zeros_like(Y) if need_y else None)
+        else:
+            gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, X.detach().contiguous(), Y.detach().contiguous(),
+                                     grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y)
+        return gx, gy, None, None, None, None, None, None
+
+
 def k_kgrad(X, Y, gamma, dyadic_order, static_kernel, eps=1e-4, workspace_bytes=None):
     """Signature kernel and its first / second directional derivative along gamma -- the reference's ``k_kgrad``
     (sigkernel.py:504-593): X (A,M,D), Y (B,N,D), gamma (A,M,D) -> three (A,B) matrices
@@ -1134,14 +1229,28 @@ class SigKernel:
     Extra, optional: ``workspace_bytes`` bounds the transient HBM a call may use (default: half of
     the free memory, at most 48 GiB); ``process_group`` shards ``compute_Gram`` rows over the ranks
     of a ``torch.distributed`` group (see :mod:`sigkernel_amd.distributed`).
+
+    ``exact_gradient`` (default False): which gradient ``backward`` returns.  False: the reference's adjoint formula
+    ``sum K[i][j] K~[i+1][j+1] d inc[i][j]`` -- the continuous PDE's, the parity contract; it is NOT the derivative of the number the
+    forward pass computes (tens of per cent away at dyadic orders 0..2, so ``torch.autograd.gradcheck`` fails), only X receives it, and
+    ``compute_Gram(X, X)`` relies on the reference's 2x rule.  True: the exact adjoint of the discrete solver ("Exact
+    gradient"): forward values as ever, on whatever route they take; X AND Y receive the true gradient of those values (no 2x rule:
+    where X is Y autograd adds the two), ``compute_mmd`` / ``compute_distance`` / the scoring rules become compositions of
+    ``compute_Gram`` / ``compute_kernel`` and accept a Y that requires grad.  The backward solves every pair with the stored-grid
+    kernel (a few times the cost of the default's fused adjoints) and runs in fp64: fp32 paths are up-cast for it and their gradients
+    rounded to fp32 at the end.  Not sharded (``process_group`` raises ``NotImplementedError``); prefix and ragged calls stay forward
+    only; ``RBFKernel.sigma`` receives no gradient.
     """
 
-    def __init__(self, static_kernel, dyadic_order, _naive_solver=False, workspace_bytes=None, process_group=None):
+    def __init__(self, static_kernel, dyadic_order, _naive_solver=False, workspace_bytes=None, process_group=None, exact_gradient=False):
+        if exact_gradient and process_group is not None:
+            raise NotImplementedError("exact_gradient=True is not sharded over a process group; use a SigKernel without process_group")
         self.static_kernel = static_kernel
         self.dyadic_order = dyadic_order
         self._naive_solver = _naive_solver
         self.workspace_bytes = workspace_bytes
         self.process_group = process_group
+        self.exact_gradient = bool(exact_gradient)
 
     def _on_features(self):
         """(SigKernel of the base kernel, feature map) when the static kernel is one of function-valued paths, else None: the one
@@ -1149,7 +1258,8 @@ class SigKernel:
         paths through torch autograd of the feature map."""
         if not _functional(self.static_kernel):
             return None
-        inner = SigKernel(self.static_kernel.base_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes, self.process_group)
+        inner = SigKernel(self.static_kernel.base_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes, self.process_group,
+                          self.exact_gradient)
         return inner, _FeatureMap(self.static_kernel)
 
     def compute_kernel(self, X, Y, max_batch=100):
@@ -1165,6 +1275,8 @@ class SigKernel:
             return sharded_kernel(self, X, Y, self.process_group)
         if not _wants_grad(X, Y):
             return _SigKernel.forward(_NoGradCtx(), X, Y, self.static_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes)
+        if self.exact_gradient:
+            return _SigKernelExact.apply(X, Y, self.static_kernel, self.dyadic_order, False, False, self._naive_solver, self.workspace_bytes)
         return _SigKernel.apply(X, Y, self.static_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes)
 
     def _prefixes(self, X, Y, gram, max_batch, nodes="all"):
@@ -1297,17 +1409,19 @@ class SigKernel:
         if not _wants_grad(X, Y):
             return _SigKernelGram.forward(_NoGradCtx(), X, Y, self.static_kernel, self.dyadic_order, sym, self._naive_solver,
                                           self.workspace_bytes)
+        if self.exact_gradient:
+            return _SigKernelExact.apply(X, Y, self.static_kernel, self.dyadic_order, True, sym, self._naive_solver, self.workspace_bytes)
         return _SigKernelGram.apply(X, Y, self.static_kernel, self.dyadic_order, sym, self._naive_solver,
                                     self.workspace_bytes)
 
     def compute_distance(self, X, Y, max_batch=100):
         """(batch,) paired squared distances reduced to their mean, as the reference does (sigkernel.py:130-144)."""
-        assert not Y.requires_grad, "the second input should not require grad"
+        assert self.exact_gradient or not Y.requires_grad, "the second input should not require grad"
         f = self._on_features()
         if f is not None:
             return f[0].compute_distance(f[1](X), f[1](Y), max_batch)
         n = X.shape[0] if X.dim() == 3 else 0
-        if (not routes.no_merged_loss and X.dim() == 3 and X.shape == Y.shape and X.dtype == Y.dtype and X.device == Y.device and n > 0
+        if (not self.exact_gradient and not routes.no_merged_loss and X.dim() == 3 and X.shape == Y.shape and X.dtype == Y.dtype and X.device == Y.device and n > 0
                 and X.shape[1] >= 2 and float(n) * float((X.shape[1] - 1) << int(self.dyadic_order)) ** 2 < _cost("paired_merge_cells")):
             # training-sized batches: k(x_i, x_i) and k(x_i, y_i) as ONE paired batch of 2n pairs -- one forward and one adjoint launch
             # instead of two each (launch- and fill-bound at these sizes); the same per-pair values, and the gradient reaches X through
@@ -1322,7 +1436,7 @@ class SigKernel:
 
     def compute_scoring_rule(self, X, y, max_batch=100):
         """S(X, y) = E[k(X, X)] - 2 E[k(X, y)] with y of shape (1, len_y, dim) (sigkernel.py:146-161)."""
-        assert not y.requires_grad, "the second input should not require grad"
+        assert self.exact_gradient or not y.requires_grad, "the second input should not require grad"
         f = self._on_features()
         if f is not None:
             return f[0].compute_scoring_rule(f[1](X), f[1](y), max_batch)
@@ -1336,7 +1450,7 @@ class SigKernel:
 
     def compute_expected_scoring_rule(self, X, Y, max_batch=100):
         """S(X, Y) = E_Y[S(X, y)] (sigkernel.py:163-178)."""
-        assert not Y.requires_grad, "the second input should not require grad"
+        assert self.exact_gradient or not Y.requires_grad, "the second input should not require grad"
         f = self._on_features()
         if f is not None:
             return f[0].compute_expected_scoring_rule(f[1](X), f[1](Y), max_batch)
@@ -1356,8 +1470,8 @@ class SigKernel:
         1.27 / 4.16 / 15.1 ms against 0.58 / 0.58 / 0.80 / 1.57 / 4.48 / 15.5 at 16 / 32 / 64 / 128 / 256 / 512 paths of
         BASELINE configs[1]'s shape), fewer than two paths (the reference's 0 / 0), malformed inputs (the Gram calls raise for
         those), `routes.no_merged_loss`."""
-        if routes.no_merged_loss or self.process_group is not None or X.dim() != 3 or Y.dim() != 3:
-            return None
+        if self.exact_gradient or routes.no_merged_loss or self.process_group is not None or X.dim() != 3 or Y.dim() != 3:
+            return None      # (exact_gradient: the loss is a composition of compute_Gram calls, each with its true gradient)
         A, B = X.shape[0], Y.shape[0]
         if X.shape[1:] != Y.shape[1:] or X.shape[1] < 2 or A < 2 or B < (2 if with_yy else 1) or X.dtype != Y.dtype or X.device != Y.device:
             return None
@@ -1379,7 +1493,7 @@ class SigKernel:
         faster at 16..64 paths (tools/experiments/r04_mmd_streams.py), bit-identical gradients.  Eager calls stay on one stream:
         they are bound by the host's launch rate there, and the stream switches cost more than the overlap returns (0.59 -> 0.75 ms
         at 32 paths); large batches fill the chip with one launch (round 3: no gain from streams at BASELINE configs[3])."""
-        assert not Y.requires_grad, "the second input should not require grad"
+        assert self.exact_gradient or not Y.requires_grad, "the second input should not require grad"
         f = self._on_features()
         if f is not None:
             return f[0].compute_mmd(f[1](X), f[1](Y), max_batch)
