@@ -60,6 +60,8 @@ typedef enum sk_status {
                                cover the shape/layout (used by tests and benchmarks)            */
 #define SK_FLAG_DISCRETE 16 /* sk_solve_adj_* only: W is the exact derivative of the returned value with respect to every coarse
                              * increment -- the adjoint of the DISCRETE solver, not the reference's formula (see sk_solve_adj_*) */
+#define SK_FLAG_RAGGED 32 /* sk_solve_adj_* only, and only together with SK_FLAG_DISCRETE: every pair is differentiated on its own
+                           * sub-grid, read from a table at the head of `workspace` (see sk_solve_adj_*) */
 
 /* 340.  The number moves whenever an exported signature changes incompatibly: 310 -> 320 gave sk_solve_fwd_{linear,rbf}_sym_* their
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
@@ -741,13 +743,24 @@ int sk_solve_fwd_linear_edges_f64(const double *dXr, const double *dYt, int64_t 
  *             fixed order: bit-reproducible, no atomics); out_err is zero-filled; SK_FLAG_EDGES_GIVEN is ignored (`workspace` is
  *             scratch, kept edges are of no use to it); with SK_FLAG_FAST_ONLY: SK_ERR_BAD_ARG.  Both schemes, fp64 and fp32
  *             increments (fp64 state either way).
+ *   SK_FLAG_DISCRETE | SK_FLAG_RAGGED -- pairs of unequal length in one padded batch.  `workspace` begins with a table the caller has
+ *             written (on `stream`, or before): P entries {int32 mc, int32 nc}, the coarse cells of pair p's own paths on either side
+ *             (length - 1), then padding up to the next multiple of 256 bytes, then the k >= 1 scratch slots of
+ *             sk_adj_rescue_slot_bytes(Mc, Nc, dyadic) bytes; sk_adj_workspace_bytes with both flags is the head plus min(P, 1024) slots.
+ *             Each entry is clamped to [0, Mc] x [0, Nc].  out_final[p] = K at node (mc << dyadic, nc << dyadic) of the padded pair
+ *             -- the kernel of the truncated paths -- and W[p] its exact derivative: the sweep above over the cells a < mc, b < nc
+ *             alone (bit for bit what the contiguous sub-block inc_c[p][:mc][:nc] gives on its own), and 0 on every other cell of the
+ *             Mc x Nc block; mc == 0 or nc == 0: out_final[p] = 1, W[p] = 0, nothing swept.  Columns b >= Nc of W (ldw padding) are
+ *             not written.  SK_FLAG_RAGGED without SK_FLAG_DISCRETE, or with SK_FLAG_FAST_ONLY: SK_ERR_BAD_ARG; a workspace that
+ *             holds the head but not one slot: SK_ERR_WORKSPACE.
  *   workspace: sk_adj_workspace_bytes(...) bytes of device scratch.
  *   inc_c [P,Mc,ld]; out_final nullable [P]; W [P,Mc,ldw] (ldw = 0: dense); out_err nullable [P] doubles. */
 size_t sk_adj_workspace_bytes(int64_t P, int Mc, int Nc, int dyadic, int flags, int elem_size);
 /*   flags = SK_FLAG_FAST_ONLY: what the fast implementation alone needs (P (edges + 1) doubles; 0 when it does not cover
  *   the shape) -- the stored-grid figure grows with min(P, 1024) whole grids and is only needed for SK_FLAG_SIMPLE /
  *   SK_FLAG_EXACT calls or shapes the fast kernels do not cover; SK_FLAG_DISCRETE: the stored-grid figure (any k >= 1 slots of
- *   sk_adj_rescue_slot_bytes(Mc, Nc, dyadic) bytes serve: the blocks stride over the pairs). */
+ *   sk_adj_rescue_slot_bytes(Mc, Nc, dyadic) bytes serve: the blocks stride over the pairs); SK_FLAG_DISCRETE | SK_FLAG_RAGGED: the
+ *   table's head (8 P bytes rounded up to a multiple of 256) plus that figure; SK_FLAG_RAGGED without SK_FLAG_DISCRETE: 0. */
 
 /* Device-side rescue of the fast adjoint: re-solves with stored grids exactly the pairs whose self-check residual
  * err[p] (as written by sk_solve_adj_*) exceeds `tol`, overwriting their W (and out_final when non-NULL); a NaN residual is

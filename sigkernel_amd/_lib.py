@@ -30,6 +30,7 @@ FLAG_SIMPLE = 2
 FLAG_FAST_ONLY = 4
 FLAG_EDGES_GIVEN = 8
 FLAG_DISCRETE = 16
+FLAG_RAGGED = 32
 # the nodes of the prefix grid a call keeps (SK_NODES_* of include/sigkernel_amd.h)
 PREFIX_NODES = {"all": 0, "diagonal": 1, "last_row": 2, "last_col": 3}
 
@@ -1496,16 +1497,22 @@ class HipBackend:
     # residual of the fast adjoint's self-check above which a pair is re-solved by the stored-grid kernel
     ADJ_RESIDUAL_TOL = 1e-8
 
-    def solve_adj(self, inc_c, dyadic, naive=False, flags=0, return_residual=False, edges=None, discrete=False):
+    def solve_adj(self, inc_c, dyadic, naive=False, flags=0, return_residual=False, edges=None, discrete=False, cells=None):
         """inc_c [..., Mc, Nc] -> (final [...], W [..., Mc, Nc] = d final / d inc_c).
 
         The fast kernel recomputes K backwards instead of storing it and reports a per-pair residual; pairs whose
         residual exceeds ADJ_RESIDUAL_TOL (K exploding beyond ~1e4) are re-solved by the stored-grid kernel.
         `edges` (from solve_fwd_keep_edges on the same increments) skips the forward sweep; `final` is then None.
         discrete: W is the exact derivative of `final` -- the adjoint of the discrete solver (SK_FLAG_DISCRETE), not the
-        reference's formula; always the stored-grid kernel, any dyadic order; `edges` are ignored and the residuals are zeros."""
+        reference's formula; always the stored-grid kernel, any dyadic order; `edges` are ignored and the residuals are zeros.
+        cells (with discrete only): int32 [..., 2] on the increments' device, one row (mc, nc) per pair -- the coarse cells of the
+        pair's own paths, length - 1 on either side (SK_FLAG_RAGGED).  `final` is then K at node (mc << dyadic, nc << dyadic) of the
+        padded pair and W its exact derivative: swept over the cells a < mc, b < nc alone, exactly zero on the others; rows are
+        clamped to [0, Mc] x [0, Nc], and a pair with mc == 0 or nc == 0 gives 1 and zeros."""
+        if cells is not None and not discrete:
+            raise ValueError("solve_adj: cells= is a mode of discrete=True")
         if discrete:
-            return self._solve_adj_discrete(inc_c, dyadic, naive, return_residual)
+            return self._solve_adj_discrete(inc_c, dyadic, naive, return_residual, cells)
         if edges is not None:
             # edges kept by another kernel in its own layout (sk_solve_fwd_static_* keeps sk_rbf_adjoint_fused_mb_f64's): sweep forward here
             P_ = inc_c.numel() // (inc_c.shape[-2] * inc_c.shape[-1])
@@ -1580,24 +1587,34 @@ class HipBackend:
             return out, W, err
         return out, W
 
-    def _solve_adj_discrete(self, inc_c, dyadic, naive, return_residual):
+    def _solve_adj_discrete(self, inc_c, dyadic, naive, return_residual, cells=None):
         inc_c, ld = _row_stride(inc_c, "inc_c")
         Mc, Nc = inc_c.shape[-2:]
         batch = inc_c.shape[:-2]
         P = inc_c.numel() // (Mc * Nc)
         dev = inc_c.device
+        flags, head = FLAG_DISCRETE, 0
+        if cells is not None:
+            _dev(cells, "cells")
+            if cells.dtype != torch.int32 or cells.device != dev or tuple(cells.shape) != tuple(batch) + (2,):
+                raise ValueError("solve_adj: cells must be an int32 tensor of shape %s on %s, got %s %s on %s"
+                                 % (tuple(batch) + (2,), dev, cells.dtype, tuple(cells.shape), cells.device))
+            flags |= FLAG_RAGGED
+            head = (8 * P + 255) // 256 * 256       # the table {mc, nc} of every pair, rounded up: the slots follow it
         out = torch.empty(batch, dtype=inc_c.dtype, device=dev)
         ldw = _padded_ld(Nc, inc_c.element_size())
         Wp = torch.empty(batch + (Mc, ldw), dtype=inc_c.dtype, device=dev)
         err = torch.empty(batch, dtype=torch.float64, device=dev)
         if P:
             with _device(dev):
-                ws, nbytes = self._grid_scratch(P, Mc, Nc, dyadic, dev, 1024)
+                ws, nbytes = self._grid_scratch(P, Mc, Nc, dyadic, dev, 1024, head)
                 if not nbytes:
                     raise RuntimeError("sigkernel_amd: the stored-grid kernel cannot hold a grid of %d fine rows: no exact gradient "
                                        "for paths this long" % (Mc << int(dyadic)))
+                if head:      # on the current stream, ahead of the launch that reads it
+                    ws[:8 * P].view(torch.int32).copy_(cells.reshape(-1))
                 fn = getattr(load(), "sk_solve_adj_" + _suffix(inc_c))
-                _check(fn(_ptr(inc_c), ld, P, Mc, Nc, int(dyadic), SCHEME_NAIVE if naive else SCHEME_DEFAULT, FLAG_DISCRETE, _ptr(out),
+                _check(fn(_ptr(inc_c), ld, P, Mc, Nc, int(dyadic), SCHEME_NAIVE if naive else SCHEME_DEFAULT, flags, _ptr(out),
                           _ptr(Wp), ldw, _ptr(err), _ptr(ws), nbytes, _stream(inc_c)), "sk_solve_adj (discrete)")
         W = Wp[..., :Nc]
         return (out, W, err) if return_residual else (out, W)
@@ -1605,10 +1622,10 @@ class HipBackend:
     RESCUE_SLOTS = 64                   # flagged pairs re-solved concurrently by sk_adj_rescue_*
     GRID_SCRATCH_BYTES = 2 << 30        # cap on the stored-grid scratch (whole pairs of solution grids)
 
-    def _grid_scratch(self, P, Mc, Nc, dyadic, dev, max_slots):
+    def _grid_scratch(self, P, Mc, Nc, dyadic, dev, max_slots, head=0):
         """(uint8 tensor, bytes) holding up to max_slots pairs of solution grids, within GRID_SCRATCH_BYTES (at least one slot;
         raises when a single slot exceeds half of the free memory even after releasing torch's cached blocks; (None, 0) when
-        the stored-grid kernel cannot hold the grid at all)."""
+        the stored-grid kernel cannot hold the grid at all).  `head`: bytes in front of the slots (the ragged table)."""
         if not int(load().sk_adj_rescue_slot_bytes(Mc, Nc, int(dyadic))):
             return None, 0
         slot = int(load().sk_adj_rescue_slot_bytes(Mc, Nc, int(dyadic)))
@@ -1623,7 +1640,7 @@ class HipBackend:
         if n < 1:
             raise RuntimeError("sigkernel_amd: no memory for one stored-grid scratch slot (%d bytes): pairs that fail the fast "
                                "adjoint's self-check could not be re-solved" % slot)
-        return torch.empty(n * slot, dtype=torch.uint8, device=dev), n * slot
+        return torch.empty(head + n * slot, dtype=torch.uint8, device=dev), head + n * slot
 
     def deriv_increments(self, G0, G1, G2, eps):
         """Static Gram matrices [..., M, N] of X, X + eps*gamma, X + 2*eps*gamma -> one tensor [3, ..., M-1, N-1]:

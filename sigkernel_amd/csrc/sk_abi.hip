@@ -54,12 +54,13 @@ size_t adj_fast_workspace_bytes(const Geom &g, int elem_size) {
 template <typename T>
 int solve_adj(const T *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, T *out_final, T *W,
               int64_t ldw, double *out_err, void *ws, size_t ws_bytes, void *stream) {
-    const bool discrete = (flags & SK_FLAG_DISCRETE) != 0;
+    const bool discrete = (flags & SK_FLAG_DISCRETE) != 0, ragged = (flags & SK_FLAG_RAGGED) != 0;
+    if (ragged && !discrete) return SK_ERR_BAD_ARG;   // the sub-grid table is a mode of the discrete adjoint alone
     if (discrete) {
         // the exact adjoint of the discrete solver: always the stored-grid kernel, so kept edges are of no use (ignored) and
         // SK_FLAG_FAST_ONLY cannot be honoured
         if (flags & SK_FLAG_FAST_ONLY) return SK_ERR_BAD_ARG;
-        flags &= ~(SK_FLAG_DISCRETE | SK_FLAG_EDGES_GIVEN);
+        flags &= ~(SK_FLAG_DISCRETE | SK_FLAG_RAGGED | SK_FLAG_EDGES_GIVEN);
     }
     if (bad_common(inc_c, P, Mc, Nc, dyadic, scheme, flags) || !W || (ld != 0 && ld < Nc) || (ldw != 0 && ldw < Nc))
         return SK_ERR_BAD_ARG;
@@ -69,7 +70,7 @@ int solve_adj(const T *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic,
     hipStream_t s = (hipStream_t)stream;
     if (discrete) {
         if (out_err && hipMemsetAsync(out_err, 0, sizeof(double) * (size_t)P, s) != hipSuccess) return SK_ERR_LAUNCH;
-        return launch_adj_simple<T>(inc_c, g, out_final, W, ldw, ws, ws_bytes, s, true);
+        return launch_adj_simple<T>(inc_c, g, out_final, W, ldw, ws, ws_bytes, s, true, ragged);
     }
     const bool fast_shape = dyadic >= 0 && dyadic <= (sizeof(T) == 8 ? 2 : 1);   // launch_adj_wave's scope
     const size_t fast_ws = fast_shape ? adj_fast_workspace_bytes(g, (int)sizeof(T)) : 0;
@@ -838,6 +839,7 @@ size_t sk_adj_workspace_bytes(int64_t P, int Mc, int Nc, int dyadic, int flags, 
     if (P <= 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16 || (elem_size != 4 && elem_size != 8)) return 0;
     const Geom g = make_geom(P, Mc, Nc, dyadic, SK_SCHEME_DEFAULT);
     const size_t simple = adj_simple_workspace_bytes(g);
+    if (flags & SK_FLAG_RAGGED) return (flags & SK_FLAG_DISCRETE) ? adj_ragged_head_bytes(P) + simple : 0;
     if (flags & (SK_FLAG_EXACT | SK_FLAG_SIMPLE | SK_FLAG_DISCRETE)) return simple;
     const bool fast_shape = dyadic <= (elem_size == 8 ? 2 : 1);   // launch_adj_wave's scope
     const size_t fast = fast_shape ? adj_fast_workspace_bytes(g, elem_size) : 0;

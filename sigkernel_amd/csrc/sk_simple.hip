@@ -39,6 +39,14 @@ __global__ __launch_bounds__(WAVE) void k_fwd_simple(const T *__restrict__ inc_c
 // `mode`: bit 0 the naive stencil, bit 1 (ADJ_DISCRETE, wave-uniform) the exact adjoint of the discrete solver (adj_pair_discrete)
 // instead of the reference's formula (adj_pair) -- a launch-time mode of the same two instances, in the argument that carried the stencil.
 constexpr int ADJ_DISCRETE = 2;
+// bit 2 (ADJ_RAGGED, wave-uniform, only together with ADJ_DISCRETE): `ws` begins with a table of P entries {int32 mc, int32 nc}, the
+// coarse cells of each pair's own sub-grid (len - 1 on either side), rounded up to a multiple of 256 bytes (adj_ragged_head_doubles:
+// a function of P, so the slots' offset travels in the arguments the kernel already has); the per-block slots follow.  Pair p is
+// swept over its (mc, nc) corner of the padded (Mc, Nc) block alone -- out_final = K at node (mc << d, nc << d) of the padded pair,
+// W = its exact derivative, zero on every cell with a >= mc or b >= nc; an empty sub-grid (mc == 0 or nc == 0) gives 1 and zeros.
+constexpr int ADJ_RAGGED = 4;
+
+__host__ __device__ inline int64_t adj_ragged_head_doubles(int64_t P) { return (P + 31) / 32 * 32; }   // 8 bytes per entry, 256-byte units
 
 template <typename T>
 __global__ __launch_bounds__(WAVE) void k_adj_simple(const T *__restrict__ inc_c, int64_t ld, int64_t P, int Mc, int Nc, int d,
@@ -50,9 +58,23 @@ __global__ __launch_bounds__(WAVE) void k_adj_simple(const T *__restrict__ inc_c
     double *Kr = Kf + gs;
     const int naive = mode & 1;
     if (mode & ADJ_DISCRETE) {
-        for (int64_t p = blockIdx.x; p < P; p += gridDim.x)
-            adj_pair_discrete<T>(inc_c + p * (int64_t)Mc * ld, ld, Mc, Nc, d, naive, lds, Kf, Kr, out_final ? out_final + p : nullptr,
-                                 W + p * (int64_t)Mc * ldw, ldw);
+        const int *cells = (mode & ADJ_RAGGED) ? reinterpret_cast<const int *>(ws) : nullptr;
+        if (cells) { Kf += adj_ragged_head_doubles(P); Kr += adj_ragged_head_doubles(P); }
+        for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
+            // the pair's own sub-grid, clamped to its block: a wrong table never reaches outside the pair's increments, W block or slot
+            const int mc = cells ? min(max(cells[2 * p], 0), Mc) : Mc, nc = cells ? min(max(cells[2 * p + 1], 0), Nc) : Nc;
+            T *Wp = W + p * (int64_t)Mc * ldw;
+            if (mc > 0 && nc > 0)
+                adj_pair_discrete<T>(inc_c + p * (int64_t)Mc * ld, ld, mc, nc, d, naive, lds, Kf, Kr, out_final ? out_final + p : nullptr,
+                                     Wp, ldw);
+            else if (threadIdx.x == 0 && out_final)
+                out_final[p] = (T)1.;
+            if (mc < Mc || nc < Nc)
+                for (int c = threadIdx.x; c < Mc * Nc; c += WAVE) {
+                    const int a = c / Nc, b = c - a * Nc;
+                    if (a >= mc || b >= nc) Wp[(int64_t)a * ldw + b] = (T)0.;
+                }
+        }
         return;
     }
     for (int64_t p = blockIdx.x; p < P; p += gridDim.x)
@@ -180,6 +202,8 @@ int pick_blocks(int64_t P) {
 
 size_t simple_lds_bytes(const Geom &g) { return sizeof(double) * 3 * (size_t)(g.MM + 1); }
 
+size_t adj_ragged_head_bytes(int64_t P) { return (size_t)adj_ragged_head_doubles(P) * sizeof(double); }
+
 size_t adj_simple_workspace_bytes(const Geom &g) {
     const int64_t gs = (int64_t)(g.MM + 1) * (g.NN + 1);
     int64_t blocks = g.P < 1024 ? g.P : 1024;
@@ -199,19 +223,21 @@ int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, 
 
 template <typename T>
 int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes,
-                      hipStream_t s, bool discrete) {
+                      hipStream_t s, bool discrete, bool ragged) {
     const size_t lds = simple_lds_bytes(g);
     if (lds > 160 * 1024) return SK_ERR_UNSUPPORTED;
+    if (ragged && !discrete) return SK_ERR_BAD_ARG;
     const int64_t gs = (int64_t)(g.MM + 1) * (g.NN + 1);
     const size_t per_block = (size_t)2 * gs * sizeof(double);
-    if (!ws || ws_bytes < per_block) return SK_ERR_WORKSPACE;
-    int64_t blocks = (int64_t)(ws_bytes / per_block);
+    const size_t head = ragged ? adj_ragged_head_bytes(g.P) : 0;   // the kernel derives the same offset from P
+    if (!ws || ws_bytes < head || ws_bytes - head < per_block) return SK_ERR_WORKSPACE;
+    int64_t blocks = (int64_t)((ws_bytes - head) / per_block);
     if (blocks > g.P) blocks = g.P;
     if (blocks > 1024) blocks = 1024;      // (4096 blocks were measured for the discrete mode: no gain, profiles/exact_gradient.txt)
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)k_adj_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     SK_LAUNCH(k_adj_simple<T>, dim3((int)blocks), dim3(WAVE), lds, s, inc_c, g.ld, g.P, g.Mc, g.Nc, g.dyadic,
-                       g.naive | (discrete ? ADJ_DISCRETE : 0), out_final, W, ldw, (double *)ws);
+                       g.naive | (discrete ? ADJ_DISCRETE : 0) | (ragged ? ADJ_RAGGED : 0), out_final, W, ldw, (double *)ws);
     return check_launch();
 }
 
@@ -243,8 +269,8 @@ template int launch_adj_rescue<float>(const float *, const Geom &, const double 
 template int launch_fwd_simple<double>(const double *, const Geom &, double *, double *, double *, hipStream_t);
 template int launch_fwd_simple<float>(const float *, const Geom &, float *, float *, double *, hipStream_t);
 template int launch_adj_simple<double>(const double *, const Geom &, double *, double *, int64_t, void *, size_t,
-                                       hipStream_t, bool);
-template int launch_adj_simple<float>(const float *, const Geom &, float *, float *, int64_t, void *, size_t, hipStream_t, bool);
+                                       hipStream_t, bool, bool);
+template int launch_adj_simple<float>(const float *, const Geom &, float *, float *, int64_t, void *, size_t, hipStream_t, bool, bool);
 
 template <typename T>
 int launch_deriv_simple(const T *inc, const T *inc_d, const T *inc_dd, const Geom &g, T *out_k, T *out_kd, T *out_kdd,

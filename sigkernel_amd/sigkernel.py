@@ -755,21 +755,33 @@ class _SigKernelGram(torch.autograd.Function):
         return grad_X, None, None, None, None, None, None
 
 
-def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need_y):
+def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need_y, cells=None):
     """(dL/dX, dL/dY) of one tile under exact_gradient=True (None where not needed): increments -> sk_solve_adj_* with SK_FLAG_DISCRETE
     (W = the exact derivative of the solver's value with respect to every coarse increment) -> the chain rule through the static
     kernel for BOTH arguments, from the same W.
 
     Linear / RBF: sk_static_adjoint for X; for Y sk_static_adjoint2 (Gram) or, where that has no kernel (paired batches, linear paths
     wider than 8 dims), sk_static_adjoint on the swapped pairs with W transposed (both static kernels are symmetric).
-    Generic (any duck-typed static kernel): sk_increments_adjoint + ONE vector-Jacobian product through the static kernel for both."""
+    Generic (any duck-typed static kernel): sk_increments_adjoint + ONE vector-Jacobian product through the static kernel for both.
+
+    cells (ragged batches): (cx, cy), int32 coarse cells (length - 1) of the tile's paths on either side.  The pairs' table -- row
+    (cx[a], cy[b]) for pair a * B + b of a Gram tile, (cx[p], cy[p]) paired -- goes with the launch (SK_FLAG_RAGGED): every pair is
+    swept on its own sub-grid and W is exactly zero elsewhere, so the chain rule below runs unchanged on the padded paths and gives
+    the padding an exactly zero gradient."""
+    more = {}
+    if cells is not None:
+        cx, cy = cells
+        if gram:
+            more["cells"] = torch.stack((cx[:, None].expand(-1, cy.shape[0]), cy[None, :].expand(cx.shape[0], -1)), dim=-1).contiguous()
+        else:
+            more["cells"] = torch.stack((cx, cy), dim=-1).contiguous()
     fused = _fused_static(static_kernel, gram)
     inc = None
     if fused is not None and hasattr(be, "static_adjoint"):
         inc = be.static_increments(fused[0], fused[1], Xt, Yt, gram)
     if inc is not None:
         kind, param = fused
-        _, W = be.solve_adj(inc, dyadic, naive, discrete=True)
+        _, W = be.solve_adj(inc, dyadic, naive, discrete=True, **more)
         del inc
         gx = be.static_adjoint(kind, param, Xt, Yt, W, go, gram) if need_x else None
         gy = None
@@ -783,7 +795,7 @@ def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need
     Xg, Yg = Xt.clone().requires_grad_(need_x), Yt.clone().requires_grad_(need_y)
     with torch.enable_grad():
         G = static_kernel.Gram_matrix(Xg, Yg) if gram else static_kernel.batch_kernel(Xg, Yg)
-    _, W = be.solve_adj(be.increments(G.detach().contiguous()), dyadic, naive, discrete=True)
+    _, W = be.solve_adj(be.increments(G.detach().contiguous()), dyadic, naive, discrete=True, **more)
     dG = be.increments_adjoint(W, go)
     del W
     wrt = [t for t, need in ((Xg, need_x), (Yg, need_y)) if need]
@@ -793,14 +805,15 @@ def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need
     return (torch.zeros_like(Xt) if need_x and gx is None else gx), (torch.zeros_like(Yt) if need_y and gy is None else gy)
 
 
-def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspace_bytes, need_x, need_y):
+def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspace_bytes, need_x, need_y, cells=None):
     """(dL/dX, dL/dY) of a Gram block (go (A, B)) or a paired batch (go (A,)) under exact_gradient=True, over row tiles sized like
     _rows_gradient's streaming tiles, with the stored-grid scratch of the discrete adjoint (min(pairs, 1024) slots of two fine grids,
     at most _lib.HipBackend.GRID_SCRATCH_BYTES) taken out of the budget first -- though never more than half of it.  fp32 paths are
-    up-cast: the whole backward runs in fp64 and the gradients are rounded to fp32 at the end."""
+    up-cast: the whole backward runs in fp64 and the gradients are rounded to fp32 at the end.  cells (ragged batches): (cx (A,), cy),
+    int32 coarse cells of every path, length - 1; each row tile takes its slice (_exact_tile)."""
     if Xd.dtype != torch.float64:
         gx, gy = _exact_gradient(be, static_kernel, Xd.double(), Yd.double(), go.double(), dyadic, naive, gram, workspace_bytes,
-                                 need_x, need_y)
+                                 need_x, need_y, cells)
         return (None if gx is None else gx.to(Xd.dtype)), (None if gy is None else gy.to(Yd.dtype))
     A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
     Bp = Yd.shape[0] if gram else 1
@@ -813,7 +826,8 @@ def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspac
     gy = torch.zeros_like(Yd) if (need_y and gram) else (torch.empty_like(Yd) if need_y else None)
     for a0, a1 in _tiles(A, per_row, max(budget - scratch, budget // 2)):
         tx, ty = _exact_tile(be, static_kernel, Xd[a0:a1].contiguous(), Yd if gram else Yd[a0:a1].contiguous(), go[a0:a1].contiguous(),
-                             dyadic, naive, gram, need_x, need_y)
+                             dyadic, naive, gram, need_x, need_y,
+                             None if cells is None else (cells[0][a0:a1], cells[1] if gram else cells[1][a0:a1]))
         if need_x:
             gx[a0:a1] = tx
         if need_y and gram:
@@ -848,6 +862,33 @@ class _SigKernelExact(torch.autograd.Function):
             gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, X.detach().contiguous(), Y.detach().contiguous(),
                                      grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y)
         return gx, gy, None, None, None, None, None, None
+
+
+class _SigKernelRaggedExact(torch.autograd.Function):
+    """compute_kernel_ragged / compute_Gram_ragged under SigKernel(exact_gradient=True): forward is _prefix_at -- the values of the
+    no-grad call, bit for bit -- and backward the true gradient of those values for both arguments: the exact adjoint of the discrete
+    solver run on every pair's own sub-grid (sk_solve_adj_* with SK_FLAG_DISCRETE | SK_FLAG_RAGGED), then _exact_gradient's chain rule
+    on the padded paths.  The padding receives exactly zero, whatever finite values it holds."""
+
+    @staticmethod
+    def forward(ctx, X, Y, lx, ly, static_kernel, dyadic_order, gram, _naive_solver, workspace_bytes):
+        ctx.save_for_backward(X, Y, lx, ly)
+        ctx.args = (static_kernel, dyadic_order, gram, _naive_solver, workspace_bytes)
+        return _prefix_at(_lib.get_backend(), static_kernel, X.detach(), Y.detach(), lx, ly, dyadic_order, _naive_solver, gram,
+                          workspace_bytes)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        X, Y, lx, ly = ctx.saved_tensors
+        static_kernel, d, gram, naive, workspace_bytes = ctx.args
+        need_x, need_y = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        if X.shape[1] < 2 or Y.shape[1] < 2 or X.shape[0] == 0 or Y.shape[0] == 0:   # single points / empty batches: k = 1 whatever the paths
+            gx, gy = (torch.zeros_like(X) if need_x else None), (torch.zeros_like(Y) if need_y else None)
+        else:
+            gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, X.detach().contiguous(), Y.detach().contiguous(),
+                                     grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y,
+                                     (lx - 1, ly - 1))
+        return gx, gy, None, None, None, None, None, None, None
 
 
 def k_kgrad(X, Y, gamma, dyadic_order, static_kernel, eps=1e-4, workspace_bytes=None):
@@ -1191,8 +1232,8 @@ def _lengths(name, lens, count, padded, device, with_host=False):
 
 def pad_paths(paths):
     """A list of (len_i, dim) tensors -> (X (batch, max len, dim), lens (batch,) int64): every path padded at its END by repeating its
-    last point, for ``SigKernel.compute_Gram_ragged`` / ``compute_kernel_ragged`` / ``compute_mmd_ragged`` (which never read the
-    padding: any finite values would do).  ``X[i, :lens[i]]`` is path i again."""
+    last point, for ``SigKernel.compute_Gram_ragged`` / ``compute_kernel_ragged`` / ``compute_mmd_ragged`` (whose values never depend
+    on the padding, and whose gradients under ``exact_gradient=True`` are exactly zero on it: any finite values would do).  ``X[i, :lens[i]]`` is path i again."""
     paths = list(paths)
     if not paths:
         raise ValueError("pad_paths needs at least one path")
@@ -1238,8 +1279,10 @@ class SigKernel:
     where X is Y autograd adds the two), ``compute_mmd`` / ``compute_distance`` / the scoring rules become compositions of
     ``compute_Gram`` / ``compute_kernel`` and accept a Y that requires grad.  The backward solves every pair with the stored-grid
     kernel (a few times the cost of the default's fused adjoints) and runs in fp64: fp32 paths are up-cast for it and their gradients
-    rounded to fp32 at the end.  Not sharded (``process_group`` raises ``NotImplementedError``); prefix and ragged calls stay forward
-    only; ``RBFKernel.sigma`` receives no gradient.
+    rounded to fp32 at the end.  Ragged batches (``compute_Gram_ragged`` / ``compute_kernel_ragged`` / ``compute_mmd_ragged``) get
+    their gradients in this mode and in this mode only: every pair's backward sweeps its own sub-grid, and the padding -- any finite
+    values -- receives exactly zero.  Not sharded (``process_group`` raises ``NotImplementedError``); prefix calls stay forward only;
+    ``RBFKernel.sigma`` receives no gradient.
     """
 
     def __init__(self, static_kernel, dyadic_order, _naive_solver=False, workspace_bytes=None, process_group=None, exact_gradient=False):
@@ -1342,11 +1385,15 @@ class SigKernel:
         _check_inputs(X, Y, paired=not gram)
         if self.process_group is not None:
             raise NotImplementedError("%s is not sharded over a process group; call it on a SigKernel without process_group" % what)
-        if _wants_grad(X, Y):
-            raise NotImplementedError("%s is forward only: gradients of ragged batches are not built.  Call it under torch.no_grad() "
-                                      "or on detached paths" % what)
+        if _wants_grad(X, Y) and not self.exact_gradient:
+            raise NotImplementedError("%s is forward only on this object: the reference's adjoint formula is not built for ragged "
+                                      "batches.  Construct the SigKernel with exact_gradient=True for their true gradient, or call it "
+                                      "under torch.no_grad() or on detached paths" % what)
         lx = _lengths("len_x", len_x, X.shape[0], X.shape[1], X.device)
         ly = _lengths("len_y", len_y, Y.shape[0], Y.shape[1], Y.device)
+        if _wants_grad(X, Y):
+            return _SigKernelRaggedExact.apply(X, Y, lx, ly, self.static_kernel, self.dyadic_order, gram, self._naive_solver,
+                                               self.workspace_bytes)
         return _prefix_at(_lib.get_backend(), self.static_kernel, X.detach(), Y.detach(), lx, ly, self.dyadic_order, self._naive_solver,
                           gram, self.workspace_bytes)
 
@@ -1359,8 +1406,15 @@ class SigKernel:
         the (batch_X, batch_Y, Lx, Ly) tensor is never built.  A path of one point gives exactly 1.  The values past a path's length
         never reach its result.  The lengths are integer tensors (any device) or sequences of ints, checked once on the host: a wrong
         count, a non-integer dtype or a value outside [1, padded length] raises ``ValueError``.  ``sym=True`` requires ``Y is X`` and equal lengths; every pair is computed and the matrix then symmetrised
-        (K + K^T) / 2.  Forward only.  A sweep costs what the PADDED shape costs: sort or bucket by length first where lengths vary a
-        lot.  ``max_batch`` is accepted and ignored, as elsewhere."""
+        (K + K^T) / 2.  A forward sweep costs what the PADDED shape costs: sort or bucket by length first where lengths vary a
+        lot.  ``max_batch`` is accepted and ignored, as elsewhere.
+
+        Gradients: forward only on a default object (paths that require grad raise ``NotImplementedError`` outside
+        ``torch.no_grad()``).  Under ``SigKernel(..., exact_gradient=True)`` X and Y both receive the true gradient of the returned
+        values -- the same values, bit for bit, as the no-grad call: the backward sweeps every pair over its OWN sub-grid (its cost
+        follows the true lengths, not the padded ones) and runs the chain rule on the padded paths.  The padding may hold any finite
+        values and receives a gradient of exactly zero, as does a one-point path; where ``X is Y`` autograd adds the two
+        contributions; fp32 paths get fp32 gradients of an fp64 backward."""
         if sym:
             if Y is not X:
                 raise ValueError("sym=True needs Y is X")
@@ -1374,12 +1428,15 @@ class SigKernel:
 
     def compute_kernel_ragged(self, X, Y, len_x, len_y, max_batch=100):
         """The paired form of ``compute_Gram_ragged``: X (batch, Lx, dim), Y (batch, Ly, dim), len_x / len_y (batch,) -> (batch,):
-        out[i] = k(X^i[:len_x[i]], Y^i[:len_y[i]])."""
+        out[i] = k(X^i[:len_x[i]], Y^i[:len_y[i]]).  Gradients as there: under ``exact_gradient=True`` for both arguments, the padding
+        (any finite values) receiving exactly zero; forward only on a default object."""
         return self._ragged(X, Y, len_x, len_y, False, "compute_kernel_ragged")
 
     def compute_mmd_ragged(self, X, len_x, Y, len_y, max_batch=100):
         """``compute_mmd``'s unbiased MMD^2 estimator on two samples of paths of unequal length (padded as for
-        ``compute_Gram_ragged``): three ragged Gram matrices, K_XX and K_YY without their diagonals.  Forward only."""
+        ``compute_Gram_ragged``): three ragged Gram matrices, K_XX and K_YY without their diagonals.  Forward only on a default object;
+        under ``exact_gradient=True`` a composition of three ``compute_Gram_ragged`` calls with their true gradients, for X and Y (the
+        padding -- any finite values -- receives exactly zero)."""
         if X.dim() >= 2 and Y.dim() >= 2:      # (a feature map keeps batch and length: axes 0 and 1)
             len_x = _Lengths("len_x", len_x, X.shape[0], X.shape[1], X.device)
             len_y = _Lengths("len_y", len_y, Y.shape[0], Y.shape[1], Y.device)
