@@ -1100,6 +1100,8 @@ class HipBackend:
         g[:, :-1] -= T         # d inc[p,q] / d x[p]   = -s^2 dy[q]
         if float(param) != 1.0:
             g = g * (float(param) ** 2)
+        if rws is None:
+            g = self._deliver_nan_weights(g, scale)
         return g.to(X.dtype), _WorstResidual(err)
 
     def rbf_adjoint_fused_mb(self, X, Y, sigma, dyadic, edges, scale, gram=True, kfinal=None, naive=False):
@@ -1157,6 +1159,8 @@ class HipBackend:
         # (one small product per y_b, then the sum over b: the flat (A x BN) (BN x D) product runs at 75 GFLOP/s in rocBLAS)
         accd[:, 0] += torch.bmm(n0v.transpose(0, 1), Yd).sum(0) if gram else torch.einsum("ac,acd->ad", n0v[:, 0], Yd)
         g = (-2.0 / float(sigma)) * (X.double() * cs - accd)               # sum_c V G (-2/sigma) (x_r - y_c)
+        if rws is None:
+            g = self._deliver_nan_weights(g, scale)
         return g.to(X.dtype), _WorstResidual(err)
 
     def linear_adjoint_fused(self, X, Y, param, dyadic, edges, scale, gram=True, kfinal=None, naive=False, staged=None, gscale=None, yside=False):
@@ -1224,6 +1228,8 @@ class HipBackend:
             g = torch.empty(A, M, D, dtype=torch.float64, device=dev)
             _check(lib.sk_linear_adjoint_finish_f64(_ptr(tpart), A, chunks, rows.value, M, D, float(param) ** 2, _ptr(gscale), _ptr(g), _stream(X)),
                    "sk_linear_adjoint_finish")
+            if rws is None:
+                g = self._deliver_nan_weights(g, scale)
         res = _WorstResidual(err)
         self.last_fused_err = err
         if g.dtype != X.dtype:
@@ -1294,6 +1300,8 @@ class HipBackend:
             g = torch.empty(A, M, D, dtype=torch.float64, device=dev)
             _check(lib.sk_rbf_adjoint_finish_f64(_ptr(gpart), A, chunks, rows.value, outw.value, _ptr(X64), M, D, float(sigma), _ptr(gscale), _ptr(g),
                                                  _stream(X)), "sk_rbf_adjoint_finish")
+            if rws is None:
+                g = self._deliver_nan_weights(g, scale)
         res = _WorstResidual(err)
         self.last_fused_err = err
         if g.dtype != X.dtype:
@@ -1320,6 +1328,17 @@ class HipBackend:
             return g.to(Y.dtype)
         g = (-2.0 / float(sigma)) * (Y[b0:].double() * folded[..., 0:1] - folded[..., 2:2 + D])
         return g.to(Y.dtype)
+
+    @staticmethod
+    def _deliver_nan_weights(g, scale):
+        """A fused adjoint launched WITHOUT its device-side rescue (no forward values, or a grid the stored-grid kernel cannot hold): to
+        the sweep a NaN weight means "a pair the screen took out", so a NaN of the caller's upstream gradient would contribute zero.
+        The rows of such pairs become NaN here, as plain arithmetic on grad_output gives -- a select on the device, nothing read back;
+        finite weights leave every bit of g as it is.  (With the rescue armed k_screen marks such pairs and the rescue adds s * exact.)"""
+        if scale is None:
+            return g
+        hit = torch.isnan(scale.view(g.shape[0], -1)).any(1)
+        return torch.where(hit[:, None, None], torch.full((), float("nan"), dtype=g.dtype, device=g.device), g)
 
     FUSED_SCREEN = 1e3        # |K[MM][NN]| above which a pair leaves the fused adjoint's sweep for the stored-grid rescue
     FUSED_RESCUE_BLOCKS = 64  # flagged chunks re-solved concurrently

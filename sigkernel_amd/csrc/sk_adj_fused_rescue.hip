@@ -7,7 +7,8 @@
 // those of the other pairs of its lane group.  So:
 //   * k_screen marks, BEFORE the sweep, every pair whose forward value |K[MM][NN]| exceeds `screen` (the caller has the
 //     forward values; the backward recurrence is safe below ~1e3): its upstream gradient becomes NaN -- the fused kernels skip
-//     such a pair entirely -- and its residual entry -1;
+//     such a pair entirely -- and its residual entry -1; a pair whose upstream gradient is the caller's NaN is marked the same way,
+//     so that the rescue's s * exact delivers the NaN the sweep would drop;
 //   * after the sweep k_fused_rescue walks the lane groups' chunks (the same ChunkSplit the sweep used).  A chunk with marked
 //     pairs only gets their EXACT contributions added to its partial sums (stored-grid adjoint of sk_pair_sweep.h +
 //     static-kernel chain rule, one wavefront per chunk, pairs in ascending order: reproducible); a chunk in which a pair that
@@ -26,8 +27,12 @@ __global__ void k_screen(const double *__restrict__ kfinal, const double *__rest
                          double *__restrict__ scale_eff, double *__restrict__ err) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
-    const bool wild = fabs(kfinal[p]) > screen;      // (a NaN value -- poisoned inputs -- is left to the sweep: NaN either way)
-    scale_eff[p] = wild ? __longlong_as_double(0x7ff8000000000000LL) : (scale ? scale[p] : 1.0);
+    const double sp = scale ? scale[p] : 1.0;
+    // (a NaN value -- poisoned inputs -- is left to the sweep: NaN either way.)  A NaN upstream gradient of the CALLER's is marked like a
+    // wild pair: to the sweep a NaN weight means "taken out", so the pair would contribute zero; the rescue adds s * exact = NaN, which
+    // is what plain arithmetic on grad_output gives
+    const bool wild = fabs(kfinal[p]) > screen || sp != sp;
+    scale_eff[p] = wild ? __longlong_as_double(0x7ff8000000000000LL) : sp;
     err[p] = wild ? -1.0 : 0.0;
 }
 
