@@ -271,7 +271,11 @@ __device__ __forceinline__ void trunc_adjoint(const TruncParams &prm, double *yl
 //             left over: the error of D is then 2^-53 |X| / |dX| relative to D (dX is itself a subtraction) -- what subtracting leaves
 //             for |X| = O(1), far less where |X| << 1, the wide bandwidth, and nothing is lost where kap << 1;
 //   g(i, c) = D(i, c) - D(i - 1, c), zero in row 0, in column 0, in padding rows and off the columns.  A zero row and a zero column in
-//             front add nothing to any exclusive prefix, so the recursion below is the one of the steps.
+//             front add nothing to any exclusive prefix, so the recursion below is the one of the steps.  D is rounded once before it is
+//             used (no contraction of its product into this subtraction): two equal rows -- a repeated point, a constant path -- then
+//             have equal D, bit for bit, and g is exactly 0 as it is for a zero step of the plain kernel.
+//   An infinite coordinate makes d2 infinite, not NaN; d2 - d2 is added to X so that it becomes NaN as a NaN coordinate does (kap = 0 for a
+//             point at infinity would give finite levels for an inf in y and NaN ones for the same inf in x).
 // A lane carries kap and X of column c - 1 for each of its two rows and D of its second row: five doubles.  The row above a lane's first
 // row is the lane above, one column ahead: its carried D, read by DPP at the top of the step before it is overwritten, is D(i - 1, c).
 __device__ __forceinline__ void trunc_points(const TruncParams &prm, double *ylds) {
@@ -359,9 +363,13 @@ __device__ __forceinline__ void trunc_points(const TruncParams &prm, double *yld
                         d2 = fma(e, e, d2);
                     }
                 }
-                const double xn = d2 * nparam, kn = exp_nonpos(xn);
+                const double xn = d2 * nparam + (d2 - d2), kn = exp_nonpos(xn);     // (an infinite d2 -- an inf coordinate -- is NaN, not kap = 0)
                 const double dx = xn - xc[r];
-                const double d = (dx <= 0.0 ? kc[r] : -kn) * expm1_nonpos(-__builtin_fabs(dx));
+                double d;
+                {       // rounded ONCE: contracted into g below, the product would stay exact there and rounded in dup, and equal rows give g != 0
+#pragma clang fp contract(off)
+                    d = (dx <= 0.0 ? kc[r] : -kn) * expm1_nonpos(-__builtin_fabs(dx));
+                }
                 double g = d - dup;
                 g = (act && j > 0 && node[r]) ? g : 0.0;
                 kc[r] = kn;
@@ -518,9 +526,13 @@ __device__ __forceinline__ void trunc_points_adjoint(const TruncParams &prm, dou
                             const double e = xr[r][k] - yv[k];
                             d2 = fma(e, e, d2);
                         }
-                        const double xn = d2 * nparam, kn = exp_nonpos(xn);
+                        const double xn = d2 * nparam + (d2 - d2), kn = exp_nonpos(xn);     // (as trunc_points: inf is NaN)
                         const double dx = xn - xc[r];
-                        const double d = (dx <= 0.0 ? kc[r] : -kn) * expm1_nonpos(-__builtin_fabs(dx));
+                        double d;
+                        {       // (as trunc_points: rounded once)
+#pragma clang fp contract(off)
+                            d = (dx <= 0.0 ? kc[r] : -kn) * expm1_nonpos(-__builtin_fabs(dx));
+                        }
                         double g = d - dup;
                         g = (act && j > 0 && node[r]) ? g : 0.0;
                         kc[r] = kn;

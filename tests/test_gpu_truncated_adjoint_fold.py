@@ -4,7 +4,9 @@ GPU from the parent commit by tests/golden/make_golden_truncated_adjoint_fold.py
 ran every case twice).  Every value and every gradient must be equal (np.array_equal) and every call must launch each instance of
 k_trunc_sig as often as it did.  The shapes are the smallest that reach each branch: both sides requiring grad, sym, the paired runs of
 three pairs, fp32, the paired widening at 16 coordinates, two row bands with two column tiles, the long gradient on (Y, X) alone, a lowered block
-count, and without a keyword the restatement."""
+count, and without a keyword the restatement.  The three points cases were re-recorded after trunc_points / trunc_points_adjoint began to
+round the first difference D once before using it (equal rows then give g = 0 exactly: CHANGELOG, "Truncated-kernel value regimes"),
+which moved their values by <= 3.1e-16 relative; every other entry of the file came out bit-identical in that recording."""
 import ctypes
 import os
 
