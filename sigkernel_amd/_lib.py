@@ -1394,7 +1394,14 @@ class HipBackend:
                     # wider or longer paths: T[a] = sum_b scale[a, b] W[a, b] (Mc x Nc) @ dY[b] (Nc x D) IS a batched matrix product --
                     # a plain library GEMM (rocBLAS under torch.matmul)
                     # (256 x 256 pairs of 100 points: dim 12 / 20 / 32 7.2 / 24.4 / 42.9 -> 2.3 / 2.5 / 4.9 ms, equal to 1e-15)
-                    T = _pair_gemm_sum(W[..., :N - 1], Y[:, 1:] - Y[:, :-1], scale, gram)
+                    if X.dtype != torch.float64:
+                        # fp32 paths: the product accumulates in fp64 -- sums over B N signed terms in fp32 leave sqrt(B N) fp32
+                        # roundings in the gradient (2.3e-7 of it on 5 x 64 steps: the whole budget of two fp32 ulps)
+                        Yd = Y.double()
+                        T = _pair_gemm_sum(W[..., :N - 1].double(), Yd[:, 1:] - Yd[:, :-1], None if scale is None else scale.double(),
+                                           gram).to(X.dtype)
+                    else:
+                        T = _pair_gemm_sum(W[..., :N - 1], Y[:, 1:] - Y[:, :-1], scale, gram)
                 g = torch.zeros(A, M, D, dtype=X.dtype, device=X.device)
                 g[:, 1:] += T          # d inc[p,q] / d x[p+1] = +s^2 dy[q]
                 g[:, :-1] -= T         # d inc[p,q] / d x[p]   = -s^2 dy[q]
@@ -1403,6 +1410,12 @@ class HipBackend:
                 # wide paths: the kernel writes H = go_ab dL/dG (.) G per node (k_static_wide_mfma, first pass); with
                 # dG/dx_m = -(2 / sigma) G (x_m - y_n):  dL/dx_a[m] = -(2 / sigma) (rowsum_bn(H) x_m - sum_b H[a, b] @ y_b) -- the
                 # second term is the batched GEMM of the linear branch above
+                if X.dtype != torch.float64:
+                    # fp32 paths: both passes in fp64.  sum_n H[m][n] (y_n - x_m) telescopes -- H carries the alternating four-corner
+                    # pattern of W against the smooth G (y - x) -- so an fp32 H loses |G (y - x)| / |its step| digits before the GEMM
+                    # sees it (1.4e-6 of the gradient on 65 x 64 points at 34 dims, against 2.4e-7 for two fp32 ulps; 6e-8 this way)
+                    g = self.static_adjoint(kind, param, X.double(), Y.double(), W.double(), None if scale is None else scale.double(), gram)
+                    return g.to(X.dtype)
                 H = torch.empty((A, B, M, _padded_ld(N, X.element_size())) if gram else (A, M, _padded_ld(N, X.element_size())),
                                 dtype=X.dtype, device=X.device)
                 _check(fn(1, float(param), _ptr(X), _ptr(Y), _ptr(W), ldw, _ptr(scale), A, B if gram else 0, M, N, D, _ptr(H),

@@ -1233,7 +1233,8 @@ __global__ __launch_bounds__(WD_TPB) void k_static_wide_mfma(const T *__restrict
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = r0 + 16 * w + lk + 4 * r;
-                    if (row < Mc && col < ld) o[(int64_t)row * ld + col] = (T)acc[j][nt][r];
+                    // (the padding columns' accumulators are <dx_p, 0>: NaN for a NaN or inf coordinate of x, so they are written as 0)
+                    if (row < Mc && col < ld) o[(int64_t)row * ld + col] = col < Nc ? (T)acc[j][nt][r] : (T)0;
                 }
             }
         }

@@ -10,6 +10,10 @@ summation order).  Outside `offset` the second term is below 1e-11.  Rows marked
 fp32 inputs: two fp32 ulps on top.  LinearKernel at s = 10 (|K| up to 1e18) is held to the ledger's RESCUE_GRAD_TOL and must show the
 rescue kernels on its trace.
 
+Beside the routes of value_regimes.ROUTES the table holds the rows above 32 dims (WIDE_ROUTES: k_static_wide_mfma through the API, D = 33
+beside D = 32) and two operations on three shapes each (OPERATION_ROUTES): `paired_grad`, compute_kernel weighted by a random vector, and
+`gram_grad_y`, the gradient with respect to the second argument of compute_Gram (exact_gradient=True, the mode that returns one).
+
 test_gpu_exp_probe measures the hand-written exponential itself (csrc/sk_internal.h: exp_nonpos) through single isolated nodes.
 
 With SK_VALUE_REGIMES_REPORT=<file> every case appends its measured error and bound to that file (profiles/value_regimes.txt)."""
@@ -29,7 +33,8 @@ pytestmark = pytest.mark.gpu
 with open(os.path.join(GOLDEN, "value_regimes.json")) as _f:
     RECORDED = json.load(_f)
 CASES = V.route_cases()
-WANT = {"gram_grad": "gram", "exact_grad": "exact", "sym": "sym", "sym_grad": "sym", "prefix": "prefix", "mmd_grad": "mmd", "kgrad": "gram"}
+WANT = {"gram_grad": "gram", "exact_grad": "exact", "sym": "sym", "sym_grad": "sym", "prefix": "prefix", "mmd_grad": "mmd", "kgrad": "gram",
+        "paired_grad": "paired", "gram_grad_y": "gram_y"}
 
 
 def _report(line):
@@ -56,7 +61,7 @@ def _call(row, sh, kind, X, Y, w, sigma):
     Xd, Yd, wd = (torch.from_numpy(a).to(dt).cuda() for a in (X, Y, w))
     kern = sigkernel_amd.LinearKernel() if kind == "linear" else sigkernel_amd.RBFKernel(sigma)
     op = row["op"]
-    sk = sigkernel_amd.SigKernel(kern, sh["d"], exact_gradient=op == "exact_grad")
+    sk = sigkernel_amd.SigKernel(kern, sh["d"], exact_gradient=op in ("exact_grad", "gram_grad_y"))
     if op == "sym":
         return {"value": sk.compute_Gram(Xd, Xd, sym=True)}
     if op == "prefix":
@@ -64,7 +69,16 @@ def _call(row, sh, kind, X, Y, w, sigma):
     if op == "kgrad":
         gamma = torch.randn(X.shape, generator=torch.Generator().manual_seed(1), dtype=torch.float64).to(dt).cuda()
         return {"k": sk.compute_kernel_and_derivatives_Gram(Xd, Yd, gamma)[0]}
+    if op == "gram_grad_y":
+        Yg = Yd.clone().requires_grad_(True)
+        v = sk.compute_Gram(Xd, Yg)
+        (v * wd).sum().backward()
+        return {"value": v.detach(), "grad": Yg.grad}
     Xg = Xd.clone().requires_grad_(True)
+    if op == "paired_grad":
+        v = sk.compute_kernel(Xg, Yd)
+        (v * wd.diagonal()).sum().backward()
+        return {"value": v.detach(), "grad": Xg.grad}
     if op == "mmd_grad":
         v = sk.compute_mmd(Xg, Yd)
         v.backward()

@@ -302,6 +302,48 @@ ROUTES = [
     _row("derivative Gram (static nodes with the library exp)", "kgrad", [shape(2, 2, 12, 10, 3, 1)], kinds=("rbf",), families=("drift",),
          claims=("k_static_nodesIdLi4ELi1ELi3E", "k_deriv_wave"), outputs=("k",)),
 ]
+# Paths of more than 32 dims (HipBackend.MAX_FUSED_DIM): static kernel, increments and the first pass of the RBF chain rule are
+# k_static_wide_mfma (tests/wide_value_regimes.py holds it to the yardstick launch by launch; these rows do it through the API).
+# LinearKernel: WIDE_LINEAR stages the row-differenced paths (sk_static.hip:1165, s^2 (p1[k] - p0[k])) and the chain rule is a library
+# GEMM of W with dY (_lib.py:1397): a common offset never reaches a product.  RBFKernel forms |x|^2 + |y|^2 - 2 <x, y> from the points
+# (sk_static.hip:1260) and the second pass subtracts rowsum(H) x from H @ y (_lib.py:1414): the reference's own arithmetic, with its
+# allowance.  The D = 32 row next to D = 33 runs the same settings through k_static_nodes (the same form of the exponent).
+# (These rows, and OPERATION_ROUTES below, are kept apart from ROUTES because tests/upstream_gradients.py takes every gradient row of
+# ROUTES through its own families; route_cases() walks all three lists.)
+WHY_LIN_WIDE = "sk_static.hip:1165 (WIDE_LINEAR stages differences), _lib.py:1397 (GEMM of W with dY)"
+WIDE = ("k_static_wide_mfma",)
+WIDE_ROUTES = [
+    _row("wide static D=40, tile edges", "gram_grad", [shape(2, 5, 66, 65, 40, 1)], invariant=("linear",), why=WHY_LIN_WIDE,
+         claims=WIDE + ("k_fwd_wave", "k_adj_wave")),
+    _row("wide static D=33 d=0", "gram_grad", [shape(2, 2, 20, 17, 33, 0)], invariant=("linear",), why=WHY_LIN_WIDE,
+         claims=WIDE + ("k_fwd_wave", "k_adj_wave")),
+    _row("static tiles D=32 d=0 (beside D=33)", "gram_grad", [shape(2, 2, 20, 17, 32, 0)], invariant=("linear",), why=WHY_LIN_STATIC,
+         claims=("k_fwd_wave", "k_adj_wave", "k_static_{static}", "k_static_{kind}_adj_tiled")),
+    _row("wide static D=40 symmetric with gradient", "sym_grad", [shape(4, 4, 20, 20, 40, 1, sym=True)], invariant=("linear",),
+         why=WHY_LIN_WIDE, claims=WIDE + ("k_fwd_wave", "k_adj_wave")),
+    _row("wide static D=40 exact_gradient=True", "exact_grad", [shape(3, 3, 20, 17, 40, 1)], invariant=("linear",), why=WHY_LIN_WIDE,
+         claims=WIDE + ("k_fwd_wave", "k_adj_simple")),
+    _row("wide static D=40 loss", "mmd_grad", [shape(4, 4, 20, 20, 40, 1)], invariant=("linear",), why=WHY_LIN_WIDE,
+         claims=WIDE + ("k_fwd_wave", "k_adj_wave")),
+]
+# compute_kernel (paired batches) with its gradient, and the gradient with respect to the SECOND argument of compute_Gram
+PAIRED40 = shape(3, 3, 20, 17, 40, 1)
+OPERATION_ROUTES = [
+    _row("paired F1/A1", "paired_grad", [BASE], claims=A1, invariant=KINDS, why=WHY_F1),
+    _row("paired S1/S2 static stage D=12", "paired_grad", [shape(3, 3, 20, 17, 12, 1)], invariant=("linear",), why=WHY_LIN_STATIC,
+         claims=("k_fwd_wave", "k_adj_wave", "k_static_{static}", "k_static_{kind}_adj")),
+    _row("paired wide static D=40", "paired_grad", [PAIRED40], invariant=("linear",), why=WHY_LIN_WIDE, claims=WIDE + ("k_fwd_wave", "k_adj_wave")),
+    # (exact_gradient=True: the only mode with a gradient for Y.  Up to 8 dims LinearKernel's is sk_static_adjoint2 on pre-differenced x
+    # (_lib.py:1438); beyond, and for RBFKernel beyond 32, sk_static_adjoint on the swapped pairs with W transposed)
+    _row("second argument exact_gradient=True", "gram_grad_y", [BASE], invariant=("linear",), why="_lib.py:1438 (pre-differenced x); " + WHY_LIN_STATIC,
+         claims=("k_fwd_fusedI", "k_adj_simple", "k_static_{static}", "k_{kind}_adj2")),
+    _row("second argument static stage D=12", "gram_grad_y", [shape(3, 3, 20, 17, 12, 1)], invariant=("linear",), why=WHY_LIN_STATIC,
+         claims={"linear": ("k_fwd_wave", "k_adj_simple", "k_static_linear", "k_static_linear_adj_tiled"),
+                 "rbf": ("k_fwd_wave", "k_adj_simple", "k_static_nodes", "k_rbf_adj2")}),
+    _row("second argument wide static D=40", "gram_grad_y", [PAIRED40], invariant=("linear",), why=WHY_LIN_WIDE,
+         claims=WIDE + ("k_fwd_wave", "k_adj_simple")),
+]
+ALL_ROUTES = ROUTES + WIDE_ROUTES + OPERATION_ROUTES
 RESCUE_CLAIMS = ("k_screen", "k_fused_rescue")
 
 
@@ -314,7 +356,7 @@ def claims_of(row, kind, settings=None):
 def route_cases():
     """[(row, shape, kind, family, parameter label, settings)] -- every cell of the GPU test"""
     out = []
-    for row in ROUTES:
+    for row in ALL_ROUTES:
         for sh in row["shapes"]:
             for kind in row["kinds"]:
                 for fam, lab, st in family_cases(kind, row["families"]):
@@ -344,7 +386,7 @@ def _cached_inputs(fam, lab, kind, key, seed):
     return inputs(st, _SHAPES[key], seed)
 
 
-_SHAPES = {shape_key(sh): sh for row in ROUTES for sh in row["shapes"]}
+_SHAPES = {shape_key(sh): sh for row in ALL_ROUTES for sh in row["shapes"]}
 
 
 def case_inputs(fam, lab, kind, sh, seed=0):
@@ -365,6 +407,12 @@ def _cached_want(fam, lab, kind, key, what):
         return K, (2 * g1, g1 + g2)      # the reference's 2x rule (all pairs) or both arguments (the triangle)
     if what == "prefix":
         return prefix_ld(kind, sigma, X, Y, d), None
+    if what == "paired":      # compute_kernel: the diagonal pairs, weighted by the diagonal of w
+        K, g = gram_ld(kind, sigma, X, Y, d, np.diag(np.diag(w)))
+        return np.diagonal(K).copy(), g
+    if what == "gram_y":      # d sum(w K(X, Y)) / dY: the first-argument gradient of K(Y, X) under the transposed weights; the API returns a
+        K, g = gram_ld(kind, sigma, Y, X, d, w.T.copy(), exact=True)      # gradient for Y under exact_gradient=True alone
+        return K.T.copy(), g
     assert what == "mmd", what
     return mmd_ld(kind, sigma, X, Y, d)
 
