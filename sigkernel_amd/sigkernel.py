@@ -868,7 +868,9 @@ class _SigKernelRaggedExact(torch.autograd.Function):
     """compute_kernel_ragged / compute_Gram_ragged under SigKernel(exact_gradient=True): forward is _prefix_at -- the values of the
     no-grad call, bit for bit -- and backward the true gradient of those values for both arguments: the exact adjoint of the discrete
     solver run on every pair's own sub-grid (sk_solve_adj_* with SK_FLAG_DISCRETE | SK_FLAG_RAGGED), then _exact_gradient's chain rule
-    on the padded paths.  The padding receives exactly zero, whatever finite values it holds."""
+    on the paths with every padded point overwritten by its path's last true point (_repeat_last_point).  The padding receives exactly
+    zero whatever it holds -- huge values, NaN and inf included -- and never reaches a true point's gradient
+    (tests/test_gpu_prefix_value_regimes.py)."""
 
     @staticmethod
     def forward(ctx, X, Y, lx, ly, static_kernel, dyadic_order, gram, _naive_solver, workspace_bytes):
@@ -885,10 +887,23 @@ class _SigKernelRaggedExact(torch.autograd.Function):
         if X.shape[1] < 2 or Y.shape[1] < 2 or X.shape[0] == 0 or Y.shape[0] == 0:   # single points / empty batches: k = 1 whatever the paths
             gx, gy = (torch.zeros_like(X) if need_x else None), (torch.zeros_like(Y) if need_y else None)
         else:
-            gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, X.detach().contiguous(), Y.detach().contiguous(),
+            # W is exactly zero outside a pair's sub-grid, but the static stage still evaluates |x|^2 + |y|^2 - 2 <x, y> and x - y on the
+            # padding: 0 * (inf - inf) for a padding whose squares or differences overflow, or that is not finite.  So the chain rule
+            # runs on the paths padded with their last TRUE point: every true-point sum gains +-0 from the padding, the padding's own
+            # gradient is 0 * finite, and a batch of full lengths is handed on as it is.
+            gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, _repeat_last_point(X.detach(), lx).contiguous(),
+                                     _repeat_last_point(Y.detach(), ly).contiguous(),
                                      grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y,
                                      (lx - 1, ly - 1))
         return gx, gy, None, None, None, None, None, None, None
+
+
+def _repeat_last_point(P, lens):
+    """P (batch, length, dim) with every point from lens[i] on overwritten by point lens[i] - 1 of its path (lens: int32 on P's device)"""
+    idx = lens.long()
+    last = P[torch.arange(P.shape[0], device=P.device), idx - 1]
+    pad = torch.arange(P.shape[1], device=P.device)[None, :] >= idx[:, None]
+    return torch.where(pad[:, :, None], last[:, None, :], P)
 
 
 def k_kgrad(X, Y, gamma, dyadic_order, static_kernel, eps=1e-4, workspace_bytes=None):
@@ -1233,7 +1248,7 @@ def _lengths(name, lens, count, padded, device, with_host=False):
 def pad_paths(paths):
     """A list of (len_i, dim) tensors -> (X (batch, max len, dim), lens (batch,) int64): every path padded at its END by repeating its
     last point, for ``SigKernel.compute_Gram_ragged`` / ``compute_kernel_ragged`` / ``compute_mmd_ragged`` (whose values never depend
-    on the padding, and whose gradients under ``exact_gradient=True`` are exactly zero on it: any finite values would do).  ``X[i, :lens[i]]`` is path i again."""
+    on the padding, and whose gradients under ``exact_gradient=True`` are exactly zero on it: any values would do, NaN and inf included).  ``X[i, :lens[i]]`` is path i again."""
     paths = list(paths)
     if not paths:
         raise ValueError("pad_paths needs at least one path")
@@ -1280,8 +1295,8 @@ class SigKernel:
     ``compute_Gram`` / ``compute_kernel`` and accept a Y that requires grad.  The backward solves every pair with the stored-grid
     kernel (a few times the cost of the default's fused adjoints) and runs in fp64: fp32 paths are up-cast for it and their gradients
     rounded to fp32 at the end.  Ragged batches (``compute_Gram_ragged`` / ``compute_kernel_ragged`` / ``compute_mmd_ragged``) get
-    their gradients in this mode and in this mode only: every pair's backward sweeps its own sub-grid, and the padding -- any finite
-    values -- receives exactly zero.  Not sharded (``process_group`` raises ``NotImplementedError``); prefix calls stay forward only;
+    their gradients in this mode and in this mode only: every pair's backward sweeps its own sub-grid, and the padding -- any
+    values, NaN and inf included -- receives exactly zero.  Not sharded (``process_group`` raises ``NotImplementedError``); prefix calls stay forward only;
     ``RBFKernel.sigma`` receives no gradient.
     """
 
@@ -1399,12 +1414,13 @@ class SigKernel:
 
     def compute_Gram_ragged(self, X, Y, len_x, len_y, sym=False, max_batch=100):
         """Gram matrix of two batches of paths of UNEQUAL length: X (batch_X, Lx, dim), Y (batch_Y, Ly, dim) hold the paths padded at
-        their ends to common lengths (``pad_paths``; any finite padding), len_x (batch_X,) / len_y (batch_Y,) their point counts ->
+        their ends to common lengths (``pad_paths``; any padding), len_x (batch_X,) / len_y (batch_Y,) their point counts ->
         (batch_X, batch_Y): out[a, b] = k(X^a[:len_x[a]], Y^b[:len_y[b]]) -- node (len_x[a] - 1, len_y[b] - 1) of
         ``compute_Gram_prefixes``'s grid, bit for bit: one sweep of the padded pairs by the fused prefix kernel that stores that one node
         per pair (dim <= 8, one band per pair; else gathered from row tiles of the streaming solver's grid within ``workspace_bytes``):
         the (batch_X, batch_Y, Lx, Ly) tensor is never built.  A path of one point gives exactly 1.  The values past a path's length
-        never reach its result.  The lengths are integer tensors (any device) or sequences of ints, checked once on the host: a wrong
+        never reach its result, whatever they are -- huge, NaN or inf (a function-valued static kernel maps them through its feature
+        map first: keep them finite there).  The lengths are integer tensors (any device) or sequences of ints, checked once on the host: a wrong
         count, a non-integer dtype or a value outside [1, padded length] raises ``ValueError``.  ``sym=True`` requires ``Y is X`` and equal lengths; every pair is computed and the matrix then symmetrised
         (K + K^T) / 2.  A forward sweep costs what the PADDED shape costs: sort or bucket by length first where lengths vary a
         lot.  ``max_batch`` is accepted and ignored, as elsewhere.
@@ -1412,8 +1428,8 @@ class SigKernel:
         Gradients: forward only on a default object (paths that require grad raise ``NotImplementedError`` outside
         ``torch.no_grad()``).  Under ``SigKernel(..., exact_gradient=True)`` X and Y both receive the true gradient of the returned
         values -- the same values, bit for bit, as the no-grad call: the backward sweeps every pair over its OWN sub-grid (its cost
-        follows the true lengths, not the padded ones) and runs the chain rule on the padded paths.  The padding may hold any finite
-        values and receives a gradient of exactly zero, as does a one-point path; where ``X is Y`` autograd adds the two
+        follows the true lengths, not the padded ones) and runs the chain rule on the padded paths.  The padding may hold any
+        values (NaN and inf included: the backward overwrites it with each path's last true point) and receives a gradient of exactly zero, as does a one-point path; where ``X is Y`` autograd adds the two
         contributions; fp32 paths get fp32 gradients of an fp64 backward."""
         if sym:
             if Y is not X:
@@ -1429,14 +1445,14 @@ class SigKernel:
     def compute_kernel_ragged(self, X, Y, len_x, len_y, max_batch=100):
         """The paired form of ``compute_Gram_ragged``: X (batch, Lx, dim), Y (batch, Ly, dim), len_x / len_y (batch,) -> (batch,):
         out[i] = k(X^i[:len_x[i]], Y^i[:len_y[i]]).  Gradients as there: under ``exact_gradient=True`` for both arguments, the padding
-        (any finite values) receiving exactly zero; forward only on a default object."""
+        (any values) receiving exactly zero; forward only on a default object."""
         return self._ragged(X, Y, len_x, len_y, False, "compute_kernel_ragged")
 
     def compute_mmd_ragged(self, X, len_x, Y, len_y, max_batch=100):
         """``compute_mmd``'s unbiased MMD^2 estimator on two samples of paths of unequal length (padded as for
         ``compute_Gram_ragged``): three ragged Gram matrices, K_XX and K_YY without their diagonals.  Forward only on a default object;
         under ``exact_gradient=True`` a composition of three ``compute_Gram_ragged`` calls with their true gradients, for X and Y (the
-        padding -- any finite values -- receives exactly zero)."""
+        padding -- any values -- receives exactly zero)."""
         if X.dim() >= 2 and Y.dim() >= 2:      # (a feature map keeps batch and length: axes 0 and 1)
             len_x = _Lengths("len_x", len_x, X.shape[0], X.shape[1], X.device)
             len_y = _Lengths("len_y", len_y, Y.shape[0], Y.shape[1], Y.device)
