@@ -62,6 +62,8 @@ typedef enum sk_status {
                              * increment -- the adjoint of the DISCRETE solver, not the reference's formula (see sk_solve_adj_*) */
 #define SK_FLAG_RAGGED 32 /* sk_solve_adj_* only, and only together with SK_FLAG_DISCRETE: every pair is differentiated on its own
                            * sub-grid, read from a table at the head of `workspace` (see sk_solve_adj_*) */
+#define SK_FLAG_SOURCES 64 /* sk_solve_adj_* only, and only together with SK_FLAG_DISCRETE (never with SK_FLAG_RAGGED): W is in/out -- on
+                            * entry the weight S of every coarse node in L = sum S K, on exit dL / d inc_c (see sk_solve_adj_*) */
 
 /* 340.  The number moves whenever an exported signature changes incompatibly: 310 -> 320 gave sk_solve_fwd_{linear,rbf}_sym_* their
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
@@ -753,6 +755,17 @@ int sk_solve_fwd_linear_edges_f64(const double *dXr, const double *dYt, int64_t 
  *             Mc x Nc block; mc == 0 or nc == 0: out_final[p] = 1, W[p] = 0, nothing swept.  Columns b >= Nc of W (ldw padding) are
  *             not written.  SK_FLAG_RAGGED without SK_FLAG_DISCRETE, or with SK_FLAG_FAST_ONLY: SK_ERR_BAD_ARG; a workspace that
  *             holds the head but not one slot: SK_ERR_WORKSPACE.
+ *   SK_FLAG_DISCRETE | SK_FLAG_SOURCES -- the adjoint of a weighted sum of prefix kernels, L_p = sum_{a,b} S_p[a][b] K_p[(a+1) << d][(b+1) << d]
+ *             (the coarse nodes of pair p's grid: the kernels of its truncated paths; row 0 and column 0 of that grid are the constant 1
+ *             and carry no gradient), in ONE reverse sweep per pair.  W is IN/OUT: on entry W[p][a][b] = S_p[a][b], on exit
+ *             W[p][a][b] = dL_p / d inc_c[p][a][b].  The recurrence above with a source per node in place of the 1 at the far corner:
+ *               u[i][j] = src(i, j) + P(g[i][j+1]) u[i][j+1] + P(g[i+1][j]) u[i+1][j] - Q(g[i+1][j+1]) u[i+1][j+1],
+ *               src(i, j) = S[((i+1) >> d) - 1][((j+1) >> d) - 1] where (i+1) and (j+1) are both multiples of 2^d, else 0.
+ *             Every source of a pair is read before the first store to its W block; columns b >= Nc of W (ldw padding) are neither
+ *             read nor written.  A one-hot S at (Mc-1, Nc-1) gives the plain SK_FLAG_DISCRETE result bit for bit; a one-hot S at
+ *             (mc-1, nc-1) what SK_FLAG_RAGGED gives for the entry (mc, nc), zeros included.  out_final[p] = K_p[MM][NN] as without the
+ *             flag, out_err is zero-filled, the workspace is that of SK_FLAG_DISCRETE.  No atomics: bit-reproducible.
+ *             SK_FLAG_SOURCES without SK_FLAG_DISCRETE, with SK_FLAG_RAGGED or with SK_FLAG_FAST_ONLY: SK_ERR_BAD_ARG.
  *   workspace: sk_adj_workspace_bytes(...) bytes of device scratch.
  *   inc_c [P,Mc,ld]; out_final nullable [P]; W [P,Mc,ldw] (ldw = 0: dense); out_err nullable [P] doubles. */
 size_t sk_adj_workspace_bytes(int64_t P, int Mc, int Nc, int dyadic, int flags, int elem_size);
@@ -760,7 +773,8 @@ size_t sk_adj_workspace_bytes(int64_t P, int Mc, int Nc, int dyadic, int flags, 
  *   the shape) -- the stored-grid figure grows with min(P, 1024) whole grids and is only needed for SK_FLAG_SIMPLE /
  *   SK_FLAG_EXACT calls or shapes the fast kernels do not cover; SK_FLAG_DISCRETE: the stored-grid figure (any k >= 1 slots of
  *   sk_adj_rescue_slot_bytes(Mc, Nc, dyadic) bytes serve: the blocks stride over the pairs); SK_FLAG_DISCRETE | SK_FLAG_RAGGED: the
- *   table's head (8 P bytes rounded up to a multiple of 256) plus that figure; SK_FLAG_RAGGED without SK_FLAG_DISCRETE: 0. */
+ *   table's head (8 P bytes rounded up to a multiple of 256) plus that figure; SK_FLAG_RAGGED without SK_FLAG_DISCRETE: 0;
+ *   SK_FLAG_SOURCES changes nothing (SK_FLAG_DISCRETE | SK_FLAG_SOURCES: the figure of SK_FLAG_DISCRETE). */
 
 /* Device-side rescue of the fast adjoint: re-solves with stored grids exactly the pairs whose self-check residual
  * err[p] (as written by sk_solve_adj_*) exceeds `tol`, overwriting their W (and out_final when non-NULL); a NaN residual is

@@ -31,6 +31,7 @@ FLAG_FAST_ONLY = 4
 FLAG_EDGES_GIVEN = 8
 FLAG_DISCRETE = 16
 FLAG_RAGGED = 32
+FLAG_SOURCES = 64
 # the nodes of the prefix grid a call keeps (SK_NODES_* of include/sigkernel_amd.h)
 PREFIX_NODES = {"all": 0, "diagonal": 1, "last_row": 2, "last_col": 3}
 
@@ -1529,7 +1530,7 @@ class HipBackend:
     # residual of the fast adjoint's self-check above which a pair is re-solved by the stored-grid kernel
     ADJ_RESIDUAL_TOL = 1e-8
 
-    def solve_adj(self, inc_c, dyadic, naive=False, flags=0, return_residual=False, edges=None, discrete=False, cells=None):
+    def solve_adj(self, inc_c, dyadic, naive=False, flags=0, return_residual=False, edges=None, discrete=False, cells=None, sources=None):
         """inc_c [..., Mc, Nc] -> (final [...], W [..., Mc, Nc] = d final / d inc_c).
 
         The fast kernel recomputes K backwards instead of storing it and reports a per-pair residual; pairs whose
@@ -1540,11 +1541,19 @@ class HipBackend:
         cells (with discrete only): int32 [..., 2] on the increments' device, one row (mc, nc) per pair -- the coarse cells of the
         pair's own paths, length - 1 on either side (SK_FLAG_RAGGED).  `final` is then K at node (mc << dyadic, nc << dyadic) of the
         padded pair and W its exact derivative: swept over the cells a < mc, b < nc alone, exactly zero on the others; rows are
-        clamped to [0, Mc] x [0, Nc], and a pair with mc == 0 or nc == 0 gives 1 and zeros."""
+        clamped to [0, Mc] x [0, Nc], and a pair with mc == 0 or nc == 0 gives 1 and zeros.
+        sources (with discrete only, never with cells): S [..., Mc, Nc] of the increments' dtype and device, the weight of coarse node
+        (a + 1, b + 1) of every pair in L = sum S[a][b] K[(a+1) << dyadic][(b+1) << dyadic] -- the prefix kernels of the pair
+        (SK_FLAG_SOURCES).  W is then dL / d inc_c, from one reverse sweep per pair with the sources injected at their own cells;
+        `final` stays K[MM][NN].  S is copied into the padded W buffer on the launch stream and is not modified."""
         if cells is not None and not discrete:
             raise ValueError("solve_adj: cells= is a mode of discrete=True")
+        if sources is not None and not discrete:
+            raise ValueError("solve_adj: sources= is a mode of discrete=True")
+        if sources is not None and cells is not None:
+            raise ValueError("solve_adj: sources= and cells= do not combine")
         if discrete:
-            return self._solve_adj_discrete(inc_c, dyadic, naive, return_residual, cells)
+            return self._solve_adj_discrete(inc_c, dyadic, naive, return_residual, cells, sources)
         if edges is not None:
             # edges kept by another kernel in its own layout (sk_solve_fwd_static_* keeps sk_rbf_adjoint_fused_mb_f64's): sweep forward here
             P_ = inc_c.numel() // (inc_c.shape[-2] * inc_c.shape[-1])
@@ -1619,7 +1628,7 @@ class HipBackend:
             return out, W, err
         return out, W
 
-    def _solve_adj_discrete(self, inc_c, dyadic, naive, return_residual, cells=None):
+    def _solve_adj_discrete(self, inc_c, dyadic, naive, return_residual, cells=None, sources=None):
         inc_c, ld = _row_stride(inc_c, "inc_c")
         Mc, Nc = inc_c.shape[-2:]
         batch = inc_c.shape[:-2]
@@ -1633,9 +1642,17 @@ class HipBackend:
                                  % (tuple(batch) + (2,), dev, cells.dtype, tuple(cells.shape), cells.device))
             flags |= FLAG_RAGGED
             head = (8 * P + 255) // 256 * 256       # the table {mc, nc} of every pair, rounded up: the slots follow it
+        if sources is not None:
+            _dev(sources, "sources")
+            if sources.dtype != inc_c.dtype or sources.device != dev or tuple(sources.shape) != tuple(inc_c.shape):
+                raise ValueError("solve_adj: sources must be a %s tensor of shape %s on %s, got %s %s on %s"
+                                 % (inc_c.dtype, tuple(inc_c.shape), dev, sources.dtype, tuple(sources.shape), sources.device))
+            flags |= FLAG_SOURCES
         out = torch.empty(batch, dtype=inc_c.dtype, device=dev)
         ldw = _padded_ld(Nc, inc_c.element_size())
         Wp = torch.empty(batch + (Mc, ldw), dtype=inc_c.dtype, device=dev)
+        if sources is not None:   # W is in/out: the sources go in on the current stream, ahead of the launch (the padding columns are never read)
+            Wp[..., :Nc].copy_(sources)
         err = torch.empty(batch, dtype=torch.float64, device=dev)
         if P:
             with _device(dev):

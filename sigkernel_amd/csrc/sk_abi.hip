@@ -55,12 +55,14 @@ template <typename T>
 int solve_adj(const T *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, T *out_final, T *W,
               int64_t ldw, double *out_err, void *ws, size_t ws_bytes, void *stream) {
     const bool discrete = (flags & SK_FLAG_DISCRETE) != 0, ragged = (flags & SK_FLAG_RAGGED) != 0;
+    const bool sources = (flags & SK_FLAG_SOURCES) != 0;
     if (ragged && !discrete) return SK_ERR_BAD_ARG;   // the sub-grid table is a mode of the discrete adjoint alone
+    if (sources && (!discrete || ragged)) return SK_ERR_BAD_ARG;   // so are the per-node sources, and the two modes do not combine
     if (discrete) {
         // the exact adjoint of the discrete solver: always the stored-grid kernel, so kept edges are of no use (ignored) and
         // SK_FLAG_FAST_ONLY cannot be honoured
         if (flags & SK_FLAG_FAST_ONLY) return SK_ERR_BAD_ARG;
-        flags &= ~(SK_FLAG_DISCRETE | SK_FLAG_RAGGED | SK_FLAG_EDGES_GIVEN);
+        flags &= ~(SK_FLAG_DISCRETE | SK_FLAG_RAGGED | SK_FLAG_SOURCES | SK_FLAG_EDGES_GIVEN);
     }
     if (bad_common(inc_c, P, Mc, Nc, dyadic, scheme, flags) || !W || (ld != 0 && ld < Nc) || (ldw != 0 && ldw < Nc))
         return SK_ERR_BAD_ARG;
@@ -70,7 +72,7 @@ int solve_adj(const T *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic,
     hipStream_t s = (hipStream_t)stream;
     if (discrete) {
         if (out_err && hipMemsetAsync(out_err, 0, sizeof(double) * (size_t)P, s) != hipSuccess) return SK_ERR_LAUNCH;
-        return launch_adj_simple<T>(inc_c, g, out_final, W, ldw, ws, ws_bytes, s, true, ragged);
+        return launch_adj_simple<T>(inc_c, g, out_final, W, ldw, ws, ws_bytes, s, true, ragged, sources);
     }
     const bool fast_shape = dyadic >= 0 && dyadic <= (sizeof(T) == 8 ? 2 : 1);   // launch_adj_wave's scope
     const size_t fast_ws = fast_shape ? adj_fast_workspace_bytes(g, (int)sizeof(T)) : 0;

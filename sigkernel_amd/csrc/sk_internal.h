@@ -90,9 +90,10 @@ template <typename T>
 int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, double *out_edges, hipStream_t s);
 template <typename T>
 int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes, hipStream_t s,
-                      bool discrete = false, bool ragged = false);   // discrete: the exact adjoint of the discrete solver
-// (adj_pair_discrete); ragged (with discrete only): each pair on its own sub-grid, from the {mc, nc} table of adj_ragged_head_bytes(P)
-// bytes that the caller wrote at the head of ws; the slots follow it
+                      bool discrete = false, bool ragged = false, bool sources = false);   // discrete: the exact adjoint of the discrete
+// solver (adj_pair_discrete); ragged (with discrete only): each pair on its own sub-grid, from the {mc, nc} table of
+// adj_ragged_head_bytes(P) bytes that the caller wrote at the head of ws; the slots follow it; sources (with discrete only, never with
+// ragged): W is in/out -- on entry the weight of every coarse node in the differentiated sum, on exit that sum's derivative
 size_t adj_ragged_head_bytes(int64_t P);
 // K, K_gamma, K_gamma_gamma (directional derivatives) from three increment arrays of equal layout
 template <typename T>

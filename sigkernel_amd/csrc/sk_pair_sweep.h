@@ -102,9 +102,14 @@ __device__ __forceinline__ double stencil_q(double g, int naive) { return naive 
 // the same 3 (MM + 1) doubles of LDS, indexed by i -- and stores every cell's term to the slot's second grid (row stride NN), phase 3 sums
 // each coarse cell's r * r terms in i-major order: no atomics, the same bits on every run.  Every word of both grids that is read was
 // written for this pair, and a dropped term is never loaded.
+// `src` (nullable, row stride `lds_src`; ADJ_SOURCES of k_adj_simple): the adjoint of L = sum S[a][b] K[(a+1) << d][(b+1) << d] over the coarse
+// nodes instead of that of K[MM][NN] alone -- the same sweep with u started at src(i, j) = S[((i+1) >> d) - 1][((j+1) >> d) - 1] where
+// (i+1) and (j+1) are both multiples of 2^d, 0 elsewhere, in place of the 1 at the far corner.  `src` may be `Wp` itself (W in/out): every
+// source is read in phase 2, every store to Wp is in phase 3, and a barrier closes each diagonal in between -- hence no __restrict__ on Wp.
 template <typename T>
 __device__ void adj_pair_discrete(const T *__restrict__ inc, int64_t ld, int Mc, int Nc, int d, int naive, double *lds, double *Kf,
-                                  double *Tm, T *__restrict__ out_final_p, T *__restrict__ Wp, int64_t ldw) {
+                                  double *Tm, T *__restrict__ out_final_p, T *Wp, int64_t ldw, const T *src = nullptr,
+                                  int64_t lds_src = 0) {
     const int lane = threadIdx.x;
     const int MM = Mc << d, NN = Nc << d, r = 1 << d;
     const double rs = 1.0 / (double)r;
@@ -120,6 +125,10 @@ __device__ void adj_pair_discrete(const T *__restrict__ inc, int64_t ld, int Mc,
             const bool down = i + 1 < MM, right = j + 1 < NN;
             const T *row = inc + (int64_t)(i >> d) * ld, *row1 = inc + (int64_t)((i + 1) >> d) * ld;
             double u = (down || right) ? 0. : 1.;
+            if (src) {   // (wave-uniform)
+                const bool node = (((i + 1) | (j + 1)) & (r - 1)) == 0;
+                u = node ? (double)src[(int64_t)(((i + 1) >> d) - 1) * lds_src + (((j + 1) >> d) - 1)] : 0.;
+            }
             if (right) u += stencil_p(((double)row[(j + 1) >> d] * rs) * rs, naive) * d1[i];
             if (down) u += stencil_p(((double)row1[j >> d] * rs) * rs, naive) * d1[i + 1];
             if (down && right) u -= stencil_q(((double)row1[(j + 1) >> d] * rs) * rs, naive) * d0[i + 1];

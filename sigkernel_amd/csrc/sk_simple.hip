@@ -45,6 +45,11 @@ constexpr int ADJ_DISCRETE = 2;
 // swept over its (mc, nc) corner of the padded (Mc, Nc) block alone -- out_final = K at node (mc << d, nc << d) of the padded pair,
 // W = its exact derivative, zero on every cell with a >= mc or b >= nc; an empty sub-grid (mc == 0 or nc == 0) gives 1 and zeros.
 constexpr int ADJ_RAGGED = 4;
+// bit 3 (ADJ_SOURCES, wave-uniform, only together with ADJ_DISCRETE and never with ADJ_RAGGED): W is in/out.  On entry W[p][a][b] holds
+// S[a][b], the weight of coarse node (a + 1, b + 1) of pair p in L = sum S K (row 0 and column 0 of a prefix grid are the constant 1);
+// on exit it holds dL / d inc_c[p][a][b] -- one reverse sweep with the sources injected at their own cells (adj_pair_discrete) instead
+// of the 1 at the far corner.  Columns Nc..ldw of a padded row are neither read nor written; out_final stays K[MM][NN].
+constexpr int ADJ_SOURCES = 8;
 
 __host__ __device__ inline int64_t adj_ragged_head_doubles(int64_t P) { return (P + 31) / 32 * 32; }   // 8 bytes per entry, 256-byte units
 
@@ -66,7 +71,7 @@ __global__ __launch_bounds__(WAVE) void k_adj_simple(const T *__restrict__ inc_c
             T *Wp = W + p * (int64_t)Mc * ldw;
             if (mc > 0 && nc > 0)
                 adj_pair_discrete<T>(inc_c + p * (int64_t)Mc * ld, ld, mc, nc, d, naive, lds, Kf, Kr, out_final ? out_final + p : nullptr,
-                                     Wp, ldw);
+                                     Wp, ldw, (mode & ADJ_SOURCES) ? Wp : nullptr, ldw);
             else if (threadIdx.x == 0 && out_final)
                 out_final[p] = (T)1.;
             if (mc < Mc || nc < Nc)
@@ -223,10 +228,11 @@ int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, 
 
 template <typename T>
 int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes,
-                      hipStream_t s, bool discrete, bool ragged) {
+                      hipStream_t s, bool discrete, bool ragged, bool sources) {
     const size_t lds = simple_lds_bytes(g);
     if (lds > 160 * 1024) return SK_ERR_UNSUPPORTED;
     if (ragged && !discrete) return SK_ERR_BAD_ARG;
+    if (sources && (!discrete || ragged)) return SK_ERR_BAD_ARG;
     const int64_t gs = (int64_t)(g.MM + 1) * (g.NN + 1);
     const size_t per_block = (size_t)2 * gs * sizeof(double);
     const size_t head = ragged ? adj_ragged_head_bytes(g.P) : 0;   // the kernel derives the same offset from P
@@ -237,7 +243,7 @@ int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)k_adj_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     SK_LAUNCH(k_adj_simple<T>, dim3((int)blocks), dim3(WAVE), lds, s, inc_c, g.ld, g.P, g.Mc, g.Nc, g.dyadic,
-                       g.naive | (discrete ? ADJ_DISCRETE : 0) | (ragged ? ADJ_RAGGED : 0), out_final, W, ldw, (double *)ws);
+                       g.naive | (discrete ? ADJ_DISCRETE : 0) | (ragged ? ADJ_RAGGED : 0) | (sources ? ADJ_SOURCES : 0), out_final, W, ldw, (double *)ws);
     return check_launch();
 }
 
@@ -269,8 +275,9 @@ template int launch_adj_rescue<float>(const float *, const Geom &, const double 
 template int launch_fwd_simple<double>(const double *, const Geom &, double *, double *, double *, hipStream_t);
 template int launch_fwd_simple<float>(const float *, const Geom &, float *, float *, double *, hipStream_t);
 template int launch_adj_simple<double>(const double *, const Geom &, double *, double *, int64_t, void *, size_t,
-                                       hipStream_t, bool, bool);
-template int launch_adj_simple<float>(const float *, const Geom &, float *, float *, int64_t, void *, size_t, hipStream_t, bool, bool);
+                                       hipStream_t, bool, bool, bool);
+template int launch_adj_simple<float>(const float *, const Geom &, float *, float *, int64_t, void *, size_t, hipStream_t, bool, bool,
+                                      bool);
 
 template <typename T>
 int launch_deriv_simple(const T *inc, const T *inc_d, const T *inc_dd, const Geom &g, T *out_k, T *out_kd, T *out_kdd,

@@ -755,7 +755,7 @@ class _SigKernelGram(torch.autograd.Function):
         return grad_X, None, None, None, None, None, None
 
 
-def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need_y, cells=None):
+def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need_y, cells=None, sources=None):
     """(dL/dX, dL/dY) of one tile under exact_gradient=True (None where not needed): increments -> sk_solve_adj_* with SK_FLAG_DISCRETE
     (W = the exact derivative of the solver's value with respect to every coarse increment) -> the chain rule through the static
     kernel for BOTH arguments, from the same W.
@@ -767,8 +767,15 @@ def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need
     cells (ragged batches): (cx, cy), int32 coarse cells (length - 1) of the tile's paths on either side.  The pairs' table -- row
     (cx[a], cy[b]) for pair a * B + b of a Gram tile, (cx[p], cy[p]) paired -- goes with the launch (SK_FLAG_RAGGED): every pair is
     swept on its own sub-grid and W is exactly zero elsewhere, so the chain rule below runs unchanged on the padded paths and gives
-    the padding an exactly zero gradient."""
+    the padding an exactly zero gradient.
+
+    sources (prefix calls, in place of go: pass go=None): S (a, B, M - 1, N - 1) for a Gram tile, (a, M - 1, N - 1) paired -- dL/d(prefix
+    kernel) of every coarse node (m, n), m, n >= 1, of every pair.  They go with the launch (SK_FLAG_SOURCES): W is then dL/d(increments)
+    itself, and the chain rule below runs with a unit upstream weight."""
     more = {}
+    if sources is not None:
+        more["sources"] = sources
+        go = torch.ones(sources.shape[:-2], dtype=sources.dtype, device=sources.device)
     if cells is not None:
         cx, cy = cells
         if gram:
@@ -805,15 +812,18 @@ def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need
     return (torch.zeros_like(Xt) if need_x and gx is None else gx), (torch.zeros_like(Yt) if need_y and gy is None else gy)
 
 
-def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspace_bytes, need_x, need_y, cells=None):
+def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspace_bytes, need_x, need_y, cells=None, sources=None):
     """(dL/dX, dL/dY) of a Gram block (go (A, B)) or a paired batch (go (A,)) under exact_gradient=True, over row tiles sized like
     _rows_gradient's streaming tiles, with the stored-grid scratch of the discrete adjoint (min(pairs, 1024) slots of two fine grids,
     at most _lib.HipBackend.GRID_SCRATCH_BYTES) taken out of the budget first -- though never more than half of it.  fp32 paths are
     up-cast: the whole backward runs in fp64 and the gradients are rounded to fp32 at the end.  cells (ragged batches): (cx (A,), cy),
-    int32 coarse cells of every path, length - 1; each row tile takes its slice (_exact_tile)."""
+    int32 coarse cells of every path, length - 1; each row tile takes its slice (_exact_tile).  sources (prefix calls, in place of go:
+    pass go=None): a function (a0, a1) -> the sources of rows a0..a1 in the paths' dtype (_exact_tile), built tile by tile so that nothing
+    of size pairs x M x N outlives a tile; the tiles are those of a call with go."""
     if Xd.dtype != torch.float64:
-        gx, gy = _exact_gradient(be, static_kernel, Xd.double(), Yd.double(), go.double(), dyadic, naive, gram, workspace_bytes,
-                                 need_x, need_y, cells)
+        up = None if sources is None else (lambda a0, a1: sources(a0, a1).double())
+        gx, gy = _exact_gradient(be, static_kernel, Xd.double(), Yd.double(), None if go is None else go.double(), dyadic, naive, gram,
+                                 workspace_bytes, need_x, need_y, cells, up)
         return (None if gx is None else gx.to(Xd.dtype)), (None if gy is None else gy.to(Yd.dtype))
     A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
     Bp = Yd.shape[0] if gram else 1
@@ -825,9 +835,10 @@ def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspac
     gx = torch.empty_like(Xd) if need_x else None
     gy = torch.zeros_like(Yd) if (need_y and gram) else (torch.empty_like(Yd) if need_y else None)
     for a0, a1 in _tiles(A, per_row, max(budget - scratch, budget // 2)):
-        tx, ty = _exact_tile(be, static_kernel, Xd[a0:a1].contiguous(), Yd if gram else Yd[a0:a1].contiguous(), go[a0:a1].contiguous(),
-                             dyadic, naive, gram, need_x, need_y,
-                             None if cells is None else (cells[0][a0:a1], cells[1] if gram else cells[1][a0:a1]))
+        tx, ty = _exact_tile(be, static_kernel, Xd[a0:a1].contiguous(), Yd if gram else Yd[a0:a1].contiguous(),
+                             None if go is None else go[a0:a1].contiguous(), dyadic, naive, gram, need_x, need_y,
+                             None if cells is None else (cells[0][a0:a1], cells[1] if gram else cells[1][a0:a1]),
+                             None if sources is None else sources(a0, a1).contiguous())
         if need_x:
             gx[a0:a1] = tx
         if need_y and gram:
@@ -896,6 +907,62 @@ class _SigKernelRaggedExact(torch.autograd.Function):
                                      grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y,
                                      (lx - 1, ly - 1))
         return gx, gy, None, None, None, None, None, None, None
+
+
+def _prefix_sources(go, nodes, Mc, Nc):
+    """grad_output of a prefix call (rows of a tile: (a, B, ...) Gram, (a, ...) paired; `...` = (M, N) for nodes="all", else the slice's
+    length) -> the sources (..., Mc, Nc) of the adjoint sweep: the weight of every coarse node (m, n) with m, n >= 1.  Row 0 and column
+    0 of a prefix grid are the constant 1 and element 0 of every slice with them: their weights reach no path."""
+    if nodes == "all":
+        return go[..., 1:, 1:]
+    S = torch.zeros(go.shape[:-1] + (Mc, Nc), dtype=go.dtype, device=go.device)
+    if nodes == "diagonal":
+        torch.diagonal(S, dim1=-2, dim2=-1).copy_(go[..., 1:])
+    elif nodes == "last_row":
+        S[..., Mc - 1, :] = go[..., 1:]
+    else:
+        S[..., :, Nc - 1] = go[..., 1:]
+    return S
+
+
+class _SigKernelPrefixExact(torch.autograd.Function):
+    """compute_Gram_prefixes / compute_kernel_prefixes (every `nodes` mode) under SigKernel(exact_gradient=True): forward is _prefix_grid
+    -- the values of the no-grad call, bit for bit, on whatever route it takes -- and backward the true gradient of sum(grad_output *
+    values) for both arguments.  The discrete solver is a linear recursion in K, so the adjoint of ANY weighted sum of coarse nodes is
+    one reverse sweep per pair with each weight injected at its own node (sk_solve_adj_* with SK_FLAG_DISCRETE | SK_FLAG_SOURCES): a
+    backward costs what compute_Gram's does under exact_gradient=True, however many nodes carry a weight.  W is then dL/d(increments)
+    and _exact_gradient's chain rule runs with a unit upstream weight.  nodes="diagonal" on paths of unequal length touches the first
+    T = min(len_x, len_y) points of either side alone: the backward runs on the truncated paths and the points cut away get exactly
+    zero."""
+
+    @staticmethod
+    def forward(ctx, X, Y, static_kernel, dyadic_order, gram, nodes, _naive_solver, workspace_bytes):
+        ctx.save_for_backward(X, Y)
+        ctx.args = (static_kernel, dyadic_order, gram, nodes, _naive_solver, workspace_bytes)
+        return _prefix_grid(_lib.get_backend(), static_kernel, X.detach(), Y.detach(), dyadic_order, _naive_solver, gram, workspace_bytes,
+                            nodes)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        X, Y = ctx.saved_tensors
+        static_kernel, d, gram, nodes, naive, workspace_bytes = ctx.args
+        need_x, need_y = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        if X.shape[1] < 2 or Y.shape[1] < 2 or X.shape[0] == 0 or Y.shape[0] == 0:   # single points / empty batches: k = 1 whatever the paths
+            gx, gy = (torch.zeros_like(X) if need_x else None), (torch.zeros_like(Y) if need_y else None)
+            return gx, gy, None, None, None, None, None, None
+        Xd, Yd = X.detach(), Y.detach()
+        if nodes == "diagonal" and X.shape[1] != Y.shape[1]:
+            T = min(X.shape[1], Y.shape[1])
+            Xd, Yd = Xd[:, :T], Yd[:, :T]
+        Mc, Nc = Xd.shape[1] - 1, Yd.shape[1] - 1
+        go = grad_output.to(X.dtype)
+        gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, Xd.contiguous(), Yd.contiguous(), None, d, naive, gram, workspace_bytes,
+                                 need_x, need_y, sources=lambda a0, a1: _prefix_sources(go[a0:a1], nodes, Mc, Nc))
+        if need_x and gx.shape != X.shape:
+            gx = torch.cat((gx, torch.zeros_like(X[:, gx.shape[1]:])), dim=1)
+        if need_y and gy.shape != Y.shape:
+            gy = torch.cat((gy, torch.zeros_like(Y[:, gy.shape[1]:])), dim=1)
+        return gx, gy, None, None, None, None, None, None
 
 
 def _repeat_last_point(P, lens):
@@ -1296,8 +1363,10 @@ class SigKernel:
     kernel (a few times the cost of the default's fused adjoints) and runs in fp64: fp32 paths are up-cast for it and their gradients
     rounded to fp32 at the end.  Ragged batches (``compute_Gram_ragged`` / ``compute_kernel_ragged`` / ``compute_mmd_ragged``) get
     their gradients in this mode and in this mode only: every pair's backward sweeps its own sub-grid, and the padding -- any
-    values, NaN and inf included -- receives exactly zero.  Not sharded (``process_group`` raises ``NotImplementedError``); prefix calls stay forward only;
-    ``RBFKernel.sigma`` receives no gradient.
+    values, NaN and inf included -- receives exactly zero.  The prefix methods (``compute_Gram_prefixes`` /
+    ``compute_kernel_prefixes`` in every ``nodes`` mode, ``compute_mmd_prefixes``) likewise: one reverse sweep per pair differentiates any
+    weighting of a pair's prefix kernels -- a loss over time costs one backward, not one per time.  Not sharded (``process_group`` raises
+    ``NotImplementedError``); ``RBFKernel.sigma`` receives no gradient.
     """
 
     def __init__(self, static_kernel, dyadic_order, _naive_solver=False, workspace_bytes=None, process_group=None, exact_gradient=False):
@@ -1348,8 +1417,13 @@ class SigKernel:
             raise NotImplementedError("prefix grids are not sharded over a process group: every rank would have to gather an "
                                       "(A, B, M, N) tensor; call it on a SigKernel without process_group")
         if _wants_grad(X, Y):
-            raise NotImplementedError("compute_Gram_prefixes / compute_kernel_prefixes are forward only: the prefix grid has no "
-                                      "gradient.  Call them under torch.no_grad() or on detached paths")
+            if not self.exact_gradient:
+                raise NotImplementedError("compute_Gram_prefixes / compute_kernel_prefixes are forward only on this object: the "
+                                          "reference's adjoint formula has no prefix form.  Construct the SigKernel with "
+                                          "exact_gradient=True for their true gradient, or call them under torch.no_grad() or on "
+                                          "detached paths")
+            return _SigKernelPrefixExact.apply(X, Y, self.static_kernel, self.dyadic_order, gram, nodes, self._naive_solver,
+                                               self.workspace_bytes)
         return _prefix_grid(_lib.get_backend(), self.static_kernel, X.detach(), Y.detach(), self.dyadic_order, self._naive_solver, gram,
                             self.workspace_bytes, nodes)
 
@@ -1357,8 +1431,8 @@ class SigKernel:
         """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim) -> (batch_X, batch_Y, len_x, len_y): out[a, b, m, n] =
         k(X^a restricted to its first m + 1 points, Y^b restricted to its first n + 1 points) -- the coarse nodes of the PDE grid the
         solver sweeps anyway (node (m << dyadic_order, n << dyadic_order) of the reference's solver grids), all in one sweep.  Row
-        m = 0 and column n = 0 are exactly 1; out[..., -1, -1] is ``compute_Gram(X, Y)``.  Forward only: no ``grad_fn``, and paths that
-        require grad raise outside ``torch.no_grad()``.  Batches of unequal length: pad every path at its end with anything and gather
+        m = 0 and column n = 0 are exactly 1; out[..., -1, -1] is ``compute_Gram(X, Y)``.  Forward only on a default object: no ``grad_fn``, and
+        paths that require grad raise outside ``torch.no_grad()``; gradients under ``exact_gradient=True``, see below.  Batches of unequal length: pad every path at its end with anything and gather
         node (len_a - 1, len_b - 1).  ``max_batch`` is accepted and ignored, as elsewhere.
 
         ``nodes`` keeps a slice of every grid instead of the grid -- the same sweep, the same values bit for bit, but neither the
@@ -1367,22 +1441,33 @@ class SigKernel:
           "last_row"  (batch_X, batch_Y, len_y):              out[a, b, n] = k(X^a, Y^b[:n+1]), a stream Y^b against complete paths
           "last_col"  (batch_X, batch_Y, len_x):              out[a, b, m] = k(X^a[:m+1], Y^b)
         Element 0 is exactly 1; the last element of "last_row" / "last_col" (of "diagonal" when len_x == len_y) is ``compute_Gram(X, Y)``.
-        Any other string raises ``ValueError``."""
+        Any other string raises ``ValueError``.
+
+        Gradients: under ``SigKernel(..., exact_gradient=True)`` X and Y both receive the true gradient of any function of the returned
+        values -- the same values, bit for bit, as the no-grad call -- for every ``nodes`` mode.  The solver is a linear recursion in
+        K, so the backward of the whole grid, or of any slice or weighting of it, is ONE reverse sweep per pair with each node's
+        upstream weight injected at that node: what a ``compute_Gram`` backward costs on such an object, not one backward per
+        prefix.  ``nodes="diagonal"`` on paths of unequal length: the points beyond min(len_x, len_y) get exactly zero.  Where
+        ``X is Y`` autograd adds the two contributions; fp32 paths get fp32 gradients of an fp64 backward; one-point paths get zeros."""
         return self._prefixes(X, Y, True, max_batch, nodes)
 
     def compute_kernel_prefixes(self, X, Y, max_batch=100, nodes="all"):
         """X (batch, len_x, dim), Y (batch, len_y, dim) -> (batch, len_x, len_y): the paired form of ``compute_Gram_prefixes``;
-        out[..., -1, -1] is ``compute_kernel(X, Y)``.  ``nodes``: as there, without the batch_Y axis."""
+        out[..., -1, -1] is ``compute_kernel(X, Y)``.  ``nodes``: as there, without the batch_Y axis.  Gradients: as there -- under
+        ``exact_gradient=True``, for both arguments, one reverse sweep per pair."""
         return self._prefixes(X, Y, False, max_batch, nodes)
 
     def compute_mmd_prefixes(self, X, Y, max_batch=100):
         """X (batch_X, len_x, dim), Y (batch_Y, len_y, dim) -> (min(len_x, len_y),): value t is ``compute_mmd(X[:, :t+1], Y[:, :t+1])``
         -- the unbiased MMD^2 of the two samples as a function of time (sequential two-sample tests, change detection) -- from three
         ``nodes="diagonal"`` sweeps (K_XX, K_YY, K_XY) and the reductions of ``compute_mmd`` over the pair axes; value 0 is 0 (every
-        kernel of one-point paths is 1).  Forward only, like the prefix methods; nothing of size pairs x len_x x len_y is allocated."""
-        if _wants_grad(X, Y):
-            raise NotImplementedError("compute_mmd_prefixes is forward only: the prefix grid has no gradient.  Call it under "
-                                      "torch.no_grad() or on detached paths")
+        kernel of one-point paths is 1); nothing of size pairs x len_x x len_y is allocated by the forward.  Forward only on a default
+        object; under ``exact_gradient=True`` a composition of three differentiable ``nodes="diagonal"`` calls, so that a loss over time
+        ``sum_t w_t MMD^2_t`` trains X and Y with three backward sweeps in all, not three per t."""
+        if _wants_grad(X, Y) and not self.exact_gradient:
+            raise NotImplementedError("compute_mmd_prefixes is forward only on this object: the reference's adjoint formula has no "
+                                      "prefix form.  Construct the SigKernel with exact_gradient=True for its true gradient, or call "
+                                      "it under torch.no_grad() or on detached paths")
         T = min(X.shape[1], Y.shape[1])
         K_XX = self.compute_Gram_prefixes(X, X, max_batch, nodes="diagonal")[..., :T]
         K_YY = self.compute_Gram_prefixes(Y, Y, max_batch, nodes="diagonal")[..., :T]
