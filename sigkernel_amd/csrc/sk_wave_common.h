@@ -77,6 +77,47 @@ __device__ __forceinline__ void set_one_in_lanes(double (&v)[S], unsigned long l
     }
 }
 
+// The same window, with one more instruction in it: the lanes of `lanes` also receive a fresh address a = (off ^ flip) + base, `off` a
+// wave-uniform scalar, `flip` and `base` per lane (v_xad_u32: one VALU instruction, one scalar operand).  Every other lane keeps its `a`.
+template <int S>
+__device__ __forceinline__ void set_one_and_address_in_lanes(double (&v)[S], unsigned &a, unsigned off, unsigned flip, unsigned base,
+                                                             unsigned long long lanes) {
+    static_assert(S == 2 || S == 4 || S == 8, "one v_mov_b64 per value");
+    if constexpr (S == 2) {
+        asm volatile("s_mov_b64 exec, %3\n\t"
+                     "v_mov_b64 %0, 1.0\n\t"
+                     "v_mov_b64 %1, 1.0\n\t"
+                     "v_xad_u32 %2, %4, %5, %6\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(v[0]), "+v"(v[1]), "+v"(a)
+                     : "s"(lanes), "s"(off), "v"(flip), "v"(base));
+    } else if constexpr (S == 4) {
+        asm volatile("s_mov_b64 exec, %5\n\t"
+                     "v_mov_b64 %0, 1.0\n\t"
+                     "v_mov_b64 %1, 1.0\n\t"
+                     "v_mov_b64 %2, 1.0\n\t"
+                     "v_mov_b64 %3, 1.0\n\t"
+                     "v_xad_u32 %4, %6, %7, %8\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(a)
+                     : "s"(lanes), "s"(off), "v"(flip), "v"(base));
+    } else {
+        asm volatile("s_mov_b64 exec, %9\n\t"
+                     "v_mov_b64 %0, 1.0\n\t"
+                     "v_mov_b64 %1, 1.0\n\t"
+                     "v_mov_b64 %2, 1.0\n\t"
+                     "v_mov_b64 %3, 1.0\n\t"
+                     "v_mov_b64 %4, 1.0\n\t"
+                     "v_mov_b64 %5, 1.0\n\t"
+                     "v_mov_b64 %6, 1.0\n\t"
+                     "v_mov_b64 %7, 1.0\n\t"
+                     "v_xad_u32 %8, %10, %11, %12\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(a)
+                     : "s"(lanes), "s"(off), "v"(flip), "v"(base));
+    }
+}
+
 __device__ __forceinline__ double dpp_shl1(double v, double fill) {
     // lane l receives lane l+1's value; lane 63 keeps `fill`
     int lo = __double2loint(v), hi = __double2hiint(v);

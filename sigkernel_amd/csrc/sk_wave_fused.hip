@@ -211,6 +211,15 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // full-wave RBF instance of 512 x 512 pairs of 64 points at dyadic 2 measured 0.4 % slower with the reordered counter alone).
     constexpr bool RESET_AT_END = !CUR && !RBF && !FULLWAVE && !MID;
     unsigned a_e;   // the odd rows are at a_e ^ 128: wave slices and slabs are 256-byte aligned, a slab row is 128 bytes
+    // CARRY: a_e is a function of the stream unit a lane reads and of its ring, nothing else, and lane l reads at step t the unit lane
+    // l - 1 read at step t - 1.  So a lane does not advance and wrap its own address: at the end of a step it takes the address of the
+    // lane above (one wave_shr:1 DPP move), and the first lane of every lane group receives its group's fresh one in the EXEC window
+    // that take_top() opens there anyway: (y_off ^ y_flip) + my_y, y_off the ring offset of the unit t + 1 -- the first lane's, kept by
+    // the scalar unit with the arithmetic of the per-lane walk below -- and y_flip the lane group's share of the slab parity.  Before a
+    // lane's first unit it holds what the prologue's closed form and the lanes above gave it: addresses of units < 0 in the same ring.
+    // Where the step has no such window at its end (one lane group per wave, RBF) or no running address (CUR) the per-lane walk stays.
+    constexpr bool CARRY = RESET_AT_END;
+    unsigned y_off = 0;
     // ---- the wave's stream of pairs, dealt in chunks: chunk 0 of a wave is fixed (C0 pairs per lane group from pair cb0 on), the
     // rest is drawn CQ = 2^logC pairs per lane group at a time from prm.queue (nullptr: chunk 0 is the whole share).  Position i of
     // lane group g is pair cb[k] + g size(k) + off, (k, off) = chunk and offset of i; NOPAIR marks "no such pair".
@@ -304,6 +313,11 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     const unsigned long long top_lanes = __builtin_amdgcn_ballot_w64(lam == 0);   // the first lane of every lane group (all lanes are active)
     const unsigned my_y = lds0 + (shy ? 0u : (unsigned)grp * y_bytes);
     const unsigned y_lim = my_y + y_bytes;
+    unsigned y_flip = 0;   // CARRY: the lane group's share of the slab parity (ypar above), as the address bit it flips
+    if constexpr (CARRY) {
+        y_flip = shy ? 0u : (unsigned)(grp & 1) << 7;
+        asm volatile("" : "+v"(y_flip));
+    }
     const unsigned ring_bytes = FULLWAVE ? (unsigned)(((WAVE >> 3) + 2) * Y_SLAB_PITCH) : y_bytes;   // = y_bytes, as a literal when L = 64
     {
         const unsigned ya = my_y + (unsigned)(yslab * Y_SLAB_PITCH + ((-lam & 7) << 4));
@@ -575,7 +589,13 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         // no register is held across the loop edge for lane 0's sake.
 #pragma unroll
         for (int i = 0; i < S; ++i) top[i] = dpp_shr1_zero(bot[i]);
-        set_one_in_lanes(top, top_lanes);
+        if constexpr (CARRY) {
+            // (the first lane of the wave keeps its own: overwritten in the window like every first lane)
+            a_e = (unsigned)__builtin_amdgcn_update_dpp((int)a_e, (int)a_e, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+            set_one_and_address_in_lanes(top, a_e, y_off, y_flip, my_y, top_lanes);
+        } else {
+            set_one_in_lanes(top, top_lanes);
+        }
     };
     for (int t = 0; t < t_end; ++t) {
         if (EDGES) {   // the edge values of the previous macro-step, straight from the state registers
@@ -720,12 +740,14 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         auto fetch_next = [&]() {
             const bool turn = ((t + 1) & (XW - 1)) == 0;   // the next step opens an x window (and, every eighth step, a y slab for
             if (__builtin_expect(turn, 0)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // lane 0): their DMA was issued XW (8) steps ago
-            // (in place: as `a_e += 16` the sum lands in a second register and is copied back at the loop edge)
-            asm("v_add_u32 %0, 16, %0" : "+v"(a_e));
-            if (((t + 1) & 7) == lam7) {   // next slab: the other parity, one slab less one row on, wrapping at the end of the ring
-                asm volatile("");          // (a real branch: if-converted, the update costs two more VALU instructions per step)
-                const unsigned e = (a_e + (unsigned)(Y_SLAB_PITCH - 128)) ^ 128u;
-                a_e = e - (e >= y_lim ? ring_bytes : 0u);
+            if constexpr (!CARRY) {
+                // (in place: as `a_e += 16` the sum lands in a second register and is copied back at the loop edge)
+                asm("v_add_u32 %0, 16, %0" : "+v"(a_e));
+                if (((t + 1) & 7) == lam7) {   // next slab: the other parity, one slab less one row on, wrapping at the end of the ring
+                    asm volatile("");          // (a real branch: if-converted, the update costs two more VALU instructions per step)
+                    const unsigned e = (a_e + (unsigned)(Y_SLAB_PITCH - 128)) ^ 128u;
+                    a_e = e - (e >= y_lim ? ring_bytes : 0u);
+                }
             }
             read_y();
             // this lane starts a pair in the next step (RESET_AT_END: tm is the NEXT step's already -- see "advance" -- and c_u0m1 is dead)
@@ -794,6 +816,15 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         if constexpr (RESET_AT_END) {
             // (an opaque move, as in the full-wave branch: left to the compiler, the copy is made twice over)
             asm volatile("v_mov_b64 %0, %1" : "=v"(corner) : "v"(top[S - 1]));
+            if constexpr (CARRY) {
+                // ring offset of unit t + 1, the first lane's next: the per-lane walk of fetch_next with lam7 = 0 and the ring at 0
+                y_off += 16u;
+                if (((t + 1) & 7) == 0) {
+                    const unsigned e = (y_off + (unsigned)(Y_SLAB_PITCH - 128)) ^ 128u;
+                    y_off = e - (e >= ring_bytes ? ring_bytes : 0u);
+                }
+                asm volatile("" : "+s"(y_off));
+            }
             take_top();   // for macro-step t + 1
         } else if (!FULLWAVE) {
             corner = top[S - 1];
