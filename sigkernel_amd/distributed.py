@@ -15,8 +15,8 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .sigkernel import (_SigKernel, _SigKernelGram, _budget, _fused_static, _gram_block, _sym_fused_gradient, _sym_triangle_ok,
-                        _sym_unfused_gradient, k_kgrad)
+from .sigkernel import (_Kept, _SigKernel, _SigKernelGram, _budget, _fused_static, _gram_block, _keep_sym_values, _sym_fused_gradient,
+                        _sym_triangle_ok, _sym_unfused_gradient, _take, k_kgrad)
 
 __all__ = ["row_range", "sharded_gram", "sharded_kernel", "ShardedGram", "ShardedPaired", "ShardedSymGram", "sharded_kgrad",
            "record_collectives", "collective_summary"]
@@ -272,18 +272,17 @@ class ShardedSymGram(torch.autograd.Function):
         bs, blocks = _folded_blocks(A, rank, world)
         Xd = X.detach().contiguous()
         strips = torch.zeros(2, bs, A, dtype=X.dtype, device=X.device)
-        kept_blocks = []
+        ctx.blocks = []
         for slot, (lo, hi) in enumerate(blocks):
             if hi > lo:
-                kept = []
+                kept = _Kept(lo, hi)
                 strips[slot, : hi - lo, lo:] = _gram_block(be, static_kernel, Xd[lo:hi].contiguous(), Xd[lo:].contiguous(),
                                                            dyadic_order, _naive_solver, workspace_bytes, 3, kept)
-                kept_blocks.append((lo, hi, kept))
+                ctx.blocks.append(kept)
         ctx.save_for_backward(X)
         ctx.args = (static_kernel, dyadic_order, _naive_solver, workspace_bytes, group)
-        ctx.blocks = kept_blocks
         K = _assemble_folded(strips, A, bs, world, group)
-        ctx.K = K.detach()        # forward values: what arms the fused adjoint's device-side rescue
+        _keep_sym_values(ctx.blocks, K)        # forward values: what arms the fused adjoint's device-side rescue
         return K
 
     @staticmethod
@@ -294,11 +293,14 @@ class ShardedSymGram(torch.autograd.Function):
         Xd = X.detach().contiguous()
         go = grad_output.to(X.dtype).contiguous()
         budget = _budget(X.device, workspace_bytes)
-        grad = _sym_fused_gradient(be, static_kernel, Xd, go, d, naive, ctx.blocks, budget, getattr(ctx, "K", None))
+        blocks = _take(ctx, "blocks")
+        if blocks is None:      # a second backward: the same row blocks with nothing kept, it sweeps forward again by itself
+            folded = _folded_blocks(X.shape[0], dist.get_rank(group), dist.get_world_size(group))[1]
+            blocks = [_Kept(lo, hi) for lo, hi in folded if hi > lo]
+        grad = _sym_fused_gradient(be, static_kernel, Xd, go, d, naive, blocks, budget)
         if grad is None:
             kind, param = _fused_static(static_kernel, True)
-            grad = _sym_unfused_gradient(be, kind, param, Xd, go, d, naive, ctx.blocks, budget)
-        ctx.blocks = [(lo, hi, []) for lo, hi, _ in ctx.blocks]      # a second backward sweeps forward again by itself
+            grad = _sym_unfused_gradient(be, kind, param, Xd, go, d, naive, blocks, budget)
         grad = _all_reduce_sum(grad.contiguous(), group)
         # X is both arguments: the reference's 2x rule (sigkernel.py:410-412)
         return 2 * grad, None, None, None, None, None

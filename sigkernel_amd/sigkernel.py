@@ -12,6 +12,7 @@ Goursat PDE solve and the adjoint PDE run in the HIP kernels of libsigkernel_amd
   results never depended on ``max_batch`` (sigkernel.py:31-39, :102-127) and still do not.
 """
 import functools
+from typing import NamedTuple
 
 import torch
 
@@ -41,6 +42,67 @@ def _tiles(n_rows, bytes_per_row, budget):
 def _cap_rows(bytes_per_row, pairs_per_row, budget):
     """bytes_per_row, raised where needed so that a row tile of `budget` bytes never holds more than _MAX_LAUNCH_PAIRS pairs."""
     return max(bytes_per_row, -(-int(budget) * int(pairs_per_row) // _MAX_LAUNCH_PAIRS))
+
+
+class _Tile:
+    """What forward keeps for the rows a0:a1 of a block: the terminal edges of their pairs (8 (MM + NN) bytes per pair; None where no
+    kernel kept them) and, on the streaming route, the increments the static kernel formed for exactly these rows (else None)."""
+    __slots__ = ("a0", "a1", "edges", "increments")
+
+    def __init__(self, a0, a1, edges=None, increments=None):
+        self.a0, self.a1, self.edges, self.increments = a0, a1, edges, increments
+
+    def take_increments(self, dtype):
+        """The kept increments where they are of `dtype`, else None.  The tile lets go of them either way: the caller's reference is
+        the last one, so they are freed before the chain rule allocates."""
+        inc, self.increments = self.increments, None
+        return inc if inc is not None and inc.dtype == dtype else None
+
+
+class _Kept:
+    """The hand-off of one forward block to its backward: the row tiles with what each kept, and the forward values K of the block's
+    pairs (what arms the fused adjoints' device-side rescue).  r0:r1 are the block's rows in the symmetric route's triangle.  The
+    Functions hold it on `ctx` and take it off with _take: every decision about kept state is a method here."""
+    __slots__ = ("tiles", "K", "r0", "r1")
+
+    def __init__(self, r0=0, r1=None, K=None):
+        self.tiles, self.K, self.r0, self.r1 = [], K, r0, r1
+
+    def add(self, a0, a1, edges, increments=None):
+        self.tiles.append(_Tile(a0, a1, edges, increments))
+
+    def whole_edges(self, n_rows):
+        """The edges where ONE tile kept them for all n_rows rows (what the fused forwards leave), else None."""
+        t = self.tiles[0] if len(self.tiles) == 1 else None
+        return t.edges if t is not None and (t.a0, t.a1) == (0, n_rows) else None
+
+    def release(self):
+        """Let go of every tile's edges and increments (K is the caller's output: it costs nothing to hold)."""
+        self.tiles = []
+
+    def row_tiles(self, n_rows, per_row, budget, strict=False):
+        """Row tiles of a backward pass with what forward kept for them.  strict: never hand back a tile with more rows than `budget`
+        allows (the kept tiling may have been sized for a route with less transient memory); a kept tiling that does not fit is
+        released -- before the fresh tiles allocate -- and the adjoint sweeps forward itself."""
+        tiles = [_Tile(a0, a1) for a0, a1 in _tiles(n_rows, per_row, budget)]
+        full = self.whole_edges(n_rows)
+        if full is not None:
+            if len(tiles) == 1:
+                return self.tiles
+            self.tiles[0].increments = None     # (formed for all rows at once: of no use to a slice)
+            per = full.numel() // n_rows       # the fused forward kept one block for all rows: slice it per tile
+            return [_Tile(t.a0, t.a1, full[t.a0 * per:t.a1 * per]) for t in tiles]
+        if self.tiles and (not strict or max(t.a1 - t.a0 for t in self.tiles) <= tiles[0].a1 - tiles[0].a0):
+            return self.tiles                  # the tiling of forward, with the edges it kept (None where the strip kernels did not apply)
+        self.release()
+        return tiles
+
+
+def _take(ctx, name="kept"):
+    """The forward's hand-off, once: a second backward through a retained graph finds None and sweeps forward by itself."""
+    kept = getattr(ctx, name, None)
+    setattr(ctx, name, None)
+    return kept
 
 
 def _fused_static(static_kernel, gram):
@@ -177,28 +239,28 @@ def _upcast_tile(X, dyadic):
     return X.dtype == torch.float32 and dyadic == 2
 
 
-def _tile_gradient(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, edges=None):
+def _tile_gradient(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, kept=None):
     """dL/dX for one tile on the unfused routes: increments -> adjoint PDE (W = dK/d inc_c) -> chain through the static kernel.
+    kept: the _Tile forward left for exactly these rows (its edges spare the adjoint's forward sweep, its increments the static kernel).
 
     Linear / RBF: sk_static_increments -> sk_solve_adj -> sk_static_adjoint.
     Generic (any duck-typed static kernel): G with autograd -> sk_increments -> sk_solve_adj ->
     sk_increments_adjoint (scaled by the upstream gradient) -> one vector-Jacobian product through the static kernel;
     this replaces the reference's h = 1e-9 finite difference (sigkernel.py:313-341, :472-500)."""
     fused = _fused_static(static_kernel, gram)
+    edges = kept.edges if kept is not None else None
     if fused is not None and hasattr(be, "static_adjoint"):
         if _upcast_tile(Xt, dyadic) and edges is None:
             # fp32 paths at dyadic 2: the streaming adjoint exists for fp64 there.  The whole tile in fp64 -- increments formed
             # from the up-cast paths, adjoint, chain rule -- instead of fp32 increments up-cast in 4 GB chunks (round 2: 3x slower)
             g = _tile_gradient(be, static_kernel, Xt.double(), Yt.double(), go.double(), dyadic, naive, gram)
             return g.to(Xt.dtype)
-        inc = getattr(edges, "_sk_increments", None) if edges is not None else None      # (what _gram_block kept with the edges)
-        if inc is None or inc.shape[:-2] != ((Xt.shape[0], Yt.shape[0]) if gram else (Xt.shape[0],)) or inc.dtype != Xt.dtype:
+        inc = kept.take_increments(Xt.dtype) if edges is not None else None      # (what _gram_block kept beside the edges)
+        if inc is None:
             inc = be.static_increments(fused[0], fused[1], Xt, Yt, gram)
         if inc is not None:
             _, W = be.solve_adj(inc, dyadic, naive, edges=edges) if edges is not None else be.solve_adj(inc, dyadic, naive)
-            del inc
-            if getattr(edges, "_sk_increments", None) is not None:
-                edges._sk_increments = None      # (freed before the chain rule allocates)
+            del inc      # (freed before the chain rule allocates)
             return be.static_adjoint(fused[0], fused[1], Xt, Yt, W, go, gram)
     Xg = Xt.clone().requires_grad_(True)
     with torch.enable_grad():
@@ -212,17 +274,18 @@ def _tile_gradient(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, edges=Non
     return g
 
 
-def _fused_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, budget, Kvals=None, route=FUSED):
+def _fused_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, budget, route=FUSED):
     """dL/dX for all rows through the fused adjoints -- sk_linear_adjoint_fused_f64 / sk_rbf_adjoint_fused_f64 (route FUSED) or their
     multi-band forms (FUSED_MB): adjoint PDE and the static kernel's chain rule in one kernel, from the paths and the forward's
     edges; no matrix of size pairs x M x N -- one launch per row tile.  None when the kernel does not cover the case after all (the
     caller then takes the streaming route, tiled by ITS transient memory).  Exploding kernels are the library's business: with the
-    forward values (Kvals, or what the forward re-run here returns) the launch takes such pairs out of the sweep and adds their
+    forward values (kept.K, or what the forward re-run here returns) the launch takes such pairs out of the sweep and adds their
     exact, stored-grid share on the device (csrc/sk_adj_fused_rescue.hip) -- nothing is read back, a backward pass has no host
     synchronisation."""
     A, M = Xd.shape[0], Xd.shape[1]
     kind, param = _fused_static(static_kernel, gram)
     linear = kind == 0
+    Kvals = kept.K
     if route == FUSED_MB:
         adj_mb = be.linear_adjoint_fused_mb if linear else be.rbf_adjoint_fused_mb
         # long / wide paths: sk_solve_fwd_static_* (edges) + the multi-band adjoint; per pair the edges, the partial sums and node row 0
@@ -231,7 +294,8 @@ def _fused_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, bu
             return None
         per_row = _cap_rows((Yd.shape[0] if gram else 1) * pair_bytes, Yd.shape[0] if gram else 1, budget)
         grad = torch.empty_like(Xd)
-        for a0, a1, edges in _edge_tiles(kept, A, per_row, budget, strict=True):
+        for t in kept.row_tiles(A, per_row, budget, strict=True):
+            a0, a1, edges = t.a0, t.a1, t.edges
             Xt = Xd[a0:a1].contiguous()
             Yt = Yd if gram else Yd[a0:a1].contiguous()
             got = go if go is None else go[a0:a1].reshape(-1).contiguous()
@@ -250,7 +314,8 @@ def _fused_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, bu
         return grad
     per_row = _cap_rows((64 * Yd.shape[0] + 2048 * M) if gram else 4096 * M, Yd.shape[0] if gram else 1, budget)      # edges and partial sums only
     grad = torch.empty_like(Xd)
-    for a0, a1, edges in _edge_tiles(kept, A, per_row, budget):
+    for t in kept.row_tiles(A, per_row, budget):
+        a0, a1, edges = t.a0, t.a1, t.edges
         Xt = Xd[a0:a1].contiguous()
         Yt = Yd if gram else Yd[a0:a1].contiguous()
         Kt = None if Kvals is None else Kvals[a0:a1]
@@ -271,18 +336,18 @@ def _fused_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, bu
     return grad
 
 
-def _swapped_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, kept, budget, Kvals=None):
+def _swapped_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, kept, budget):
     """dL/dX of a Gram block whose FIRST paths are long and whose second paths fit the one-band adjoints' lanes (route FUSED_SWAP):
     the adjoint runs on the pairs (y_b, x_a) -- k and the static kernel are symmetric -- with the SECOND-argument sums of that sweep
     (sk_rbf_adjoint_fused_f64 / sk_linear_adjoint_fused_f64 with ypart), folded with the transposed upstream gradient:
     d k(x_a, y_b) / d x_a = d2 k(y_b, x_a).  Tiled over the rows of Y by the memory of the sums (48 / 64 bytes per pair and column).
-    kept: the edges the forward kept for the swapped pairs, else they are formed here.  None where the kernel declines (the caller streams)."""
+    kept: the edges the forward kept for the swapped pairs (one block for all rows), else they are formed here.  None where the kernel declines (the caller streams)."""
     A, B = Xd.shape[0], Yd.shape[0]
     kind, param = _fused_static(static_kernel, True)
     linear = kind == 0
     fwd, adj = (be.solve_fwd_fused_linear, be.linear_adjoint_fused) if linear else (be.solve_fwd_fused_rbf, be.rbf_adjoint_fused)
-    edges = kept[0][2] if (kept and len(kept) == 1 and kept[0][:2] == (0, A) and kept[0][2] is not None) else None
-    KT = None if Kvals is None else Kvals.t().contiguous()
+    edges = kept.whole_edges(A)
+    KT = None if kept.K is None else kept.K.double().t().contiguous()
     if edges is None:
         res = fwd(Yd, Xd, param, dyadic, naive, True, keep_edges=True)
         if res is None or res[1] is None:
@@ -302,31 +367,33 @@ def _swapped_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, kept, budget
     return grad
 
 
-def _rows_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, workspace_bytes, Kvals=None):
+def _rows_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, workspace_bytes):
     """dL/dX (A,M,D) of a Gram block (gram=True: go (A,B)) or a paired batch (go (A,)): the fused linear / RBF adjoint when it
     applies, else the unfused routes tiled over rows by their transient memory (3 (Linear/RBF) or 8 (generic) arrays of the
-    size of the tile's increments).  kept: what forward left for the tiles ([(a0, a1, edges)] or None)."""
+    size of the tile's increments).  kept: what forward left (_Kept), None where it left nothing or a backward has used it."""
+    if kept is None:
+        kept = _Kept()
     A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
     budget = _budget(Xd.device, workspace_bytes)
     route = _route(be, OP_ADJOINT, static_kernel, Xd, Yd, dyadic, naive, gram)
     if route in (FUSED, FUSED_MB):
-        g = _fused_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, budget, Kvals, route)
+        g = _fused_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, kept, budget, route)
         if g is not None:
             return g
     if route == FUSED_SWAP and gram:
         # (fp32 paths: swept in fp64 like every one-band call -- the edges their forward kept are those of the up-cast paths)
-        g = _swapped_gradient(be, static_kernel, Xd.double(), Yd.double(), go.double(), dyadic, naive, kept, budget,
-                              None if Kvals is None else Kvals.double())
+        g = _swapped_gradient(be, static_kernel, Xd.double(), Yd.double(), go.double(), dyadic, naive, kept, budget)
         if g is not None:
             return g.to(Xd.dtype)
-        kept = None       # (edges of the swapped pairs are of no use to the streaming route below)
+        kept.release()    # (edges of the swapped pairs are of no use to the streaming route below)
     fused = _fused_static(static_kernel, gram) is not None
     esize = 8 if (fused and _upcast_tile(Xd, dyadic)) else Xd.element_size()
     per_row = (3 if fused else 8) * (Yd.shape[0] if gram else 1) * M * N * esize
     grad = torch.empty_like(Xd)
-    for a0, a1, edges in _edge_tiles(kept, A, per_row, budget, strict=True):
+    for t in kept.row_tiles(A, per_row, budget, strict=True):
+        a0, a1 = t.a0, t.a1
         grad[a0:a1] = _tile_gradient(be, static_kernel, Xd[a0:a1].contiguous(), Yd if gram else Yd[a0:a1].contiguous(),
-                                     go[a0:a1].contiguous(), dyadic, naive, gram, edges=edges)
+                                     go[a0:a1].contiguous(), dyadic, naive, gram, t)
     return grad
 
 
@@ -383,7 +450,6 @@ class _SigKernel(torch.autograd.Function):
         if M < 2 or N < 2 or A == 0:  # a single point: the grid is its boundary, k = 1 (sigkernel.py:212-253 with MM = 0);
             return torch.ones(A, dtype=X.dtype, device=X.device)   # an empty batch: an empty result, like the CPU reference
         Xd, Yd = X.detach(), Y.detach()
-        ctx.kept_edges = None
         # (whether a gradient can be ASKED for -- not X.requires_grad: under torch.no_grad() a leaf X must not make the forward keep edges,
         # take the adjoint's kernel family or up-cast fp32 paths)
         need = bool(ctx.needs_input_grad[0])
@@ -398,13 +464,13 @@ class _SigKernel(torch.autograd.Function):
                 res = _fused_forward(be, static_kernel, Xd, Yd, dyadic_order, _naive_solver, gram=False, keep_edges=True)
                 if res is not None:
                     K, edges = res
+                    ctx.kept = _Kept(K=K.detach())
                     if edges is not None:
-                        ctx.kept_edges = [(0, A, edges)]
-                    ctx.K = K.detach()
+                        ctx.kept.add(0, A, edges)
                     return K
         K = _fused_forward(be, static_kernel, Xd, Yd, dyadic_order, _naive_solver, gram=False)
         if K is not None:
-            ctx.K = K.detach() if need else None     # forward values: what arms the fused adjoint's device-side rescue
+            ctx.kept = _Kept(K=K.detach()) if need else None     # forward values: what arms the fused adjoint's device-side rescue
             return K
         K = torch.empty(A, dtype=X.dtype, device=X.device)
         per_row = 2 * M * N * X.element_size()
@@ -421,9 +487,8 @@ class _SigKernel(torch.autograd.Function):
         A, M, N = X.shape[0], X.shape[1], Y.shape[1]
         if M >= 2 and N >= 2 and A > 0:
             go = grad_output.to(X.dtype).contiguous()
-            kept, ctx.kept_edges = getattr(ctx, "kept_edges", None), None
-            grad_X = _rows_gradient(be, sk, X.detach().contiguous(), Y.detach().contiguous(), go, d, naive, False, kept,
-                                    ctx.workspace_bytes, getattr(ctx, "K", None))
+            grad_X = _rows_gradient(be, sk, X.detach().contiguous(), Y.detach().contiguous(), go, d, naive, False, _take(ctx),
+                                    ctx.workspace_bytes)
         else:
             grad_X = torch.zeros_like(X)     # single points / an empty batch: k = 1 whatever X is
         return grad_X, None, None, None, None, None
@@ -452,7 +517,7 @@ _MAX_LAUNCH_PAIRS = 1 << 30  # pairs per fused launch (the fused kernels index p
 def _gram_block(be, static_kernel, Xd, Yd, dyadic_order, naive, workspace_bytes, rows_factor=None, keep=None):
     """K[a, b] for every pair of Xd x Yd (no autograd): fused kernel, or increments + solver tiled over rows of Xd.
 
-    keep (a list, when a gradient is pending): receives one (a0, a1, edges) per tile -- the terminal row/column of every
+    keep (a _Kept, when a gradient is pending): receives one tile per row tile -- the terminal row/column of every
     pair, 8(MM+NN) bytes per pair, which lets backward skip its forward sweep.  The reference keeps the whole solution
     grid for the same purpose (sigkernel.py:248, :397-399)."""
     A, B, M, N = Xd.shape[0], Yd.shape[0], Xd.shape[1], Yd.shape[1]
@@ -462,17 +527,16 @@ def _gram_block(be, static_kernel, Xd, Yd, dyadic_order, naive, workspace_bytes,
         # 5.2 s and 114 GB streamed)
         rows = max(1, _MAX_LAUNCH_PAIRS // B)
         K = torch.empty(A, B, dtype=Xd.dtype, device=Xd.device)
-        kept_all = []
+        merged = []
         for a0 in range(0, A, rows):
             a1 = min(a0 + rows, A)
-            sub = [] if keep is not None else None
+            sub = _Kept() if keep is not None else None
             K[a0:a1] = _gram_block(be, static_kernel, Xd[a0:a1], Yd, dyadic_order, naive, workspace_bytes, rows_factor, sub)
-            if sub:
-                kept_all.extend((a0 + s0, a0 + s1, e) for s0, s1, e in sub)
+            if sub is not None:
+                merged.extend(_Tile(a0 + t.a0, a0 + t.a1, t.edges, t.increments) for t in sub.tiles)
         # edges only when every tile kept them for all of its rows (else backward tiles by its own budget and sweeps forward itself)
-        if keep is not None and kept_all and kept_all[0][0] == 0 and kept_all[-1][1] == A \
-                and all(kept_all[i][1] == kept_all[i + 1][0] for i in range(len(kept_all) - 1)):
-            keep.extend(kept_all)
+        if merged and merged[0].a0 == 0 and merged[-1].a1 == A and all(s.a1 == t.a0 for s, t in zip(merged, merged[1:])):
+            keep.tiles.extend(merged)
         return K
     budget = None   # (asked of the device only where it is needed: a small fused call does not pay for hipMemGetInfo)
     if keep is not None and hasattr(be, "solve_fwd_keep_edges"):
@@ -491,7 +555,7 @@ def _gram_block(be, static_kernel, Xd, Yd, dyadic_order, naive, workspace_bytes,
         if res is not None:
             K, edges = res
             if edges is not None:
-                keep.append((0, A, edges))      # one block for all rows: backward slices it per tile
+                keep.add(0, A, edges)      # one block for all rows: backward slices it per tile
             return K
     else:
         K = _fused_forward(be, static_kernel, Xd, Yd, dyadic_order, naive, gram=True)
@@ -509,12 +573,11 @@ def _gram_block(be, static_kernel, Xd, Yd, dyadic_order, naive, workspace_bytes,
         inc = _increments(be, static_kernel, Xd[a0:a1], Yd, True, by_kernel)     # sigkernel.py:362-363 (:364 by index)
         if keep is not None:
             K[a0:a1], edges = be.solve_fwd_keep_edges(inc, dyadic_order, naive)  # :378 / :395, + the edges for backward
-            if edges is not None and by_kernel and len(tiles) == 1 and \
-                    inc.numel() * inc.element_size() <= _cost("keep_increments_fraction") * budget:
-                # one tile of moderate size: its increments ride along with the edges, and backward does not evaluate the static
-                # kernel a second time (a quarter of a gradient step on wide paths, profiles/r06_keep_inc.txt)
-                edges._sk_increments = inc
-            keep.append((a0, a1, edges))
+            # one tile of moderate size: its increments are kept beside the edges, and backward does not evaluate the static
+            # kernel a second time (a quarter of a gradient step on wide paths, profiles/r06_keep_inc.txt)
+            keep_inc = edges is not None and by_kernel and len(tiles) == 1 and \
+                inc.numel() * inc.element_size() <= _cost("keep_increments_fraction") * budget
+            keep.add(a0, a1, edges, inc if keep_inc else None)
         else:
             K[a0:a1] = be.solve_fwd(inc, dyadic_order, naive)                    # :378 / :395
     return K
@@ -523,8 +586,8 @@ def _gram_block(be, static_kernel, Xd, Yd, dyadic_order, naive, workspace_bytes,
 def _gram_symmetric(be, static_kernel, Xd, dyadic_order, naive, workspace_bytes, keep_blocks=None):
     """compute_Gram(X, X, sym=True): only the blocks on and above the diagonal of a T x T tiling are solved and
     mirrored, like the reference's CPU solver does pair by pair (cython_backend.pyx:74-97; its GPU path ignores `sym`).
-    The result is exactly symmetric.  keep_blocks (a list, when a gradient is pending) receives (r0, r1, kept edges) per
-    row block for _SigKernelGram.backward's triangular adjoint."""
+    The result is exactly symmetric.  keep_blocks (a list, when a gradient is pending) receives one _Kept per
+    row block r0:r1 for _SigKernelGram.backward's triangular adjoint (the caller gives each its rows of the finished K)."""
     A = Xd.shape[0]
     if keep_blocks is None and hasattr(be, "solve_fwd_fused_sym"):
         # exactly LinearKernel / RBFKernel within the single-band fused kernels' scope: the triangle in ONE launch, every value
@@ -554,11 +617,11 @@ def _gram_symmetric(be, static_kernel, Xd, dyadic_order, naive, workspace_bytes,
     step = -(-A // T)
     for r0 in range(0, A, step):
         r1 = min(r0 + step, A)
-        kept = [] if keep_blocks is not None else None
+        kept = _Kept(r0, r1) if keep_blocks is not None else None
         blk = _gram_block(be, static_kernel, Xd[r0:r1].contiguous(), Xd[r0:].contiguous(), dyadic_order, naive, workspace_bytes,
                           3 if keep_blocks is not None else None, kept)
         if keep_blocks is not None:
-            keep_blocks.append((r0, r1, kept))
+            keep_blocks.append(kept)
         K[r0:r1, r0:] = blk
         if r1 < A:
             K[r1:, r0:r1] = blk[:, r1 - r0:].t()
@@ -568,20 +631,11 @@ def _gram_symmetric(be, static_kernel, Xd, dyadic_order, naive, workspace_bytes,
     return K
 
 
-def _edge_tiles(kept, n_rows, per_row, budget, strict=False):
-    """Row tiles of a backward pass with the terminal edges forward kept for them: [(a0, a1, edges or None)].
-    strict: never hand back a tile with more rows than `budget` allows (the kept tiling may have been sized for a route with
-    less transient memory); kept edges that do not match the tiling are then dropped and the adjoint sweeps forward itself."""
-    tiles = [(a0, a1, None) for a0, a1 in _tiles(n_rows, per_row, budget)]
-    if kept and len(kept) == 1 and kept[0][:2] == (0, n_rows) and kept[0][2] is not None:
-        if len(tiles) == 1:
-            return kept
-        full = kept[0][2]              # the fused forward kept one block for all rows: slice it per tile
-        per = full.numel() // n_rows
-        return [(a0, a1, full[a0 * per:a1 * per]) for a0, a1, _ in tiles]
-    if kept and (not strict or max(a1 - a0 for a0, a1, _ in kept) <= tiles[0][1] - tiles[0][0]):
-        return kept                    # the tiling of forward, with the edges it kept (None where the strip kernels did not apply)
-    return tiles
+def _keep_sym_values(sym_blocks, K):
+    """Every row block of the triangle gets its rows of the finished K (r0:r1 against the columns from r0 on)."""
+    Kd = K.detach()
+    for blk in sym_blocks:
+        blk.K = Kd[blk.r0:blk.r1, blk.r0:]
 
 
 def _sym_triangle_ok(be, static_kernel, Xd, dyadic, naive):
@@ -608,12 +662,12 @@ def _same_storage(Xd, Yd):
     return Xd.shape == Yd.shape and Xd.data_ptr() == Yd.data_ptr() and Xd.stride() == Yd.stride()
 
 
-def _sym_fused_gradient(be, static_kernel, Xd, go, dyadic, naive, sym_blocks, budget, Kvals=None):
+def _sym_fused_gradient(be, static_kernel, Xd, go, dyadic, naive, sym_blocks, budget):
     """dL/dX of compute_Gram(X, X, sym=True) from the triangular row blocks through the FUSED RBF adjoint with the
     second-argument sums (sk_rbf_adjoint_fused_f64 with ypart): per row block r0:r1 ONE launch over the solved pairs
     (a in r0:r1, b >= r0) gives the first-argument rows r0:r1 and, per pair, the sums that what the unsolved mirror pairs
     (b, a), b >= r1, owe to rows r1: is folded from (d1 K(x_b, x_a) = d2 K(x_a, x_b): the scheme is symmetric).  Neither the
-    increments nor W exist in HBM, and exploding pairs are rescued on the device (Kvals: the forward's (A, A) values).  None when
+    increments nor W exist in HBM, and exploding pairs are rescued on the device (each block's K: its rows of the forward's values).  None when
     the kernel does not cover the case or the forward kept no edges; the caller then takes the unfused triangular route."""
     if not (type(static_kernel) is RBFKernel and _route(be, OP_ADJOINT, static_kernel, Xd, Xd, dyadic, naive, True) == FUSED
             and Xd.dtype == torch.float64 and hasattr(be, "second_argument_gradient")):
@@ -621,18 +675,19 @@ def _sym_fused_gradient(be, static_kernel, Xd, go, dyadic, naive, sym_blocks, bu
     A, M = Xd.shape[0], Xd.shape[1]
     sigma = float(static_kernel.sigma)
     grad = torch.zeros_like(Xd)
-    for r0, r1, kept in sym_blocks:
-        if not kept or len(kept) != 1 or kept[0][2] is None or kept[0][:2] != (0, r1 - r0):
+    for blk in sym_blocks:
+        r0, r1 = blk.r0, blk.r1
+        edges = blk.whole_edges(r1 - r0)
+        if edges is None:
             return None
         Xc = Xd[r0:].contiguous()
         nb = Xc.shape[0]
         # rows per launch by the memory of the second-argument sums (48 bytes per pair and node column)
         per_row = 64 * nb * (M + 16)
-        edges = kept[0][2]
         per = edges.numel() // (r1 - r0)
         for a0, a1 in _tiles(r1 - r0, per_row, budget):
             Xt = Xd[r0 + a0:r0 + a1].contiguous()
-            Kt = None if Kvals is None else Kvals[r0 + a0:r0 + a1, r0:]
+            Kt = None if blk.K is None else blk.K[a0:a1]
             res = be.rbf_adjoint_fused(Xt, Xc, sigma, dyadic, edges[a0 * per:a1 * per], go[r0 + a0:r0 + a1, r0:].reshape(-1).contiguous(),
                                        gram=True, yside=r1 < A, kfinal=Kt, naive=naive)
             if res is None:
@@ -648,24 +703,24 @@ def _sym_unfused_gradient(be, kind, param, Xd, go, dyadic, naive, sym_blocks, bu
     """The same through sk_static_increments -> sk_solve_adj -> sk_static_adjoint (first argument) + sk_static_adjoint2 (second
     argument of the SAME W, weighted by the transposed upstream gradient); owns the stored-grid rescue."""
     A, M, N = Xd.shape[0], Xd.shape[1], Xd.shape[1]
-    if _upcast_tile(Xd, dyadic) and all(not kept or all(e[2] is None for e in kept) for _, _, kept in sym_blocks):
+    if _upcast_tile(Xd, dyadic) and all(t.edges is None for blk in sym_blocks for t in blk.tiles):
         # fp32 paths at dyadic 2 without kept edges: the whole route in fp64 (see _tile_gradient)
         return _sym_unfused_gradient(be, kind, param, Xd.double(), go.double(), dyadic, naive, sym_blocks, budget).to(Xd.dtype)
     grad_X = torch.zeros_like(Xd)
-    for r0, r1, kept in sym_blocks:
+    for blk in sym_blocks:
+        r0, r1 = blk.r0, blk.r1
         Xr, Xc = Xd[r0:r1].contiguous(), Xd[r0:].contiguous()
         go_blk = go[r0:r1, r0:].contiguous()
         go_t = go[r0:, r0:r1].t().contiguous()         # [a, b] -> upstream gradient of the mirror pair (b, a)
         per_row = 3 * Xc.shape[0] * M * N * Xd.element_size()
-        for a0, a1, edges in _edge_tiles(kept, r1 - r0, per_row, budget):
+        for t in blk.row_tiles(r1 - r0, per_row, budget):
+            a0, a1, edges = t.a0, t.a1, t.edges
             Xt = Xr[a0:a1].contiguous()
-            inc = getattr(edges, "_sk_increments", None) if edges is not None else None      # (what _gram_block kept with the edges)
-            if inc is None or inc.shape[:-2] != (Xt.shape[0], Xc.shape[0]) or inc.dtype != Xt.dtype:
+            inc = t.take_increments(Xt.dtype) if edges is not None else None      # (what _gram_block kept beside the edges)
+            if inc is None:
                 inc = be.static_increments(kind, param, Xt, Xc, True)
             _, W = be.solve_adj(inc, dyadic, naive, edges=edges) if edges is not None else be.solve_adj(inc, dyadic, naive)
             del inc
-            if getattr(edges, "_sk_increments", None) is not None:
-                edges._sk_increments = None
             grad_X[r0 + a0:r0 + a1] += be.static_adjoint(kind, param, Xt, Xc, W, go_blk[a0:a1].contiguous(), True)
             if r1 < A:
                 g2 = be.static_adjoint2(kind, param, Xt, Xc, W, go_t[a0:a1].contiguous(), r1 - r0)
@@ -687,14 +742,13 @@ class _SigKernelGram(torch.autograd.Function):
         ctx.save_for_backward(X, Y)
         ctx.static_kernel, ctx.dyadic_order, ctx._naive_solver = static_kernel, dyadic_order, _naive_solver
         ctx.workspace_bytes = workspace_bytes
-        ctx.sym_blocks = ctx.kept_edges = ctx.K = None
+        ctx.sym_blocks = ctx.kept = None
         if M < 2 or N < 2 or A == 0 or B == 0:   # single points: k = 1; an empty batch: an empty matrix
             return torch.ones(A, B, dtype=X.dtype, device=X.device)
         Xd, Yd = X.detach(), Y.detach()
         need, need_y = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])      # (not need: see _SigKernel.forward)
         # `sym`: the reference's GPU path ignores it (sigkernel.py:366-382) and its CPU path silently assumes X is Y.
         # Here it halves the work when that assumption can be checked (same storage) and no gradient is needed.
-        ctx.sym_blocks = None
         if sym and _same_storage(Xd, Yd):
             if not need and not need_y:
                 return _gram_symmetric(be, static_kernel, Xd.contiguous(), dyadic_order, _naive_solver, workspace_bytes)
@@ -706,17 +760,18 @@ class _SigKernelGram(torch.autograd.Function):
                 ctx.sym_blocks = []
                 K = _gram_symmetric(be, static_kernel, Xd.contiguous(), dyadic_order, _naive_solver, workspace_bytes,
                                     ctx.sym_blocks)
-                ctx.K = K.detach()
+                _keep_sym_values(ctx.sym_blocks, K)
                 return K
         fused = _fused_static(static_kernel, True) is not None
         # with a gradient pending, tile like backward will, so that the caching allocator can reuse the same blocks
         rows_factor = (3 if fused else 8) if need else None
-        ctx.kept_edges = [] if need else None
-        K = _gram_block(be, static_kernel, Xd, Yd, dyadic_order, _naive_solver, workspace_bytes, rows_factor, ctx.kept_edges)
+        ctx.kept = _Kept() if need else None
+        K = _gram_block(be, static_kernel, Xd, Yd, dyadic_order, _naive_solver, workspace_bytes, rows_factor, ctx.kept)
         if sym and _same_storage(Xd, Yd):   # all pairs were solved (fused adjoint ahead): still hand back an exactly symmetric matrix
             iu = torch.triu_indices(A, A, offset=1, device=K.device)
             K[iu[1], iu[0]] = K[iu[0], iu[1]]
-        ctx.K = K.detach() if need else None     # forward values: what arms the fused adjoints' device-side rescue
+        if need:
+            ctx.kept.K = K.detach()     # forward values: what arms the fused adjoints' device-side rescue
         return K
 
     @staticmethod
@@ -726,7 +781,8 @@ class _SigKernelGram(torch.autograd.Function):
         be = _lib.get_backend()
         A, B, M, N = X.shape[0], Y.shape[0], X.shape[1], Y.shape[1]
         grad_X = None
-        if M >= 2 and N >= 2 and getattr(ctx, "sym_blocks", None):
+        sym_blocks = _take(ctx, "sym_blocks")
+        if M >= 2 and N >= 2 and sym_blocks:
             # compute_Gram(X, X, sym=True): per row block r0:r1 the pairs (a, b >= r0) were solved.  Their first-argument
             # contraction gives rows r0:r1; the second-argument contraction of the SAME W, weighted by the transposed
             # upstream gradient, gives what the unsolved mirror pairs (b, a), b >= r1, owe to rows r1: (K is symmetric, so
@@ -735,17 +791,15 @@ class _SigKernelGram(torch.autograd.Function):
             go = grad_output.to(X.dtype).contiguous()
             kind, param = _fused_static(sk, True)
             budget = _budget(X.device, ctx.workspace_bytes)
-            g_fused = _sym_fused_gradient(be, sk, Xd, go, d, naive, ctx.sym_blocks, budget, getattr(ctx, "K", None))
+            g_fused = _sym_fused_gradient(be, sk, Xd, go, d, naive, sym_blocks, budget)
             if g_fused is not None:
                 grad_X = g_fused
             else:
-                grad_X = _sym_unfused_gradient(be, kind, param, Xd, go, d, naive, ctx.sym_blocks, budget)
-            ctx.sym_blocks = None
+                grad_X = _sym_unfused_gradient(be, kind, param, Xd, go, d, naive, sym_blocks, budget)
         elif M >= 2 and N >= 2 and A > 0 and B > 0:
             go = grad_output.to(X.dtype).contiguous()
-            kept, ctx.kept_edges = getattr(ctx, "kept_edges", None), None
-            grad_X = _rows_gradient(be, sk, X.detach().contiguous(), Y.detach().contiguous(), go, d, naive, True, kept,
-                                    ctx.workspace_bytes, getattr(ctx, "K", None))
+            grad_X = _rows_gradient(be, sk, X.detach().contiguous(), Y.detach().contiguous(), go, d, naive, True, _take(ctx),
+                                    ctx.workspace_bytes)
         # the reference doubles the gradient when Y requires grad (written for compute_Gram(X, X) with a
         # symmetric grad_output, sigkernel.py:410-412) and never returns a gradient for Y
         if grad_X is None:
@@ -1088,6 +1142,19 @@ def _loss_weights(A, B, dtype, device, max_cached=16):
     return w
 
 
+class _LossLaunch(NamedTuple):
+    """What the one-launch loss forward (csrc/sk_loss.hip) leaves for its adjoint launch."""
+    fused: tuple       # (kind, param) of the static kernel
+    out: torch.Tensor       # the rectangle's values, then the triangle's
+    edges: torch.Tensor
+    staged: tuple      # (Zr, Zt, Zr_adj): [X; Y] as the kernels read it
+    wb: torch.Tensor        # d value / dK of the rectangle's pairs
+    A: int
+    B: int
+    M: int
+    Yd: torch.Tensor
+
+
 class _SigKernelLoss(torch.autograd.Function):
     """K_XX_m - 2 mean(K_XY) [+ K_YY_m] for TRAINING-SIZED batches: the value the reference's compute_mmd / compute_scoring_rule /
     compute_expected_scoring_rule (sigkernel.py:146-197) assemble from three (two) compute_Gram calls, from ONE Gram block
@@ -1107,7 +1174,7 @@ class _SigKernelLoss(torch.autograd.Function):
         A, B = X.shape[0], Y.shape[0]
         Xd, Yd = X.detach().contiguous(), Y.detach().contiguous()
         ctx.static_kernel, ctx.dyadic_order, ctx._naive_solver, ctx.workspace_bytes = static_kernel, dyadic_order, _naive_solver, workspace_bytes
-        ctx.kept_edges = ctx.K = ctx.launch = None
+        ctx.kept = ctx.launch = None
         need = ctx.needs_input_grad[0]
         fast = _loss_launch_ok(be, static_kernel, Xd, Yd, dyadic_order, _naive_solver, need, with_yy, workspace_bytes)
         if fast is not None:
@@ -1118,7 +1185,7 @@ class _SigKernelLoss(torch.autograd.Function):
                 val, out, edges, staged, wb = res
                 if need:
                     ctx.save_for_backward(X)
-                    ctx.launch = (fast, out, edges, staged, wb, A, B, Xd.shape[1], Yd)
+                    ctx.launch = _LossLaunch(fast, out, edges, staged, wb, A, B, Xd.shape[1], Yd)
                 return val
         Z = torch.cat((Xd, Yd))
         wf, wb, wy = _loss_weights(A, B, X.dtype, X.device)
@@ -1129,15 +1196,15 @@ class _SigKernelLoss(torch.autograd.Function):
         # 0.305 / 0.534 / 1.29 ms forked against 0.309 / 0.561 / 1.28 on one stream at 32 / 64 / 128 paths, tools/experiments/r04_merged_fork.py)
         K_YY = _gram_symmetric(be, static_kernel, Yd, dyadic_order, _naive_solver, workspace_bytes) if with_yy else None
         fused = _fused_static(static_kernel, True) is not None
-        ctx.kept_edges = [] if need else None
+        ctx.kept = _Kept() if need else None
         K_XZ = _gram_block(be, static_kernel, Xd, Z, dyadic_order, _naive_solver, workspace_bytes, (3 if fused else 8) if need else None,
-                           ctx.kept_edges)
+                           ctx.kept)
         val = (K_XZ * wf).sum()
         if with_yy:
             val = val + (K_YY * wy).sum()
         if need:
             ctx.save_for_backward(X, Z)
-            ctx.K, ctx.wb = K_XZ, wb
+            ctx.kept.K, ctx.wb = K_XZ, wb
         return val
 
     @staticmethod
@@ -1148,27 +1215,26 @@ class _SigKernelLoss(torch.autograd.Function):
             # arrays the forward staged and the edges it kept; the upstream scalar stays on the device and multiplies the fold of the
             # partial sums into dL/dX (the adjoint is linear in it): screen + sweep + rescue + fold, four launches
             (X,) = ctx.saved_tensors
-            (kind, param), out, edges, (Zr, Zt, Zr_adj), wb, A, B, M, Yd = ctx.launch
+            L = ctx.launch      # (not taken off: the staged arrays serve every backward through a retained graph)
+            (kind, param), (Zr, Zt, Zr_adj), wb, A, B = L.fused, L.staged, L.wb, L.A, L.B
             Xd = X.detach().contiguous()
             gs = grad_output.detach().to(torch.float64).contiguous()
             adj = be.linear_adjoint_fused if kind == 0 else be.rbf_adjoint_fused
-            res = adj(Xd, None, param, ctx.dyadic_order, edges, wb, gram=True, kfinal=out[:A * (A + B)], naive=ctx._naive_solver,
-                      staged=(Zr_adj, Zt, A + B, M), gscale=gs)
+            res = adj(Xd, None, param, ctx.dyadic_order, L.edges, wb, gram=True, kfinal=L.out[:A * (A + B)], naive=ctx._naive_solver,
+                      staged=(Zr_adj, Zt, A + B, L.M), gscale=gs)
             if res is None:
                 # sk_route_query named the one-band adjoint for this shape and its launcher declined all the same (a scope or workspace
                 # check the query does not mirror): like every other gradient route, fall back -- the rows' gradient from the paths
                 # (its own forward sweep; the kept edges are of no use to the streaming kernels) with the same weights
                 go = (wb.view(A, A + B) * gs).contiguous()
-                g = _rows_gradient(be, ctx.static_kernel, Xd, torch.cat((Xd, Yd)), go, ctx.dyadic_order, ctx._naive_solver, True, None,
-                                   ctx.workspace_bytes, None)
+                g = _rows_gradient(be, ctx.static_kernel, Xd, torch.cat((Xd, L.Yd)), go, ctx.dyadic_order, ctx._naive_solver, True, None,
+                                   ctx.workspace_bytes)
                 return g, None, None, None, None, None, None
             return res[0], None, None, None, None, None, None
         X, Z = ctx.saved_tensors
         go = (ctx.wb * grad_output.to(X.dtype)).contiguous()
-        kept, ctx.kept_edges = ctx.kept_edges, None
-        grad_X = _rows_gradient(be, ctx.static_kernel, X.detach().contiguous(), Z, go, ctx.dyadic_order, ctx._naive_solver, True, kept,
-                                ctx.workspace_bytes, ctx.K)
-        ctx.K = None
+        grad_X = _rows_gradient(be, ctx.static_kernel, X.detach().contiguous(), Z, go, ctx.dyadic_order, ctx._naive_solver, True, _take(ctx),
+                                ctx.workspace_bytes)
         return grad_X, None, None, None, None, None, None
 
 

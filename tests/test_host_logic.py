@@ -69,9 +69,9 @@ def test_symmetric_gram_triangular_blocks_with_gradient(oracle_backend, name, mo
         step = -(-A // 3)
         for r0 in range(0, A, step):
             r1 = min(r0 + step, A)
-            kept = []
+            kept = S._Kept(r0, r1)
             blk = S._gram_block(be, static_kernel, Xd[r0:r1].contiguous(), Xd[r0:].contiguous(), dyadic_order, naive, workspace_bytes, 3, kept)
-            keep_blocks.append((r0, r1, kept))
+            keep_blocks.append(kept)
             K[r0:r1, r0:] = blk
             if r1 < A:
                 K[r1:, r0:r1] = blk[:, r1 - r0:].t()
