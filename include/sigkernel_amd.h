@@ -223,6 +223,23 @@ int sk_static_adjoint_f64(int kind, double param, const double *X, const double 
 int sk_static_adjoint_f32(int kind, double param, const float *X, const float *Y, const float *W, int64_t ldw,
                           const float *scale, int64_t A, int64_t B, int M, int N, int D, float *out, void *stream);
 
+/* sk_static_adjoint_f64 for RBFKernel with the bandwidth's gradient from the same launch (k_static_rbf_adj's parameter mode: per node
+ * the kernel already holds c = scale_p dL/dG[m][n] G[m][n] and r2 = |x_m - y_n|^2; dG/dsigma = G r2 / sigma^2).  An added entry: the
+ * version number stays.  fp64; kind 1 and D <= 32 only (kind 0, D > 32: SK_ERR_UNSUPPORTED; the caller differentiates the static
+ * kernel itself there).  Arguments up to D as for sk_static_adjoint_f64.
+ *   out_dX [A,M,D] = dL/dX, bit for bit what sk_static_adjoint_f64 gives from k_static_rbf_adj (for 17 <= D <= 32 and N <= 128 that
+ *   entry runs the tiled kernel instead: equal up to rounding);
+ *   out_partials [*n_partials]: one sum of c r2 per block of the launch, every element written;
+ *       dL/dparam = (out_partials[0] + out_partials[1] + ...) / param^2,
+ *   added by the caller in index order -- no atomics, the same bits every time.  The kernel has ONE output pointer: both arrays are
+ *   one allocation, out_partials == out_dX + A M D (anything else: SK_ERR_BAD_ARG).
+ *   *n_partials: how many partials the caller allocated; it must equal what the shape needs.  out_dX == NULL and out_partials == NULL:
+ *   size query, *n_partials receives that number (a function of A, M and D) and nothing is launched.
+ * SK_ERR_BAD_ARG: a null pointer, a wrong count, non-adjacent outputs, param <= 0 -- all refused before any launch. */
+int sk_static_adjoint_param_f64(int kind, double param, const double *X, const double *Y, const double *W, int64_t ldw,
+                                const double *scale, int64_t A, int64_t B, int M, int N, int D, double *out_dX, double *out_partials,
+                                int64_t *n_partials, void *stream);
+
 /* LinearKernel adjoint from pre-differenced paths (the fast route for path dim <= 8; same contraction as
  * sk_static_adjoint_* with kind 0): dYt [Bn][8][ldy] fp64 = y[q+1]-y[q], dimension-major, zero-padded -- the array
  * sk_solve_fwd_linear_* takes; W [P, Mc, ldw]; scale [P] nullable; out [A, Mc, D] = sum_b scale_ab sum_q W[a,b,p,q] dy[b,q,:].

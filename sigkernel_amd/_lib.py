@@ -69,6 +69,8 @@ SIGNATURES = {
     "sk_static_increments_f32": (_int, [_int, ctypes.c_double, _vp, _vp, _i64, _i64, _int, _int, _int, _vp, _i64, _vp]),
     "sk_static_adjoint_f64": (_int, [_int, ctypes.c_double, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
     "sk_static_adjoint_f32": (_int, [_int, ctypes.c_double, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
+    "sk_static_adjoint_param_f64": (_int, [_int, ctypes.c_double, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp,
+                                           ctypes.POINTER(ctypes.c_int64), _vp]),
     "sk_linear_adjoint_f64": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
     "sk_linear_adjoint_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp]),
     "sk_static_adjoint2_f64": (_int, [_int, ctypes.c_double, _vp, _vp, _vp, _int, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _int,
@@ -1430,6 +1432,34 @@ class HipBackend:
             _check(fn(1, float(param), _ptr(X), _ptr(Y), _ptr(W), ldw, _ptr(scale), A, B if gram else 0, M, N, D, _ptr(g),
                       _stream(X)), "sk_static_adjoint")
             return g
+
+    def static_adjoint_param(self, kind, param, X, Y, W, scale, gram):
+        """(dL/dX (A,M,D), dL/dparam, a 0-d fp64 device tensor) of RBFKernel(param) from ONE launch of k_static_rbf_adj in its
+        parameter mode (sk_static_adjoint_param_f64): the block sums of c r2 land behind dX in the same allocation and are added here
+        in index order -- no atomics, the same bits every time.  fp64 paths; None outside the kernel's scope (LinearKernel, more than
+        MAX_FUSED_DIM dims): the caller differentiates the static kernel itself there."""
+        if kind != 1 or X.shape[2] > self.MAX_FUSED_DIM:
+            return None
+        _dev(X, "X")
+        _dev(Y, "Y")
+        if X.dtype != torch.float64:
+            raise ValueError("static_adjoint_param runs on fp64 paths (the exact backward up-casts fp32 ones)")
+        W, ldw = _row_stride(W, "W")
+        A, M, D = X.shape
+        B, N = Y.shape[0], Y.shape[1]
+        if scale is not None:
+            _dev(scale, "scale")
+            if scale.dtype != W.dtype:
+                raise ValueError("scale must have W's dtype")
+        with _device(X.device):
+            fn = load().sk_static_adjoint_param_f64
+            n = ctypes.c_int64(0)
+            shape = (1, float(param), None, None, None, 0, None, A, B if gram else 0, M, N, D)
+            _check(fn(*shape, None, None, ctypes.byref(n), None), "sk_static_adjoint_param")      # size query
+            buf = torch.empty(A * M * D + n.value, dtype=X.dtype, device=X.device)
+            _check(fn(1, float(param), _ptr(X), _ptr(Y), _ptr(W), ldw, _ptr(scale), A, B if gram else 0, M, N, D, _ptr(buf),
+                      buf.data_ptr() + 8 * A * M * D, ctypes.byref(n), _stream(X)), "sk_static_adjoint_param")
+            return buf[:A * M * D].view(A, M, D), buf[A * M * D:].sum() / float(param) ** 2
 
     def static_adjoint2(self, kind, param, X, Y, W, scale, b0=0):
         """dL/dY[b0:] (B-b0, N, D) from W = dL/d inc_c of the Gram pairs (a, b) and the per-pair upstream gradient `scale`

@@ -424,6 +424,23 @@ int sk_static_adjoint_f32(int kind, double param, const float *X, const float *Y
                                         (hipStream_t)stream);
 }
 
+int sk_static_adjoint_param_f64(int kind, double param, const double *X, const double *Y, const double *W, int64_t ldw,
+                                const double *scale, int64_t A, int64_t B, int M, int N, int D, double *out_dX, double *out_partials,
+                                int64_t *n_partials, void *stream) {
+    // argument checks only, before any launch
+    if (!n_partials || A < 0 || B < 0 || M < 2 || N < 2 || D < 1 || (kind != 0 && kind != 1)) return SK_ERR_BAD_ARG;
+    if (kind == 0 || D > 32) return SK_ERR_UNSUPPORTED;
+    const int64_t need = static_adjoint_param_partials(A, M, D);
+    if (!out_dX && !out_partials) {      // size query
+        *n_partials = need;
+        return SK_OK;
+    }
+    if (!X || !Y || !W || !out_dX || !out_partials || *n_partials != need) return SK_ERR_BAD_ARG;
+    if ((ldw != 0 && ldw < N - 1) || !(param > 0) || out_partials != out_dX + A * (int64_t)M * D) return SK_ERR_BAD_ARG;
+    if (A == 0) return SK_OK;
+    return launch_static_adjoint_param(param, X, Y, W, ldw ? ldw : N - 1, scale, A, B, M, N, D, out_dX, (hipStream_t)stream);
+}
+
 int sk_linear_adjoint_f64(const double *dYt, int64_t ldy, const double *W, int64_t ldw, const double *scale, int64_t A,
                           int64_t B, int Mc, int Nc, int D, double *out, void *stream) {
     if (!dYt || !W || !out || A < 0 || B < 0 || Mc < 1 || Nc < 1 || D < 1 || ldy < Nc || (ldw != 0 && ldw < Nc)) return SK_ERR_BAD_ARG;

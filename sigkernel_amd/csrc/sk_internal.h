@@ -331,6 +331,12 @@ template <typename T>
 int launch_static_adjoint(int kind, double param, const T *X, const T *Y, const T *W, int64_t ldw, const T *scale, int64_t A,
                           int64_t B, int M, int N, int D, T *out, hipStream_t s);
 
+// RBF, D <= 32, fp64: dL/dX [A, M, D] and, directly behind it, the n_partials block sums of c r2 (k_static_rbf_adj's parameter mode);
+// dL/dsigma = their sum / sigma^2.  static_adjoint_param_partials: how many there are, 0 where the mode has no kernel (D > 32).
+int64_t static_adjoint_param_partials(int64_t A, int M, int D);
+int launch_static_adjoint_param(double param, const double *X, const double *Y, const double *W, int64_t ldw, const double *scale,
+                                int64_t A, int64_t B, int M, int N, int D, double *out, hipStream_t s);
+
 template <typename T>
 int launch_linear_adjoint_dyt(const double *dYt, int64_t ldy, const T *W, int64_t ldw, const T *scale, int64_t A, int64_t B,
                               int Mc, int Nc, int D, T *out, hipStream_t s);

@@ -464,6 +464,12 @@ __global__ __launch_bounds__(NT) void k_linear_adj_dyt(const double *__restrict_
 // One block per (path a, RM consecutive node rows): thread = node column n; per pair b the thread loads its y node
 // once for the RM rows, and RM + 1 rows of W (t_r = W[r][n] - W[r][n-1], dG[m,n] = t_m - t_{m-1}) instead of 4 W values
 // per node -- the first version (one row per block) re-read every W row twice and every y node RM times more often.
+// Parameter mode (row_groups passed NEGATED; wave-uniform, like SK_FLAG_DISCRETE / _RAGGED / _SOURCES a mode of arguments the kernel
+// already has): the bandwidth's gradient from the same two numbers per node.  G = exp(-r2 / sigma), dG/dsigma = G r2 / sigma^2, so
+//      dL/dsigma = sigma^-2 sum_{a,m} sum_b s_ab sum_n dG[m,n] G[m,n] r2[m,n] = sigma^-2 sum c r2,
+// r2 the distance the exponent is formed from.  Every thread keeps ONE more accumulator, cq += c r2 over its nodes of all RM rows; the
+// block's sum goes to element blockIdx.x BEHIND the A M D elements of gX (the caller allocates A M D + A row_groups and adds the
+// partials in index order: no atomics, the same bits every time).  With the mode off nothing is stored there and dX keeps its bits.
 template <typename T, int DMAX, int NT, int RM>
 // (fp64, 17..32 dims: 260 VGPRs, one wave per SIMD.  Held to 256 -- two waves -- it is SLOWER, 12.1 -> 13.0 ms per 256 x 256 pairs of 64
 // points at dim 20, profiles/r06_wide_dims.txt: the kernel is bound by what it re-reads from L2 -- every block streams all of Y -- not by latency)
@@ -473,9 +479,11 @@ __global__ __launch_bounds__(NT) void k_static_rbf_adj(const T *__restrict__ X, 
                                                        T *__restrict__ gX) {
     __shared__ double red[NT / 64 + 1];
     const int Mc = M - 1, Nc = N - 1;
+    const bool pmode = row_groups < 0;      // parameter mode: the block's sum of c r2 goes behind dX
+    if (pmode) row_groups = -row_groups;
     const int64_t a = blockIdx.x / row_groups;
     const int m0 = (int)(blockIdx.x % row_groups) * RM;
-    double xm[RM][DMAX], xs[RM], acc[RM][DMAX], cs[RM];
+    double xm[RM][DMAX], xs[RM], acc[RM][DMAX], cs[RM], cq = 0.0;
 #pragma unroll
     for (int r = 0; r < RM; ++r) {
         cs[r] = 0.0;
@@ -529,9 +537,11 @@ __global__ __launch_bounds__(NT) void k_static_rbf_adj(const T *__restrict__ X, 
 #pragma unroll
             for (int k = 0; k < DMAX; ++k) xy = fma(xm[r][k], yn[k], xy);
             // rbf: dist = -2 xy + (xs + ys) as the reference forms it (static_kernels.py:70-73); G = exp(-dist / sigma)
-            const double g = exp_nonpos(-(fma(-2.0, xy, xs[r] + ys)) * inv_sigma);   // (a rounding-size positive argument is fine)
+            const double dist = fma(-2.0, xy, xs[r] + ys);
+            const double g = exp_nonpos(-dist * inv_sigma);   // (a rounding-size positive argument is fine)
             const double c = (m0 + r < M ? s : 0.0) * (t[r + 1] - t[r]) * g;
             cs[r] += c;
+            cq = fma(c, dist, cq);      // (parameter mode's sum; one fma per node, kept out of every value dX is formed from)
 #pragma unroll
             for (int k = 0; k < DMAX; ++k) acc[r][k] = fma(c, dk[k], acc[r][k]);
         }
@@ -558,6 +568,10 @@ __global__ __launch_bounds__(NT) void k_static_rbf_adj(const T *__restrict__ X, 
             const double v = block_sum<NT>(fma(xm[r][k] - xm[0][k], cs[r], -acc[r][k]), red);
             if (threadIdx.x == 0 && k < D && m0 + r < M) gX[(a * M + m0 + r) * (int64_t)D + k] = (T)(-2.0 * inv_sigma * v);
         }
+    if (pmode) {      // (wave-uniform: every thread of the block takes part in the sum)
+        const double v = block_sum<NT>(cq, red);
+        if (threadIdx.x == 0) gX[(int64_t)(gridDim.x / row_groups) * M * D + blockIdx.x] = (T)v;
+    }
 }
 
 // ---- second-argument adjoints (Gram only): dL/dY from W, for the pairs (a, b) with b >= b0 ---------------------------
@@ -993,36 +1007,41 @@ int launch_static_rbf_adj_tiled(double param, const T *X, const T *Y, const T *W
     return check_launch();
 }
 
+// node rows per block of k_static_rbf_adj (RM * DMAX accumulators per thread)
+constexpr int static_adj_rows(int DMAX) { return DMAX <= 8 ? 4 : DMAX == 16 ? 2 : 1; }
+
 template <typename T, int DMAX, int NT>
 int launch_static_adj_d(int kind, double param, const T *X, const T *Y, const T *W, int64_t ldw, const T *scale, int64_t A,
-                        int64_t B, int M, int N, int D, T *out, hipStream_t s) {
+                        int64_t B, int M, int N, int D, T *out, hipStream_t s, bool pmode = false) {
     // (kind 0, the LINEAR static kernel: its contraction T[a] = sum_b W[a, b] dY[b] runs from pre-differenced, dimension-major paths in
     // sk_linear_adjoint_* for dim <= 8 and in k_static_linear_adj_tiled for 9..32 dims, see launch_static_adjoint)
     if (kind == 0) {
         return SK_ERR_UNSUPPORTED;
     } else {
-        constexpr int RM = DMAX <= 8 ? 4 : DMAX == 16 ? 2 : 1;   // node rows per block (RM * DMAX accumulators per thread)
+        constexpr int RM = static_adj_rows(DMAX);
         const int row_groups = (M + RM - 1) / RM;
         const int64_t blocks = A * row_groups;
         if (blocks > 0x7fffffffLL) return SK_ERR_UNSUPPORTED;
+        // (pmode: the kernel's parameter mode travels as the sign of row_groups; out then holds A M D + blocks elements)
         SK_LAUNCH((k_static_rbf_adj<T, DMAX, NT, RM>), dim3((unsigned)blocks), dim3(NT), 0, s, X, Y, W, ldw, scale, B,
-                           M, N, D, 1.0 / param, row_groups, out);
+                           M, N, D, 1.0 / param, pmode ? -row_groups : row_groups, out);
     }
     return check_launch();
 }
 
 template <typename T, int DMAX>
 int launch_static_adj_nt(int kind, double param, const T *X, const T *Y, const T *W, int64_t ldw, const T *scale, int64_t A,
-                         int64_t B, int M, int N, int D, T *out, hipStream_t s) {
+                         int64_t B, int M, int N, int D, T *out, hipStream_t s, bool pmode = false) {
     if constexpr (DMAX >= 24) {     // 17..32 dims: the y points of a pair through LDS, shared by eight rows' waves (k_static_rbf_adj_tiled;
-        if (kind == 1 && N <= ADJT_NMAX) {      // at 16 dims it is no faster than two rows per thread: 1.87 / 1.66 against 1.80 ms, r06_lin_adj.txt)
+        if (kind == 1 && N <= ADJT_NMAX && !pmode) {      // at 16 dims it is no faster than two rows per thread: 1.87 / 1.66 against 1.80 ms, r06_lin_adj.txt)
             if (N <= 64) return launch_static_rbf_adj_tiled<T, DMAX, 1>(param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);
             return launch_static_rbf_adj_tiled<T, DMAX, 2>(param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);
         }
-        return launch_static_adj_d<T, DMAX, 128>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);
+        // (the parameter mode lives in k_static_rbf_adj alone: with it pending a short second path leaves the tiled kernel too)
+        return launch_static_adj_d<T, DMAX, 128>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s, pmode);
     } else {
-        if (N <= 80) return launch_static_adj_d<T, DMAX, 64>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);
-        return launch_static_adj_d<T, DMAX, 128>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);
+        if (N <= 80) return launch_static_adj_d<T, DMAX, 64>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s, pmode);
+        return launch_static_adj_d<T, DMAX, 128>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s, pmode);
     }
 }
 
@@ -1381,6 +1400,22 @@ int launch_static_adjoint(int kind, double param, const T *X, const T *Y, const 
     if (D <= 32) return launch_static_adj_nt<T, 32>(kind, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s);
     constexpr int64_t q = 128 / sizeof(T);
     return launch_static_wide<T>(WIDE_RBF_ADJ, param, X, Y, A, B, M, N, D, out, (N + q - 1) / q * q, W, ldw, scale, s);
+}
+
+int64_t static_adjoint_param_partials(int64_t A, int M, int D) {
+    if (D < 1 || D > 32 || M < 1 || A < 0) return 0;
+    const int RM = static_adj_rows(D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : D <= 24 ? 24 : 32);
+    return A * ((M + RM - 1) / RM);
+}
+
+int launch_static_adjoint_param(double param, const double *X, const double *Y, const double *W, int64_t ldw, const double *scale,
+                                int64_t A, int64_t B, int M, int N, int D, double *out, hipStream_t s) {
+    if (D <= 4) return launch_static_adj_nt<double, 4>(1, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s, true);
+    if (D <= 8) return launch_static_adj_nt<double, 8>(1, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s, true);
+    if (D <= 16) return launch_static_adj_nt<double, 16>(1, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s, true);
+    if (D <= 24) return launch_static_adj_nt<double, 24>(1, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s, true);
+    if (D <= 32) return launch_static_adj_nt<double, 32>(1, param, X, Y, W, ldw, scale, A, B, M, N, D, out, s, true);
+    return SK_ERR_UNSUPPORTED;
 }
 
 // out: T [A, Mc, D] (the caller differences it along the path and applies scale^2)

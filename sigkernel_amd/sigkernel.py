@@ -112,9 +112,25 @@ def _fused_static(static_kernel, gram):
     if type(static_kernel) is LinearKernel:
         # the reference's Gram_matrix ignores `scale`, batch_kernel applies it to both arguments (static_kernels.py:24,33)
         return 0, (1.0 if gram else float(static_kernel.scale))
-    if type(static_kernel) is RBFKernel and float(static_kernel.sigma) > 0:
-        return 1, float(static_kernel.sigma)
+    if type(static_kernel) is RBFKernel:
+        # (a tensor sigma is read as its value here; its gradient, where one is pending, is _static_params' business)
+        sigma = static_kernel.sigma
+        sigma = float(sigma.detach()) if isinstance(sigma, torch.Tensor) else float(sigma)
+        if sigma > 0:
+            return 1, sigma
     return None
+
+
+def _static_params(static_kernel):
+    """The static kernel's own tensors that require grad -- what SigKernel(exact_gradient=True) differentiates besides the paths:
+    exactly RBFKernel: its ``sigma`` when that is a one-element tensor requiring grad; any static kernel that is a torch.nn.Module:
+    its parameters that require grad; anything else: none."""
+    if type(static_kernel) is RBFKernel:
+        s = static_kernel.sigma
+        return (s,) if isinstance(s, torch.Tensor) and s.numel() == 1 and s.requires_grad else ()
+    if isinstance(static_kernel, torch.nn.Module):
+        return tuple(p for p in static_kernel.parameters() if p.requires_grad)
+    return ()
 
 
 STREAM, FUSED, FUSED_MB, FUSED_MB_SWAP = _lib.ROUTE_STREAM, _lib.ROUTE_FUSED, _lib.ROUTE_FUSED_MB, _lib.ROUTE_FUSED_MB_SWAP
@@ -809,8 +825,22 @@ class _SigKernelGram(torch.autograd.Function):
         return grad_X, None, None, None, None, None, None
 
 
-def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need_y, cells=None, sources=None):
-    """(dL/dX, dL/dY) of one tile under exact_gradient=True (None where not needed): increments -> sk_solve_adj_* with SK_FLAG_DISCRETE
+def _exact_static_route(be, static_kernel, gram, dim, params):
+    """How _exact_tile runs the chain rule through the static kernel: "fused" (sk_static_adjoint_* / sk_static_adjoint2_*), "param" (the
+    same with dL/dsigma from k_static_rbf_adj's parameter mode: RBFKernel.sigma pending, a backend with static_adjoint_param, at most
+    its MAX_FUSED_DIM dims) or "generic" (the static kernel in torch and one vector-Jacobian product)."""
+    fused = _fused_static(static_kernel, gram)
+    if fused is None or not hasattr(be, "static_adjoint"):
+        return "generic"
+    if not params:
+        return "fused"
+    if fused[0] == 1 and hasattr(be, "static_adjoint_param") and dim <= getattr(be, "MAX_FUSED_DIM", 0):
+        return "param"
+    return "generic"
+
+
+def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need_y, cells=None, sources=None, params=()):
+    """(dL/dX, dL/dY, [dL/dparam ...]) of one tile under exact_gradient=True (None where not needed): increments -> sk_solve_adj_* with SK_FLAG_DISCRETE
     (W = the exact derivative of the solver's value with respect to every coarse increment) -> the chain rule through the static
     kernel for BOTH arguments, from the same W.
 
@@ -825,7 +855,13 @@ def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need
 
     sources (prefix calls, in place of go: pass go=None): S (a, B, M - 1, N - 1) for a Gram tile, (a, M - 1, N - 1) paired -- dL/d(prefix
     kernel) of every coarse node (m, n), m, n >= 1, of every pair.  They go with the launch (SK_FLAG_SOURCES): W is then dL/d(increments)
-    itself, and the chain rule below runs with a unit upstream weight."""
+    itself, and the chain rule below runs with a unit upstream weight.
+
+    params (_static_params: the static kernel's tensors with a gradient pending): their gradients come back as the third result, one
+    fp64 tensor each.  RBFKernel.sigma up to 32 dims: ONE k_static_rbf_adj launch in its parameter mode gives dL/dX and dL/dsigma
+    (be.static_adjoint_param), whether or not X needs its gradient.  Every other case -- RBF beyond 32 dims, torch.nn.Module kernels, a
+    backend without that method -- is the generic branch with the parameters among the inputs of its one vector-Jacobian product; a
+    parameter the static kernel does not use gets zeros."""
     more = {}
     if sources is not None:
         more["sources"] = sources
@@ -838,13 +874,22 @@ def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need
             more["cells"] = torch.stack((cx, cy), dim=-1).contiguous()
     fused = _fused_static(static_kernel, gram)
     inc = None
-    if fused is not None and hasattr(be, "static_adjoint"):
+    route = _exact_static_route(be, static_kernel, gram, Xt.shape[2], params)
+    one_launch = route == "param"
+    if route != "generic":
         inc = be.static_increments(fused[0], fused[1], Xt, Yt, gram)
     if inc is not None:
         kind, param = fused
         _, W = be.solve_adj(inc, dyadic, naive, discrete=True, **more)
         del inc
-        gx = be.static_adjoint(kind, param, Xt, Yt, W, go, gram) if need_x else None
+        gp = []
+        if one_launch:
+            gx, dparam = be.static_adjoint_param(kind, param, Xt, Yt, W, go, gram)
+            gp = [dparam]
+            if not need_x:
+                gx = None
+        else:
+            gx = be.static_adjoint(kind, param, Xt, Yt, W, go, gram) if need_x else None
         gy = None
         if need_y:
             if gram and hasattr(be, "static_adjoint2"):
@@ -852,54 +897,68 @@ def _exact_tile(be, static_kernel, Xt, Yt, go, dyadic, naive, gram, need_x, need
             if gy is None:
                 Wt = (W.transpose(0, 1) if gram else W).transpose(-1, -2).contiguous()     # the pair (b, a), cells (j, i)
                 gy = be.static_adjoint(kind, param, Yt, Xt, Wt, go.t().contiguous() if gram else go, gram)
-        return gx, gy
+        return gx, gy, gp
     Xg, Yg = Xt.clone().requires_grad_(need_x), Yt.clone().requires_grad_(need_y)
     with torch.enable_grad():
         G = static_kernel.Gram_matrix(Xg, Yg) if gram else static_kernel.batch_kernel(Xg, Yg)
     _, W = be.solve_adj(be.increments(G.detach().contiguous()), dyadic, naive, discrete=True, **more)
     dG = be.increments_adjoint(W, go)
     del W
-    wrt = [t for t, need in ((Xg, need_x), (Yg, need_y)) if need]
+    wrt = [t for t, need in ((Xg, need_x), (Yg, need_y)) if need] + list(params)
     grads = list(torch.autograd.grad(G, wrt, dG, allow_unused=True))
     gx = (grads.pop(0) if need_x else None)
     gy = (grads.pop(0) if need_y else None)
-    return (torch.zeros_like(Xt) if need_x and gx is None else gx), (torch.zeros_like(Yt) if need_y and gy is None else gy)
+    gp = [torch.zeros(p.shape, dtype=torch.float64, device=Xt.device) if g is None else g.detach().to(device=Xt.device, dtype=torch.float64)
+          for p, g in zip(params, grads)]
+    return (torch.zeros_like(Xt) if need_x and gx is None else gx), (torch.zeros_like(Yt) if need_y and gy is None else gy), gp
 
 
-def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspace_bytes, need_x, need_y, cells=None, sources=None):
-    """(dL/dX, dL/dY) of a Gram block (go (A, B)) or a paired batch (go (A,)) under exact_gradient=True, over row tiles sized like
+def _exact_gradient(be, static_kernel, Xd, Yd, go, dyadic, naive, gram, workspace_bytes, need_x, need_y, cells=None, sources=None,
+                    params=()):
+    """(dL/dX, dL/dY, [dL/dparam ...]) of a Gram block (go (A, B)) or a paired batch (go (A,)) under exact_gradient=True, over row tiles sized like
     _rows_gradient's streaming tiles, with the stored-grid scratch of the discrete adjoint (min(pairs, 1024) slots of two fine grids,
     at most _lib.HipBackend.GRID_SCRATCH_BYTES) taken out of the budget first -- though never more than half of it.  fp32 paths are
     up-cast: the whole backward runs in fp64 and the gradients are rounded to fp32 at the end.  cells (ragged batches): (cx (A,), cy),
     int32 coarse cells of every path, length - 1; each row tile takes its slice (_exact_tile).  sources (prefix calls, in place of go:
     pass go=None): a function (a0, a1) -> the sources of rows a0..a1 in the paths' dtype (_exact_tile), built tile by tile so that nothing
-    of size pairs x M x N outlives a tile; the tiles are those of a call with go."""
+    of size pairs x M x N outlives a tile; the tiles are those of a call with go.  params (_static_params): the static kernel's tensors
+    with a gradient pending; their gradients are the third result, one fp64 tensor of the parameter's element count on the paths' device
+    each (_exact_tile), summed over the row tiles in tile order."""
     if Xd.dtype != torch.float64:
         up = None if sources is None else (lambda a0, a1: sources(a0, a1).double())
-        gx, gy = _exact_gradient(be, static_kernel, Xd.double(), Yd.double(), None if go is None else go.double(), dyadic, naive, gram,
-                                 workspace_bytes, need_x, need_y, cells, up)
-        return (None if gx is None else gx.to(Xd.dtype)), (None if gy is None else gy.to(Yd.dtype))
+        gx, gy, gp = _exact_gradient(be, static_kernel, Xd.double(), Yd.double(), None if go is None else go.double(), dyadic, naive, gram,
+                                     workspace_bytes, need_x, need_y, cells, up, params)
+        return (None if gx is None else gx.to(Xd.dtype)), (None if gy is None else gy.to(Yd.dtype)), gp
     A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
     Bp = Yd.shape[0] if gram else 1
     budget = _budget(Xd.device, workspace_bytes)
     slot = 16 * (((M - 1) << dyadic) + 1) * (((N - 1) << dyadic) + 1)
     scratch = min(min(1024, A * Bp) * slot, getattr(be, "GRID_SCRATCH_BYTES", 2 << 30))
-    fused = _fused_static(static_kernel, gram) is not None
+    fused = _exact_static_route(be, static_kernel, gram, Xd.shape[2], params) != "generic"
     per_row = (3 if fused else 8) * Bp * M * N * Xd.element_size()
     gx = torch.empty_like(Xd) if need_x else None
     gy = torch.zeros_like(Yd) if (need_y and gram) else (torch.empty_like(Yd) if need_y else None)
+    gp = None
     for a0, a1 in _tiles(A, per_row, max(budget - scratch, budget // 2)):
-        tx, ty = _exact_tile(be, static_kernel, Xd[a0:a1].contiguous(), Yd if gram else Yd[a0:a1].contiguous(),
-                             None if go is None else go[a0:a1].contiguous(), dyadic, naive, gram, need_x, need_y,
-                             None if cells is None else (cells[0][a0:a1], cells[1] if gram else cells[1][a0:a1]),
-                             None if sources is None else sources(a0, a1).contiguous())
+        tx, ty, tp = _exact_tile(be, static_kernel, Xd[a0:a1].contiguous(), Yd if gram else Yd[a0:a1].contiguous(),
+                                 None if go is None else go[a0:a1].contiguous(), dyadic, naive, gram, need_x, need_y,
+                                 None if cells is None else (cells[0][a0:a1], cells[1] if gram else cells[1][a0:a1]),
+                                 None if sources is None else sources(a0, a1).contiguous(), params)
+        gp = tp if gp is None else [g + t for g, t in zip(gp, tp)]
         if need_x:
             gx[a0:a1] = tx
         if need_y and gram:
             gy += ty            # every row tile meets every path of Y
         elif need_y:
             gy[a0:a1] = ty
-    return gx, gy
+    return gx, gy, gp
+
+
+def _param_grads(params, gp, needs):
+    """The backward results of the trailing parameter inputs: every gradient in its parameter's shape, dtype and device (gp: what
+    _exact_gradient returned, or None -- one-point paths and empty batches: k = 1 whatever the parameters are)"""
+    return tuple(None if not need else torch.zeros_like(p) if gp is None else g.reshape(p.shape).to(device=p.device, dtype=p.dtype)
+                 for p, g, need in zip(params, gp if gp is not None else params, needs))
 
 
 class _SigKernelExact(torch.autograd.Function):
@@ -909,8 +968,8 @@ class _SigKernelExact(torch.autograd.Function):
     the two contributions."""
 
     @staticmethod
-    def forward(ctx, X, Y, static_kernel, dyadic_order, gram, sym, _naive_solver, workspace_bytes):
-        ctx.save_for_backward(X, Y)
+    def forward(ctx, X, Y, static_kernel, dyadic_order, gram, sym, _naive_solver, workspace_bytes, *params):
+        ctx.save_for_backward(X, Y, *params)
         ctx.args = (static_kernel, dyadic_order, gram, _naive_solver, workspace_bytes)
         if gram:
             return _SigKernelGram.forward(_NoGradCtx(), X, Y, static_kernel, dyadic_order, sym, _naive_solver, workspace_bytes)
@@ -918,15 +977,17 @@ class _SigKernelExact(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        X, Y = ctx.saved_tensors
+        X, Y, *params = ctx.saved_tensors
         static_kernel, d, gram, naive, workspace_bytes = ctx.args
         need_x, need_y = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        gp = None
         if X.shape[1] < 2 or Y.shape[1] < 2 or X.shape[0] == 0 or Y.shape[0] == 0:   # single points / empty batches: k = 1 whatever the paths
             gx, gy = (torch.zeros_like(X) if need_x else None), (torch.zeros_like(Y) if need_y else None)
         else:
-            gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, X.detach().contiguous(), Y.detach().contiguous(),
-                                     grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y)
-        return gx, gy, None, None, None, None, None, None
+            gx, gy, gp = _exact_gradient(_lib.get_backend(), static_kernel, X.detach().contiguous(), Y.detach().contiguous(),
+                                         grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y,
+                                         params=params)
+        return (gx, gy, None, None, None, None, None, None) + _param_grads(params, gp, ctx.needs_input_grad[8:])
 
 
 class _SigKernelRaggedExact(torch.autograd.Function):
@@ -938,17 +999,18 @@ class _SigKernelRaggedExact(torch.autograd.Function):
     (tests/test_gpu_prefix_value_regimes.py)."""
 
     @staticmethod
-    def forward(ctx, X, Y, lx, ly, static_kernel, dyadic_order, gram, _naive_solver, workspace_bytes):
-        ctx.save_for_backward(X, Y, lx, ly)
+    def forward(ctx, X, Y, lx, ly, static_kernel, dyadic_order, gram, _naive_solver, workspace_bytes, *params):
+        ctx.save_for_backward(X, Y, lx, ly, *params)
         ctx.args = (static_kernel, dyadic_order, gram, _naive_solver, workspace_bytes)
         return _prefix_at(_lib.get_backend(), static_kernel, X.detach(), Y.detach(), lx, ly, dyadic_order, _naive_solver, gram,
                           workspace_bytes)
 
     @staticmethod
     def backward(ctx, grad_output):
-        X, Y, lx, ly = ctx.saved_tensors
+        X, Y, lx, ly, *params = ctx.saved_tensors
         static_kernel, d, gram, naive, workspace_bytes = ctx.args
         need_x, need_y = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        gp = None
         if X.shape[1] < 2 or Y.shape[1] < 2 or X.shape[0] == 0 or Y.shape[0] == 0:   # single points / empty batches: k = 1 whatever the paths
             gx, gy = (torch.zeros_like(X) if need_x else None), (torch.zeros_like(Y) if need_y else None)
         else:
@@ -956,11 +1018,11 @@ class _SigKernelRaggedExact(torch.autograd.Function):
             # padding: 0 * (inf - inf) for a padding whose squares or differences overflow, or that is not finite.  So the chain rule
             # runs on the paths padded with their last TRUE point: every true-point sum gains +-0 from the padding, the padding's own
             # gradient is 0 * finite, and a batch of full lengths is handed on as it is.
-            gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, _repeat_last_point(X.detach(), lx).contiguous(),
-                                     _repeat_last_point(Y.detach(), ly).contiguous(),
-                                     grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y,
-                                     (lx - 1, ly - 1))
-        return gx, gy, None, None, None, None, None, None, None
+            gx, gy, gp = _exact_gradient(_lib.get_backend(), static_kernel, _repeat_last_point(X.detach(), lx).contiguous(),
+                                         _repeat_last_point(Y.detach(), ly).contiguous(),
+                                         grad_output.to(X.dtype).contiguous(), d, naive, gram, workspace_bytes, need_x, need_y,
+                                         (lx - 1, ly - 1), params=params)
+        return (gx, gy, None, None, None, None, None, None, None) + _param_grads(params, gp, ctx.needs_input_grad[9:])
 
 
 def _prefix_sources(go, nodes, Mc, Nc):
@@ -990,33 +1052,33 @@ class _SigKernelPrefixExact(torch.autograd.Function):
     zero."""
 
     @staticmethod
-    def forward(ctx, X, Y, static_kernel, dyadic_order, gram, nodes, _naive_solver, workspace_bytes):
-        ctx.save_for_backward(X, Y)
+    def forward(ctx, X, Y, static_kernel, dyadic_order, gram, nodes, _naive_solver, workspace_bytes, *params):
+        ctx.save_for_backward(X, Y, *params)
         ctx.args = (static_kernel, dyadic_order, gram, nodes, _naive_solver, workspace_bytes)
         return _prefix_grid(_lib.get_backend(), static_kernel, X.detach(), Y.detach(), dyadic_order, _naive_solver, gram, workspace_bytes,
                             nodes)
 
     @staticmethod
     def backward(ctx, grad_output):
-        X, Y = ctx.saved_tensors
+        X, Y, *params = ctx.saved_tensors
         static_kernel, d, gram, nodes, naive, workspace_bytes = ctx.args
         need_x, need_y = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
         if X.shape[1] < 2 or Y.shape[1] < 2 or X.shape[0] == 0 or Y.shape[0] == 0:   # single points / empty batches: k = 1 whatever the paths
             gx, gy = (torch.zeros_like(X) if need_x else None), (torch.zeros_like(Y) if need_y else None)
-            return gx, gy, None, None, None, None, None, None
+            return (gx, gy, None, None, None, None, None, None) + _param_grads(params, None, ctx.needs_input_grad[8:])
         Xd, Yd = X.detach(), Y.detach()
         if nodes == "diagonal" and X.shape[1] != Y.shape[1]:
             T = min(X.shape[1], Y.shape[1])
             Xd, Yd = Xd[:, :T], Yd[:, :T]
         Mc, Nc = Xd.shape[1] - 1, Yd.shape[1] - 1
         go = grad_output.to(X.dtype)
-        gx, gy = _exact_gradient(_lib.get_backend(), static_kernel, Xd.contiguous(), Yd.contiguous(), None, d, naive, gram, workspace_bytes,
-                                 need_x, need_y, sources=lambda a0, a1: _prefix_sources(go[a0:a1], nodes, Mc, Nc))
+        gx, gy, gp = _exact_gradient(_lib.get_backend(), static_kernel, Xd.contiguous(), Yd.contiguous(), None, d, naive, gram, workspace_bytes,
+                                     need_x, need_y, sources=lambda a0, a1: _prefix_sources(go[a0:a1], nodes, Mc, Nc), params=params)
         if need_x and gx.shape != X.shape:
             gx = torch.cat((gx, torch.zeros_like(X[:, gx.shape[1]:])), dim=1)
         if need_y and gy.shape != Y.shape:
             gy = torch.cat((gy, torch.zeros_like(Y[:, gy.shape[1]:])), dim=1)
-        return gx, gy, None, None, None, None, None, None
+        return (gx, gy, None, None, None, None, None, None) + _param_grads(params, gp, ctx.needs_input_grad[8:])
 
 
 def _repeat_last_point(P, lens):
@@ -1432,7 +1494,10 @@ class SigKernel:
     values, NaN and inf included -- receives exactly zero.  The prefix methods (``compute_Gram_prefixes`` /
     ``compute_kernel_prefixes`` in every ``nodes`` mode, ``compute_mmd_prefixes``) likewise: one reverse sweep per pair differentiates any
     weighting of a pair's prefix kernels -- a loss over time costs one backward, not one per time.  Not sharded (``process_group`` raises
-    ``NotImplementedError``); ``RBFKernel.sigma`` receives no gradient.
+    ``NotImplementedError``).  The static kernel's own parameters are differentiated too: ``RBFKernel(sigma)`` with ``sigma`` a one-element
+    tensor that requires grad gets ``sigma.grad`` (up to 32 dims from the same HIP launch that gives X its gradient), a static kernel
+    that is a ``torch.nn.Module`` gets its parameters' gradients through one vector-Jacobian product; a call where only such a
+    parameter requires grad is differentiated like any other.  A default object reads a tensor ``sigma`` as its value.
     """
 
     def __init__(self, static_kernel, dyadic_order, _naive_solver=False, workspace_bytes=None, process_group=None, exact_gradient=False):
@@ -1444,6 +1509,11 @@ class SigKernel:
         self.workspace_bytes = workspace_bytes
         self.process_group = process_group
         self.exact_gradient = bool(exact_gradient)
+
+    def _params(self):
+        """The static kernel's tensors this object differentiates (_static_params) -- under exact_gradient=True; a default object
+        reads a tensor sigma as its value."""
+        return _static_params(self.static_kernel) if self.exact_gradient else ()
 
     def _on_features(self):
         """(SigKernel of the base kernel, feature map) when the static kernel is one of function-valued paths, else None: the one
@@ -1466,10 +1536,12 @@ class SigKernel:
         if self.process_group is not None:
             from .distributed import sharded_kernel
             return sharded_kernel(self, X, Y, self.process_group)
-        if not _wants_grad(X, Y):
+        params = self._params()
+        if not _wants_grad(X, Y, *params):
             return _SigKernel.forward(_NoGradCtx(), X, Y, self.static_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes)
         if self.exact_gradient:
-            return _SigKernelExact.apply(X, Y, self.static_kernel, self.dyadic_order, False, False, self._naive_solver, self.workspace_bytes)
+            return _SigKernelExact.apply(X, Y, self.static_kernel, self.dyadic_order, False, False, self._naive_solver, self.workspace_bytes,
+                                         *params)
         return _SigKernel.apply(X, Y, self.static_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes)
 
     def _prefixes(self, X, Y, gram, max_batch, nodes="all"):
@@ -1482,14 +1554,15 @@ class SigKernel:
         if self.process_group is not None:
             raise NotImplementedError("prefix grids are not sharded over a process group: every rank would have to gather an "
                                       "(A, B, M, N) tensor; call it on a SigKernel without process_group")
-        if _wants_grad(X, Y):
+        params = self._params()
+        if _wants_grad(X, Y, *params):
             if not self.exact_gradient:
                 raise NotImplementedError("compute_Gram_prefixes / compute_kernel_prefixes are forward only on this object: the "
                                           "reference's adjoint formula has no prefix form.  Construct the SigKernel with "
                                           "exact_gradient=True for their true gradient, or call them under torch.no_grad() or on "
                                           "detached paths")
             return _SigKernelPrefixExact.apply(X, Y, self.static_kernel, self.dyadic_order, gram, nodes, self._naive_solver,
-                                               self.workspace_bytes)
+                                               self.workspace_bytes, *params)
         return _prefix_grid(_lib.get_backend(), self.static_kernel, X.detach(), Y.detach(), self.dyadic_order, self._naive_solver, gram,
                             self.workspace_bytes, nodes)
 
@@ -1557,9 +1630,10 @@ class SigKernel:
                                       "under torch.no_grad() or on detached paths" % what)
         lx = _lengths("len_x", len_x, X.shape[0], X.shape[1], X.device)
         ly = _lengths("len_y", len_y, Y.shape[0], Y.shape[1], Y.device)
-        if _wants_grad(X, Y):
+        params = self._params()
+        if _wants_grad(X, Y, *params):
             return _SigKernelRaggedExact.apply(X, Y, lx, ly, self.static_kernel, self.dyadic_order, gram, self._naive_solver,
-                                               self.workspace_bytes)
+                                               self.workspace_bytes, *params)
         return _prefix_at(_lib.get_backend(), self.static_kernel, X.detach(), Y.detach(), lx, ly, self.dyadic_order, self._naive_solver,
                           gram, self.workspace_bytes)
 
@@ -1630,11 +1704,13 @@ class SigKernel:
         if self.process_group is not None:
             from .distributed import sharded_gram
             return sharded_gram(self, X, Y, sym, self.process_group)
-        if not _wants_grad(X, Y):
+        params = self._params()
+        if not _wants_grad(X, Y, *params):
             return _SigKernelGram.forward(_NoGradCtx(), X, Y, self.static_kernel, self.dyadic_order, sym, self._naive_solver,
                                           self.workspace_bytes)
         if self.exact_gradient:
-            return _SigKernelExact.apply(X, Y, self.static_kernel, self.dyadic_order, True, sym, self._naive_solver, self.workspace_bytes)
+            return _SigKernelExact.apply(X, Y, self.static_kernel, self.dyadic_order, True, sym, self._naive_solver, self.workspace_bytes,
+                                         *params)
         return _SigKernelGram.apply(X, Y, self.static_kernel, self.dyadic_order, sym, self._naive_solver,
                                     self.workspace_bytes)
 
