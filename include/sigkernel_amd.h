@@ -468,6 +468,34 @@ int sk_solve_fwd_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t 
                          int dyadic, int scheme, double inv_sigma, double *out_final, void *queue, void *stream);
 int sk_solve_fwd_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                          int dyadic, int scheme, double inv_sigma, float *out_final, void *queue, void *stream);
+/* The same four calls for a caller whose `queue` holds queue_words >= 1 zero-initialisable 64-bit counters instead of one
+ * (sk_solve_fwd_linear_* / sk_solve_fwd_rbf_* are these with queue_words = 1).  A plain Gram launch (B > 0) whose pairs share their
+ * y columns across a wave's lane groups (two or more pairs per wave) is then dealt out BY GRAM ROW-BLOCK where ceil(A / G) counters
+ * are there and the row-blocks divide the resident waves evenly (sk_plan_row_dealing says whether and how): a wave stays with the
+ * x rows of one row-block for as long as that has work, and fetches them once.  The library zeroes the counters it uses.  Same
+ * results, bit for bit.  A / 2 + 1 counters are always enough. */
+int sk_solve_fwd_linear_rows_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                 int dyadic, int scheme, double *out_final, void *queue, int64_t queue_words, void *stream);
+int sk_solve_fwd_linear_rows_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                 int dyadic, int scheme, float *out_final, void *queue, int64_t queue_words, void *stream);
+int sk_solve_fwd_rbf_rows_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                              int dyadic, int scheme, double inv_sigma, double *out_final, void *queue, int64_t queue_words, void *stream);
+int sk_solve_fwd_rbf_rows_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                              int dyadic, int scheme, double inv_sigma, float *out_final, void *queue, int64_t queue_words, void *stream);
+/* Host only, no device call: how the one-band fused forward deals the stream positions of an A x B Gram launch to its waves
+ * (csrc/sk_pair_stream.h: plan_pair_stream, plan_row_dealing).  G = 64 / L lane groups per wave of L lanes per pair, NUp padded
+ * two-column units per pair, lag 0 (linear) or 2 (rbf), waves_per_cu resident waves on each of n_cu compute units, pct per cent of the
+ * equal share dealt out up front, queue_words counters (0: no queue).  G >= 2: the shared-y order, ceil(A / G) B positions, position
+ * q = row-block q / B, column q % B; G = 1: A B positions, no row-blocks.
+ *   plan[0] mode (1: row-local dealing), [1] waves, [2] largest share per wave, [3] q_first, [4] C0, [5] n_big, [6] logC,
+ *   [7] the counter is used, [8] waves per row-block, [9] row-blocks = counters used, [10] row_q0, [11] row_rem, [12] queues;
+ *   static_first / static_end [waves_cap]: wave w's up-front positions [first, end) (NULL: not wanted; waves > waves_cap: SK_ERR_BAD_ARG);
+ *   queue_first / queue_end [queues_cap]: the positions [first, end) each counter hands out, 2^logC at a time (mode 0: one counter
+ *   from q_first to the end; no queue: none).
+ * Together these ranges are every position exactly once.  Mode 0 is the plan of a launch without the *_rows_* counters, field for field. */
+int sk_plan_row_dealing(int64_t A, int64_t B, int G, int NUp, int L, int lag, int waves_per_cu, int n_cu, int pct, int64_t queue_words,
+                        int64_t *plan, int64_t waves_cap, int64_t *static_first, int64_t *static_end, int64_t queues_cap,
+                        int64_t *queue_first, int64_t *queue_end);
 /* The PREFIX GRID of every pair with the static kernel fused in (csrc/sk_wave_prefix.hip): the sweep of sk_solve_fwd_linear_* /
  * sk_solve_fwd_rbf_* that stores every coarse node instead of the last one,
  *     out[p ldo + m (Nc + 1) + n] = k_sig(x[:m+1], y[:n+1]),   1 <= m <= Mc, 0 <= n <= Nc

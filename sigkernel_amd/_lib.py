@@ -85,6 +85,11 @@ SIGNATURES = {
     "sk_solve_fwd_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_solve_fwd_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _vp]),
     "sk_solve_fwd_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _vp]),
+    "sk_solve_fwd_linear_rows_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp]),
+    "sk_solve_fwd_linear_rows_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _i64, _vp]),
+    "sk_solve_fwd_rbf_rows_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _i64, _vp]),
+    "sk_solve_fwd_rbf_rows_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _i64, _vp]),
+    "sk_plan_row_dealing": (_int, [_i64, _i64, _int, _int, _int, _int, _int, _int, _int, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_linear_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _i64, _vp, _vp]),
@@ -368,11 +373,18 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _queue(dev, pairs=1 << 30):
+def _queue(dev, pairs=1 << 30, words=8):
     """64 bytes of device scratch for one launch's work counter (the library zeroes it on the launch stream); the caching
     allocator keeps it alive for the work queued on this stream and hands it out again afterwards.  None for launches too small to
-    fill the chip (the library then deals out equal static shares, as it would anyway)."""
-    return torch.empty(8, dtype=torch.int64, device=dev) if pairs >= 16384 else None
+    fill the chip (the library then deals out equal static shares, as it would anyway).  words: 64-bit counters (_row_queue)."""
+    return torch.empty(max(8, int(words)), dtype=torch.int64, device=dev) if pairs >= 16384 else None
+
+
+def _row_queue(dev, A, B, gram):
+    """(queue, counters) for the fused forward without edges (sk_solve_fwd_{linear,rbf}_rows_*): a plain Gram launch may deal its
+    pairs out by Gram row-block, one counter each -- A // 2 + 1 are always enough (two or more pairs per wave, or no row-blocks)."""
+    n = max(8, A // 2 + 1) if gram else 8
+    return _queue(dev, A * B if gram else A, n), n
 
 
 def _prep_paths(X, diff, dim_major, scale, rows, fd=8):
@@ -535,8 +547,9 @@ class HipBackend:
                         return out, edges
                     if rc != 2:
                         _check(rc, "sk_solve_fwd_linear_edges")
-            fn = getattr(lib, "sk_solve_fwd_linear_" + _suffix(X))
-            rc = fn(_ptr(dXr), _ptr(dYt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, _ptr(out), _ptr(_queue(dev, A * B if gram else A)), _stream(X))
+            fn = getattr(lib, "sk_solve_fwd_linear_rows_" + _suffix(X))
+            queue, words = _row_queue(dev, A, B, gram)
+            rc = fn(_ptr(dXr), _ptr(dYt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, _ptr(out), _ptr(queue), words, _stream(X))
         if rc == 2:
             return None
         _check(rc, "sk_solve_fwd_linear")
@@ -573,9 +586,10 @@ class HipBackend:
                         return out, edges
                     if rc != 2:
                         _check(rc, "sk_solve_fwd_rbf_edges")
-            fn = getattr(lib, "sk_solve_fwd_rbf_" + _suffix(X))
+            fn = getattr(lib, "sk_solve_fwd_rbf_rows_" + _suffix(X))
+            queue, words = _row_queue(dev, A, B, gram)
             rc = fn(_ptr(Xr), _ptr(Yt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, 1.0 / float(sigma),
-                    _ptr(out), _ptr(_queue(dev, A * B if gram else A)), _stream(X))
+                    _ptr(out), _ptr(queue), words, _stream(X))
         if rc == 2:
             return None
         _check(rc, "sk_solve_fwd_rbf")

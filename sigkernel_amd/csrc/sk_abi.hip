@@ -264,6 +264,7 @@ Knobs parse_knobs() {
     k.deriv_wpc = knob_int("SK_DERIV_WPC"); k.deriv_wpb = knob_int("SK_DERIV_WPB");
     k.fused_wpc = knob_int("SK_FUSED_WPC"); k.fused_wpb = knob_int("SK_FUSED_WPB"); k.fused_q_static = knob_int("SK_FUSED_Q_STATIC");
     k.fused_mid = getenv("SK_FUSED_MID") ? knob_int("SK_FUSED_MID") : 1;
+    k.fused_rows = getenv("SK_FUSED_ROWS") ? knob_int("SK_FUSED_ROWS") : 1; k.fused_row_steal = knob_int("SK_FUSED_ROW_STEAL");
     k.fusedmb_wpc = knob_int("SK_FUSEDMB_WPC"); k.fusedmb_wpb = knob_int("SK_FUSEDMB_WPB"); k.fusedmb_q_static = knob_int("SK_FUSEDMB_Q_STATIC");
     k.fusedmb_split = getenv("SK_FUSEDMB_SPLIT") ? knob_int("SK_FUSEDMB_SPLIT") : 1;
     k.fusedmb_lead = knob_int("SK_FUSEDMB_LEAD");
@@ -497,40 +498,62 @@ int sk_solve_fwd_f32(const float *inc_c, int64_t ld, int64_t P, int Mc, int Nc, 
     return solve_fwd<float>(inc_c, ld, P, Mc, Nc, dyadic, scheme, flags, out_final, out_grid, out_edges, stream);
 }
 
-int sk_solve_fwd_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
-                            int dyadic, int scheme, double *out_final, void *queue, void *stream) {
+// The fused forward without edges.  *_rows_*: `queue` holds queue_words 64-bit counters (the others: one) -- a plain Gram launch in the
+// shared-y order then deals its positions out by Gram row-block where it has a counter for each (plan_row_dealing, sk_pair_stream.h)
+int sk_solve_fwd_linear_rows_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                 int dyadic, int scheme, double *out_final, void *queue, int64_t queue_words, void *stream) {
     if (D < 1 || !dXr || !dYt || !out_final || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
     if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
     if (A == 0) return SK_OK;
     const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
-    return launch_fwd_fused_linear<double>(dXr, dYt, A, B, Mrows, Ncp, D, g, out_final, nullptr, queue, (hipStream_t)stream);
+    if (queue && queue_words < 1) return SK_ERR_BAD_ARG;
+    return launch_fwd_fused_linear<double>(dXr, dYt, A, B, Mrows, Ncp, D, g, out_final, nullptr, queue, (hipStream_t)stream, 0, nullptr, queue_words);
+}
+int sk_solve_fwd_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                            int dyadic, int scheme, double *out_final, void *queue, void *stream) {
+    return sk_solve_fwd_linear_rows_f64(dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, out_final, queue, 1, stream);
+}
+int sk_solve_fwd_linear_rows_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                 int dyadic, int scheme, float *out_final, void *queue, int64_t queue_words, void *stream) {
+    if (D < 1 || !dXr || !dYt || !out_final || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
+    if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
+    if (A == 0) return SK_OK;
+    const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
+    if (queue && queue_words < 1) return SK_ERR_BAD_ARG;
+    return launch_fwd_fused_linear<float>(dXr, dYt, A, B, Mrows, Ncp, D, g, out_final, nullptr, queue, (hipStream_t)stream, 0, nullptr, queue_words);
 }
 int sk_solve_fwd_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                             int dyadic, int scheme, float *out_final, void *queue, void *stream) {
-    if (D < 1 || !dXr || !dYt || !out_final || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
-    if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
-    if (A == 0) return SK_OK;
-    const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
-    return launch_fwd_fused_linear<float>(dXr, dYt, A, B, Mrows, Ncp, D, g, out_final, nullptr, queue, (hipStream_t)stream);
+    return sk_solve_fwd_linear_rows_f32(dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, out_final, queue, 1, stream);
 }
 
-int sk_solve_fwd_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
-                         int scheme, double inv_sigma, double *out_final, void *queue, void *stream) {
+int sk_solve_fwd_rbf_rows_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
+                              int scheme, double inv_sigma, double *out_final, void *queue, int64_t queue_words, void *stream) {
     if (D < 1 || !Xr || !Yt || !out_final || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
     if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
     if (!(inv_sigma > 0.0) || !(inv_sigma < 1e300)) return SK_ERR_BAD_ARG;
     if (A == 0) return SK_OK;
     const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
-    return launch_fwd_fused_rbf<double>(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out_final, nullptr, queue, (hipStream_t)stream);
+    if (queue && queue_words < 1) return SK_ERR_BAD_ARG;
+    return launch_fwd_fused_rbf<double>(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out_final, nullptr, queue, (hipStream_t)stream, 0, nullptr, queue_words);
+}
+int sk_solve_fwd_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
+                         int scheme, double inv_sigma, double *out_final, void *queue, void *stream) {
+    return sk_solve_fwd_rbf_rows_f64(Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out_final, queue, 1, stream);
+}
+int sk_solve_fwd_rbf_rows_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
+                              int scheme, double inv_sigma, float *out_final, void *queue, int64_t queue_words, void *stream) {
+    if (D < 1 || !Xr || !Yt || !out_final || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
+    if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
+    if (!(inv_sigma > 0.0) || !(inv_sigma < 1e300)) return SK_ERR_BAD_ARG;
+    if (A == 0) return SK_OK;
+    const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
+    if (queue && queue_words < 1) return SK_ERR_BAD_ARG;
+    return launch_fwd_fused_rbf<float>(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out_final, nullptr, queue, (hipStream_t)stream, 0, nullptr, queue_words);
 }
 int sk_solve_fwd_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
                          int scheme, double inv_sigma, float *out_final, void *queue, void *stream) {
-    if (D < 1 || !Xr || !Yt || !out_final || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
-    if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
-    if (!(inv_sigma > 0.0) || !(inv_sigma < 1e300)) return SK_ERR_BAD_ARG;
-    if (A == 0) return SK_OK;
-    const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
-    return launch_fwd_fused_rbf<float>(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out_final, nullptr, queue, (hipStream_t)stream);
+    return sk_solve_fwd_rbf_rows_f32(Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out_final, queue, 1, stream);
 }
 
 int sk_solve_prefix_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,

@@ -19,6 +19,7 @@ struct Knobs {
     int derivf_wpc, derivf_wpb, derivf_noshift;   // sk_wave_deriv_fused.hip
     int deriv_wpc, deriv_wpb;
     int fused_wpc, fused_wpb, fused_q_static, fused_mid;
+    int fused_rows, fused_row_steal;   // SK_FUSED_ROWS=0: no row-local dealing (1: the default); SK_FUSED_ROW_STEAL: its looks for another row-block, 0 = the cost table's
     int fusedmb_wpc, fusedmb_wpb, fusedmb_q_static, fusedmb_split, fusedmb_lead;
     int prefix_store;   // SK_PREFIX_STORE: store scheme of the prefix kernel (sk_wave_prefix.hip), 0 = its default
     RankW rank_w, wave_rank_w, adj_rank_w, adjf_rank_w, adjr_rank_w, deriv_rank_w, fused_rank_w, fusedmb_rank_w;
@@ -173,11 +174,14 @@ int launch_deriv_wave(const T *inc, const T *inc_d, const T *inc_dd, int64_t ld,
 // ---- sk_wave_fused.hip: forward solver with the linear static kernel fused in (no increments in HBM) ----
 template <typename TO>
 int launch_fwd_fused_linear(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                            TO *out, double *strip_edges, void *queue, hipStream_t s, int tri = 0, const int64_t *loss = nullptr);
+                            TO *out, double *strip_edges, void *queue, hipStream_t s, int tri = 0, const int64_t *loss = nullptr,
+                            int64_t queue_words = 1);
 
 template <typename TO>
 int launch_fwd_fused_rbf(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                         double inv_sigma, TO *out, double *strip_edges, void *queue, hipStream_t s, int tri = 0, const int64_t *loss = nullptr);
+                         double inv_sigma, TO *out, double *strip_edges, void *queue, hipStream_t s, int tri = 0, const int64_t *loss = nullptr,
+                         int64_t queue_words = 1);
+// (queue_words: 64-bit counters behind `queue`; row-local dealing takes one per Gram row-block and is off where they are too few)
 // (tri = 2, loss = {tri_n, tri_off}: the LOSS layout -- both staged arrays hold one batch Z of B paths; A B rectangle pairs (rows
 // Z[0 .. A)), which keep their edges, then the strict upper triangle of Z[tri_off .. tri_off + tri_n), which does not; out [P] linear)
 

@@ -185,6 +185,11 @@ struct StreamPlan {
     int64_t q_first;
     int C0, n_big, logC;
     bool queue;           // the counter is used: the caller zeroes it before the launch (else it passes queue = nullptr)
+    // ROW-LOCAL dealing (plan_row_dealing; row_wprb == 0: off, and everything above is the plan it always was)
+    int row_wprb;         // waves per row-block: wave w is at home in row-block w % n_rb
+    int row_rem;          // positions the LAST wave of a row-block takes on top of C0, so that what is left is whole chunks
+    int row_q0;           // a row-block's counter hands out its positions from this offset on (= row_wprb C0 + row_rem)
+    int64_t n_rb;         // row-blocks = counters (the caller zeroes n_rb of them)
 };
 // waves_per_cu: resident waves per CU, already capped by LDS and registers; pct: per cent of the equal share dealt out up front
 // when the counter is used (100: never use it); has_queue: the caller has a counter.
@@ -218,7 +223,41 @@ inline int plan_pair_stream(int64_t P, int G, int NUp, int L, int lag, int waves
         if (base == 0) o.waves = o.n_big;                          // no more waves than the pairs need
         o.q_first = P;
     }
+    o.row_wprb = 0; o.row_rem = 0; o.row_q0 = 0; o.n_rb = 0;
     return SK_OK;
+}
+
+// ROW-LOCAL dealing: a second look at a plan that uses the counter, for the shared-y order (one_band_geometry: position q is Gram
+// row-block q / row_len, column q % row_len; a wave's lane groups keep their x rows for as long as its positions stay inside one
+// row-block).  Under the plan above a wave's draws lie `waves` tickets apart -- several row-blocks -- so nearly every drawn position
+// brings new rows.  Here every row-block has waves of its own and a counter of its own:
+//   * wave w is at home in row-block h = w % n_rb -- waves are dispatched oldest first and run the faster the older they are on
+//     their SIMD, so every row-block gets waves of every age; there are wprb = waves / n_rb of them.  Its static share is C0
+//     contiguous positions of h, from offset (w / n_rb) C0 on -- the same `pct` per cent of the equal share as above -- and the last wave of h takes row_rem more, so that
+//     what is left of the row-block is a whole number of chunks;
+//   * the rest of h, offsets [row_q0, row_len), is drawn one chunk at a time from counter h (n_rb counters, zeroed by the caller);
+//   * a wave whose row-block is used up moves on to the first following one (wrapping) that has positions left; it finds it by looking
+//     at the counters of 64 row-blocks at a time, a bounded number of looks (the kernel's argument), then ends.
+// Every wave draws from its HOME counter until that is used up, and every row-block has wprb >= 1 waves at home, so every position is
+// handed out -- by its own waves if by nobody else -- whatever the bound; a counter hands out every ticket once.
+// Only where the row-blocks divide the launch cleanly: P = n_rb row_len, waves = n_rb wprb, one lap of lanes per position (L <= NUp:
+// the lanes that start a pair in one step all start the same position), n_rb counters in the caller's buffer.  Everywhere else the
+// plan stays what plan_pair_stream made it, field for field.
+inline void plan_row_dealing(int64_t P, int64_t row_len, int NUp, int L, int64_t queue_words, StreamPlan &o) {
+    if (!o.queue || row_len <= 0 || P <= 0 || P % row_len != 0 || L > NUp) return;
+    const int64_t n_rb = P / row_len;
+    if (n_rb > queue_words || o.waves % n_rb != 0 || row_len > 0x3fffffff) return;
+    const int64_t wprb = o.waves / n_rb;
+    if (wprb < 1 || wprb > 0x7fff) return;
+    int64_t c0 = o.C0;
+    if (c0 * wprb > row_len) c0 = row_len / wprb;      // (per = ceil(row_len / wprb): only a pct close to 100 gets here)
+    const int64_t CQ = (int64_t)1 << o.logC;
+    o.C0 = (int)c0;
+    o.row_wprb = (int)wprb;
+    o.row_rem = (int)((row_len - wprb * c0) % CQ);
+    o.row_q0 = (int)(wprb * c0) + o.row_rem;
+    o.n_rb = n_rb;
+    o.q_first = 0;      // (unused: a draw is its row-block's first position + row_q0 + the ticket)
 }
 
 }  // namespace

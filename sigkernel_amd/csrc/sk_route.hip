@@ -120,6 +120,10 @@ const CostEntry COSTS[] = {
     {"fused_static_share_rbf", 20,
      "... the RBF variants (longer macro-steps, a draw costs less of one): 2048 x 2048 pairs, dyadic 2: 52.0 ms at 35, 50.9 at 20, 50.6 at 3; "
      "512 / 1024 paths: 3.41 -> 3.34, 13.0 -> 12.8 ms; C4 335.6 -> 334.5 (profiles/r05_qstatic.txt)"},
+    {"fused_row_steal", 8,
+     "row-local dealing of the one-band fused forward (plan_row_dealing): looks at the counters of the following 64 Gram row-blocks a wave "
+     "may take, once its own row-block is used up, to find one that has positions left, before it ends (SK_FUSED_ROW_STEAL overrides; a look "
+     "is one load's round trip, every position is handed out whatever the bound): profiles/fused_fwd_row_dealing.txt"},
     {"mb_split_max_resident_share", 0.5,
      "few pairs of long paths: bands of a pair on several waves when the pairs fill at most this share of the resident waves (r05: 16 x 16 pairs "
      "of 4096 points 18.7 -> 4.7 ms; 32 x 32 pairs of 700 points 2.18 -> 1.96 ms)"},

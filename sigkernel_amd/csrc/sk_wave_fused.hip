@@ -83,6 +83,14 @@ struct FusedParams {
     // B <= 0: unused.  Consulted where a producer's stream position changes and in the store branch, never in the step loop.
     unsigned div_m;
     int div_s;
+    // ROW-LOCAL dealing of a shared-y launch that uses the counter (plan_row_dealing, sk_pair_stream.h; row_nrb == 0: off).  `queue` is
+    // then row_nrb counters, one per Gram row-block of B positions: wave w is at home in row-block h = w % row_nrb, its chunk 0 is C0
+    // positions of h from offset (w / row_nrb) C0 on (row_rem more for the last wave of h), and its draws come from counter h -- ticket
+    // v is position h B + row_q0 + v -- until that is used up; then from the first of the following row-blocks (wrapping) that has
+    // positions left, found by looking at 64 counters at a time, at most row_steal looks before the stream ends.  So a wave's
+    // positions stay inside one row-block for as long as it has any.
+    int row_nrb, row_q0;        // consulted where a chunk is drawn
+    int row_wprb, row_rem, row_steal;   // prologue only
 };
 template <int N>
 __device__ __forceinline__ void lds_read_units(d2_t (&v)[N], unsigned addr);
@@ -195,6 +203,11 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // even dimension rows, the odd ones at a_e ^ 128, see lds_read_dims_issue).
     constexpr bool CUR = EDGES;   // per-lane (u, ps, uk, psk, yslab, ypar) cursors
     constexpr bool MID = false;   // fetch_next in the middle of a step instead of at its end (see there)
+    // KEEPX: the instances that can take the shared-y order.  There a wave's lane groups sweep the rows x_a of ONE Gram row-block for as
+    // long as its stream positions stay inside it, and a position that opens the row-block of the wave's previous one brings no new x
+    // rows: its producer visits issue no DMA, and the lanes that start its pairs keep the rows they hold (x_new below).  The other
+    // instances (full-wave, edge-keeping) are compiled without any of it.
+    constexpr bool KEEPX = !EDGES && !FULLWAVE;
     // x rows may stay in flight across the loop edge -- not in the variant that is short of registers, where the allocator
     // moves the destinations of pending loads (tools/check_async_hazards.py)
     constexpr bool INFLIGHT_X = !(KIND == 1 && DY == 0 && ND == 8 && RCX == 0);
@@ -248,6 +261,17 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         const unsigned used = (unsigned)(below & 0xffffu) + (unsigned)((below >> 16) & 0xffffu) + (unsigned)((below >> 32) & 0xffffu);
         cb0_ = (used * (unsigned)prm.rk_wpr + (unsigned)((w32 - rr * prm.rk_wpr) * c0_)) * (unsigned)GY;
     }
+    int row_home = 0;     // row-local dealing (FusedParams::row_nrb): this wave's home row-block
+    if constexpr (KEEPX) {
+        if (prm.row_nrb > 0) {
+            // (w % n_rb, not w / wprb: waves are dispatched oldest first, and the older a wave is on its SIMD the faster it runs --
+            // this way every row-block has waves of every age)
+            const int j = w32 / prm.row_nrb;
+            row_home = w32 - j * prm.row_nrb;
+            c0_ = prm.C0 + (j == prm.row_wprb - 1 ? prm.row_rem : 0);
+            cb0_ = (unsigned)row_home * (unsigned)prm.B + (unsigned)(j * prm.C0);
+        }
+    }
     const int C0 = __builtin_amdgcn_readfirstlane(c0_), logC = prm.logC, CQ = 1 << logC;
     unsigned cb0 = (unsigned)__builtin_amdgcn_readfirstlane((int)cb0_), cb1 = NOPAIR, cb2 = NOPAIR, cb3 = NOPAIR;   // chunk k in cb[k & 3]
     int have = 1;                     // chunks known so far
@@ -282,13 +306,66 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
         int left;
         return stream_pair_left(grp, i, left);
     };
+    // What the producers park between their visits (see PARK below), one value per lane.  Row-local dealing keeps its state here too,
+    // for the same reason -- the step loop has no scalar register to spare: lane 16 the row-block this wave draws from, lane 17 how
+    // many more looks for another one it may take.
+    int pos_ab = 0;
+    if constexpr (KEEPX) pos_ab = lane == 16 ? row_home : lane == 17 ? prm.row_steal : 0;
     // make sure the chunk of stream position f is known (the producers call this with the furthest position they touch)
     auto ensure = [&](int f) __attribute__((always_inline)) {
         int off;
         const int kf = chunk_of(f, off);
         while (have <= kf) {
             unsigned b = NOPAIR;
-            if (prm.queue && t_end == 0x7fffffff) {
+            bool by_row = false;
+            if constexpr (KEEPX) {
+                int nrb = prm.row_nrb;
+                asm volatile("" : "+s"(nrb));
+                if (nrb > 0 && t_end == 0x7fffffff) {
+                    // this wave's row-block's counter; used up: a following row-block's, as long as lane 17 allows.  (A ticket is an offset
+                    // in units of positions: CQ divides what a row-block leaves to its counter, so a chunk never straddles two.)
+                    by_row = true;
+                    int rb = __builtin_amdgcn_readlane(pos_ab, 16), more = __builtin_amdgcn_readlane(pos_ab, 17);
+                    const unsigned Bu = (unsigned)prm.B;
+                    for (;;) {
+                        unsigned v = 0;
+                        if (lane == 0) v = (unsigned)atomicAdd(prm.queue + rb, (unsigned long long)CQ);
+                        const unsigned o = (unsigned)prm.row_q0 + (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+                        if (o < Bu) {
+                            b = (unsigned)rb * Bu + o;
+                            break;
+                        }
+                        // Used up.  A look at the counters of the next 64 row-blocks at once, one per lane -- a plain load, a hint: the
+                        // draw itself stays the atomic above -- and on to the first that still has positions; none: the next 64.
+                        // Every look costs one of the `more` this wave has; the stream ends when they are spent.
+                        int cand = -1;
+                        const int reach = nrb - 1 < WAVE ? nrb - 1 : WAVE;      // row-blocks other than rb a look can cover
+                        while (more > 0 && cand < 0) {
+                            more -= 1;
+                            int idx = rb + 1 + lane;
+                            idx -= idx >= nrb ? nrb : 0;
+                            unsigned c = 0;
+                            if (lane < reach)
+                                c = __hip_atomic_load(reinterpret_cast<const unsigned *>(prm.queue + idx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            const unsigned long long open =
+                                __builtin_amdgcn_ballot_w64(lane < reach && c < Bu && (unsigned)prm.row_q0 + c < Bu);
+                            if (open) {
+                                cand = rb + 1 + (int)__builtin_ctzll(open);
+                                cand -= cand >= nrb ? nrb : 0;
+                            } else if (reach < WAVE) {
+                                more = 0;       // that was every other row-block
+                            } else {
+                                rb += WAVE;
+                                rb -= rb >= nrb ? nrb : 0;
+                            }
+                        }
+                        if (cand < 0) break;      // the stream ends here
+                        rb = cand;
+                    }
+                    pos_ab = lane == 16 ? rb : lane == 17 ? more : pos_ab;
+                }
+            }
+            if (!by_row && prm.queue && t_end == 0x7fffffff) {
                 unsigned long long v = 0;
                 if (lane == 0) v = atomicAdd(prm.queue, (unsigned long long)((shy_a() > 0 ? 1 : G) * CQ));
                 const unsigned long long q = (unsigned long long)prm.q_first +
@@ -362,7 +439,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // register to hold across the step loop -- they look every position up in every visit, as all instances did before, and the lanes
     // live inside a visit only.
     constexpr bool PARK = !(EDGES && ((KIND == 0 && DY == 0 && ND == 4 && !FULLWAVE) || (KIND == 1 && DY == 2 && ND == 8 && FULLWAVE)));
-    int pos_ab = 0;
+    // (pos_ab itself is declared above ensure(), which keeps the row-local dealing's state in lanes 16 and 17, and the x producer's
+    // "this position brings new rows" in lane 18)
     // (... nor for the lane offsets of the DMA sources, which the compiler would hoist out of the step loop: an opaque lane number)
     auto dma_lane = [&]() __attribute__((always_inline)) -> int {
         int l = lane;
@@ -400,10 +478,18 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     // x slabs for the lanes that start a pair during macro-steps [t0, t0+XW): lanes lam0 + j*NUp .. +XW-1 start pair
     // t0/NUp - j, rows (lam0 + j*NUp .. +XW-1)*RC of its x
     int x_q0 = 0, x_lam0 = 0, x_slot = 0;   // next window: t0 / NUp, t0 % NUp, ring slot
+    // KEEPX: x_new says whether the window the last call stood for brings new rows.  It does not where its position opens the Gram
+    // row-block of the position before it (shared-y, one lap of lanes per position: JMAX == 1) -- group 0's row, parked in the lanes
+    // below, is G times the row-block -- and then the visits of that position issue no DMA at all: the lanes hold these rows already.
+    // Worked out by the visit that opens the position, parked in lane 18 for the others.
+    int x_new = 1;
     auto issue_x = [&]() __attribute__((always_inline)) {
         if constexpr (!PARK) pos_ab = 0;
         const int ln = dma_lane();
+        if constexpr (KEEPX) x_new = __builtin_amdgcn_readlane(pos_ab, 18);
         if (!PARK || x_lam0 == 0) {      // a new position: its rows, per lane group (not PARK: every position this visit reaches)
+            int prev0 = 0;
+            if constexpr (KEEPX) prev0 = __builtin_amdgcn_readlane(pos_ab, ((x_q0 - 1) & (NS - 1)) * G);   // (NS = 1: read before it is overwritten)
             ensure(x_q0);
             // shared-y: a = G (position / B) + g, one look-up for all groups; no such row / pair: 0 -- something valid, never stored
             const int sA = shy_a();
@@ -425,8 +511,13 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
                     pos_ab = lane == at + g ? a : pos_ab;
                 }
             }
+            if constexpr (KEEPX) {
+                const int now0 = __builtin_amdgcn_readlane(pos_ab, (x_q0 & (NS - 1)) * G);
+                x_new = (sA > 0 && JMAX == 1 && x_q0 > 0 && now0 == prev0) ? 0 : 1;
+                pos_ab = lane == 18 ? x_new : pos_ab;
+            }
         }
-        for (int j = 0; j < JMAX; ++j) {
+        for (int j = 0; j < (KEEPX && !x_new ? 0 : JMAX); ++j) {
             const int lamj = x_lam0 + j * NUp;
             if (lamj >= L) break;
             const int at = ((x_q0 - j) & (NS - 1)) * G;
@@ -562,11 +653,17 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
     };
     unsigned x_rd_off = 0;   // ring slot the x rows of this XW-step window are read from: ((t / XW) % X_SLOTS) * JMAX * XSLAB
     static_assert(X_SLOTS == 2, "x_rd_off toggles between two slots");
+    // KEEPX: x_rd_off also says, in its two lowest bits (the slot offsets are multiples of 16), whether the lanes that start a pair
+    // read their rows at all: bit 0 for the window being consumed, bit 1 for the next one (what x_new was when each was issued).  With
+    // one lap of lanes per position the lanes that start a pair in one step all start the same position, so this is wave-uniform;
+    // with more laps every position counts as new.  No scalar register of its own across the step loop.
     issue_y();
     issue_x();
+    if constexpr (KEEPX) x_rd_off = (unsigned)x_new;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     issue_y();
     issue_x();
+    if constexpr (KEEPX) x_rd_off |= (unsigned)x_new << 1;
     refresh_next();
     sweep_pair_is(psk);
     refresh_next();
@@ -752,10 +849,21 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             read_y();
             // this lane starts a pair in the next step (RESET_AT_END: tm is the NEXT step's already -- see "advance" -- and c_u0m1 is dead)
             if (RESET_AT_END ? tm == c_u0 : tm == c_u0m1) {
-                load_x_rows(my_x + (turn ? x_rd_off ^ (unsigned)(JMAX * XSLAB) : x_rd_off));
-                if constexpr (!INFLIGHT_X) {
+                if constexpr (KEEPX) {
+                    // (the rows of a position inside the row-block of the one before are the ones this lane holds)
+                    if (x_rd_off & (turn ? 2u : 1u)) {
+                        load_x_rows(my_x + ((turn ? x_rd_off ^ (unsigned)(JMAX * XSLAB) : x_rd_off) & ~3u));
+                        if constexpr (!INFLIGHT_X) {
 #pragma unroll
-                    for (int k = 0; k < RC; ++k) lds_rows_wait(dxq[k]);
+                            for (int k = 0; k < RC; ++k) lds_rows_wait(dxq[k]);
+                        }
+                    }
+                } else {
+                    load_x_rows(my_x + (turn ? x_rd_off ^ (unsigned)(JMAX * XSLAB) : x_rd_off));
+                    if constexpr (!INFLIGHT_X) {
+#pragma unroll
+                        for (int k = 0; k < RC; ++k) lds_rows_wait(dxq[k]);
+                    }
                 }
                 if constexpr (RESET_AT_END) {   // left boundary K[i][0] = 1 of the new pair
                     corner = 1.0;
@@ -916,6 +1024,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_fused(const FusedParams prm) {
             if (XW == 8 || ((t + 1) & 7) == 0) issue_y();       // slab ((t + 1) >> 3) + 1
             issue_x();       // window t + 1 + XW .. t + 2 XW
             x_rd_off ^= (unsigned)(JMAX * XSLAB);
+            if constexpr (KEEPX)      // the next window becomes the one consumed; the one just issued is the next
+                x_rd_off = (x_rd_off & ~3u) | ((x_rd_off >> 1) & 1u) | ((unsigned)x_new << 1);
             if (XW == 8 || ((t + 1) & 7) == 0) refresh_next();
         }
         if (AHEAD && CUR) read_y();   // for macro-step t + 1
@@ -947,6 +1057,8 @@ struct FusedPlan {
     size_t lds_bytes;   // per wave
     int waves_per_cu;   // from LDS and the measured optimum; still to be capped by the variant's VGPR use
     int rcx;            // coarse rows per lane when not the strip kernels' own (0: Tile<DY>::RC)
+    int64_t row_len;    // shared-y: stream positions per Gram row-block (= B); 0: the positions have no such blocks
+    int64_t queue_words;   // 64-bit counters the caller's queue buffer holds
 };
 
 template <typename TO, int DY, bool NAIVE, bool FULLWAVE, bool EDGES, int KIND, int ND, int RCX = 0>
@@ -998,9 +1110,17 @@ int launch_fused_nd(FusedParams prm, const FusedPlan &pl, hipStream_t s) {
     const int64_t max_waves = (int64_t)device_cu_count() * waves_per_cu;
     waves = sp.waves;
     per = sp.per;
+    // row-local dealing where the launch allows it (the instances that cannot take the shared-y order never get a row_len)
+    if (knobs().fused_rows != 0 && !EDGES && !FULLWAVE) plan_row_dealing(pl.P, pl.row_len, pl.NUp, pl.L, pl.queue_words, sp);
     prm.C0 = sp.C0; prm.n_big = sp.n_big; prm.logC = sp.logC; prm.q_first = sp.q_first;
+    prm.row_nrb = sp.row_wprb > 0 ? (int)sp.n_rb : 0; prm.row_q0 = sp.row_q0; prm.row_wprb = sp.row_wprb; prm.row_rem = sp.row_rem;
+    {
+        const int steal = knobs().fused_row_steal > 0 ? knobs().fused_row_steal : (int)cost_by_name("fused_row_steal");
+        prm.row_steal = steal < 1024 ? steal : 1024;
+    }
     if (sp.queue) {
-        if (hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
+        const size_t counters = prm.row_nrb > 0 ? (size_t)prm.row_nrb : 1;
+        if (hipMemsetAsync(prm.queue, 0, counters * sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
     } else {
         prm.queue = nullptr;
         // A launch that fills the chip with a dozen pairs per wave and more, but too few for the queue (a 64-row shard of the
@@ -1109,7 +1229,8 @@ int launch_fused_dy(const FusedParams &prm, const FusedPlan &pl, hipStream_t s) 
 // SK_ERR_UNSUPPORTED outside the kernel's scope.
 template <typename TO, int KIND>
 int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                     double inv_sigma, TO *out, double *strip_edges, void *queue, hipStream_t s, int tri = 0, const int64_t *loss = nullptr) {
+                     double inv_sigma, TO *out, double *strip_edges, void *queue, hipStream_t s, int tri = 0, const int64_t *loss = nullptr,
+                     int64_t queue_words = 1) {
     // (tri = 2: the caller -- sk_solve_fwd_loss_f64 -- has checked that the pair table lies behind dYt)
     if (tri == 1 && (strip_edges || A != B || g.P != A * (A + 1) / 2)) return SK_ERR_UNSUPPORTED;
     // the loss layout: loss = {tri_n, tri_off}; A rows against the B paths of the one batch, then the strict triangle of tri_n of them
@@ -1160,7 +1281,7 @@ int launch_fwd_fused(const double *dXr, const double *dYt, int64_t A, int64_t B,
     if (wpc_env > 0) waves_per_cu = waves_per_cu < wpc_env ? waves_per_cu : wpc_env;
     else if (waves_per_cu > 4) waves_per_cu &= ~3;   // whole four-wave workgroups
     if (waves_per_cu < 1) waves_per_cu = 1;
-    const FusedPlan pl{n_pos, og.GY, NUp, L, KIND == 1 ? 2 : 0, lds_bytes, waves_per_cu, rcx};
+    const FusedPlan pl{n_pos, og.GY, NUp, L, KIND == 1 ? 2 : 0, lds_bytes, waves_per_cu, rcx, shy ? B : 0, queue_words};
 
     FusedParams prm;
     prm.dXr = dXr; prm.dYt = dYt; prm.out = out; prm.edges = strip_edges; prm.P = n_pos; prm.B = B;
@@ -1209,25 +1330,70 @@ extern "C" int sk_pair_div_magic(int64_t B, uint32_t *mul, int *shift) {
     return SK_OK;
 }
 
+// (the launcher's own plan -- plan_pair_stream, then plan_row_dealing -- for the host test of the dealing; no device call)
+extern "C" int sk_plan_row_dealing(int64_t A, int64_t B, int G, int NUp, int L, int lag, int waves_per_cu, int n_cu, int pct,
+                                   int64_t queue_words, int64_t *plan, int64_t waves_cap, int64_t *static_first, int64_t *static_end,
+                                   int64_t queues_cap, int64_t *queue_first, int64_t *queue_end) {
+    if (!plan || A < 1 || B < 1 || G < 1 || G > 8 || NUp < 8 || (NUp & 7) || L < 8 || L > 64 || lag < 0 || waves_per_cu < 1 || n_cu < 1 ||
+        pct < 1 || pct > 100 || queue_words < 0 || (static_first == nullptr) != (static_end == nullptr) ||
+        (queue_first == nullptr) != (queue_end == nullptr))
+        return SK_ERR_BAD_ARG;
+    const int64_t n_pos = G >= 2 ? (A + G - 1) / G * B : A * B;
+    StreamPlan sp;
+    if (const int rc = plan_pair_stream(n_pos, 1, NUp, L, lag, waves_per_cu, n_cu, pct, queue_words > 0, sp)) return rc;
+    plan_row_dealing(n_pos, G >= 2 ? B : 0, NUp, L, queue_words, sp);
+    const bool rows = sp.row_wprb > 0;
+    const int64_t CQ = (int64_t)1 << sp.logC, n_q = rows ? sp.n_rb : (sp.queue ? 1 : 0);
+    const int64_t fields[13] = {rows ? 1 : 0, sp.waves, sp.per, sp.q_first, sp.C0, sp.n_big, sp.logC, sp.queue ? 1 : 0,
+                                sp.row_wprb, rows ? sp.n_rb : 0, sp.row_q0, sp.row_rem, n_q};
+    for (int i = 0; i < 13; ++i) plan[i] = fields[i];
+    if (static_first) {
+        if (sp.waves > waves_cap) return SK_ERR_BAD_ARG;
+        for (int64_t w = 0; w < sp.waves; ++w) {      // what the kernel's prologue makes of its wave number (cb0, C0)
+            int64_t first, count;
+            if (rows) {
+                const int64_t j = w / sp.n_rb, h = w - j * sp.n_rb;
+                first = h * B + j * sp.C0;
+                count = sp.C0 + (j == sp.row_wprb - 1 ? sp.row_rem : 0);
+            } else {
+                first = w * sp.C0 + (w < sp.n_big ? w : sp.n_big);
+                count = sp.C0 + (w < sp.n_big ? 1 : 0);
+            }
+            static_first[w] = first < n_pos ? first : n_pos;
+            static_end[w] = first + count < n_pos ? first + count : n_pos;
+        }
+    }
+    if (queue_first) {
+        if (n_q > queues_cap) return SK_ERR_BAD_ARG;
+        for (int64_t h = 0; h < n_q; ++h) {
+            queue_first[h] = rows ? h * B + sp.row_q0 : sp.q_first;
+            queue_end[h] = rows ? (h + 1) * B : n_pos;      // (mode 0: the last chunk is cut at the end of the stream)
+        }
+        if (rows && (B - sp.row_q0) % CQ != 0) return SK_ERR_LAUNCH;      // (cannot happen: row_rem makes the rest whole chunks)
+    }
+    return SK_OK;
+}
+
 template <typename TO>
 int launch_fwd_fused_linear(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                            TO *out, double *strip_edges, void *queue, hipStream_t s, int tri, const int64_t *loss) {
-    return launch_fwd_fused<TO, 0>(dXr, dYt, A, B, Mrows, Ncp, D, g, 0.0, out, strip_edges, queue, s, tri, loss);
+                            TO *out, double *strip_edges, void *queue, hipStream_t s, int tri, const int64_t *loss, int64_t queue_words) {
+    return launch_fwd_fused<TO, 0>(dXr, dYt, A, B, Mrows, Ncp, D, g, 0.0, out, strip_edges, queue, s, tri, loss, queue_words);
 }
 // Xr [A][Mrows][8]: path points x_p (zero rows / dims beyond M / D); Yt [Bn][8][Ncp]: y_q, dimension-major
 template <typename TO>
 int launch_fwd_fused_rbf(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                         double inv_sigma, TO *out, double *strip_edges, void *queue, hipStream_t s, int tri, const int64_t *loss) {
-    return launch_fwd_fused<TO, 1>(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, strip_edges, queue, s, tri, loss);
+                         double inv_sigma, TO *out, double *strip_edges, void *queue, hipStream_t s, int tri, const int64_t *loss,
+                         int64_t queue_words) {
+    return launch_fwd_fused<TO, 1>(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, strip_edges, queue, s, tri, loss, queue_words);
 }
 
 template int launch_fwd_fused_linear<double>(const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double *,
-                                             double *, void *, hipStream_t, int, const int64_t *);
+                                             double *, void *, hipStream_t, int, const int64_t *, int64_t);
 template int launch_fwd_fused_linear<float>(const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, float *,
-                                            double *, void *, hipStream_t, int, const int64_t *);
+                                            double *, void *, hipStream_t, int, const int64_t *, int64_t);
 template int launch_fwd_fused_rbf<double>(const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double, double *,
-                                          double *, void *, hipStream_t, int, const int64_t *);
+                                          double *, void *, hipStream_t, int, const int64_t *, int64_t);
 template int launch_fwd_fused_rbf<float>(const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double, float *,
-                                         double *, void *, hipStream_t, int, const int64_t *);
+                                         double *, void *, hipStream_t, int, const int64_t *, int64_t);
 
 }  // namespace sk
