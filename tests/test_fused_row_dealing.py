@@ -26,6 +26,7 @@ import pytest
 import torch
 
 import sigkernel_amd
+from launch_plans import earlier_plan as _earlier_plan      # (plan_pair_stream restated: the plan before row-local dealing)
 from oracle import oracle as O
 from poison import poisoned
 
@@ -54,29 +55,6 @@ def _plan(A, B, G, NUp, L, lag=0, wpc=12, n_cu=N_CU, pct=35, words=None):
     assert rc == 0, rc
     f = dict(zip(FIELDS, (int(v) for v in plan)))
     return f, np.stack([sf, se], 1)[: f["waves"]], np.stack([qf, qe], 1)[: f["queues"]]
-
-
-def _earlier_plan(P, NUp, L, lag, wpc, n_cu, pct, has_queue):
-    """plan_pair_stream (sk_pair_stream.h) for one stream position per wave and step, restated: the plan before row-local dealing"""
-    max_waves = n_cu * wpc
-    waves = min(P, max_waves)
-    per = (P + waves - 1) // waves
-    span = (L - 1 + lag + 24) // NUp + 2
-    logC = 0
-    while (span >> logC) + 1 > 3:
-        logC += 1
-    while ((per * (100 - pct) // 100) >> (logC + 1)) >= 24 and logC < 8:
-        logC += 1
-    queue = has_queue and waves == max_waves and per >= (8 << logC) and pct < 100
-    if queue:
-        C0, n_big, q_first = per * pct // 100, 0, waves * (per * pct // 100)
-    else:
-        base = P // waves
-        rem = P - base * waves
-        C0, n_big, q_first = base, rem, P
-        if base == 0:
-            waves = n_big
-    return dict(waves=waves, per=per, q_first=q_first, C0=C0, n_big=n_big, logC=logC, queue=int(queue))
 
 
 def _mode_expected(A, B, G, NUp, L, lag, wpc, n_cu, pct, words):
