@@ -69,7 +69,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*, sk_truncated_wide_adjoint*) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*, sk_truncated_wide_adjoint*, sk_plan_adjoint_chunks, sk_plan_one_draw) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -939,6 +939,21 @@ int sk_linear_adjoint_finish_f64(const double *tpart, int64_t A, int64_t chunks,
 int sk_plan_wave_shares(int64_t P, int G, int64_t waves, int64_t resident, int wpb, int n_cu, int64_t *first, int64_t *end, int *ppg);
 int sk_plan_group_chunks(int64_t A, int64_t B, int64_t PPG, int64_t max_groups, int G, int wpb, int n_cu, int64_t n_groups,
                          int64_t *first, int64_t *slot, int *ppg);
+/* sk_plan_adjoint_chunks: how the one-band fused adjoints launch an A x B Gram (B > 0) or a paired batch of A pairs (B == 0) on waves of
+ * G lane groups, NUp units per row, of which n_cu * wpc are resident; wpb_knob: the waves-per-workgroup knob (0: the default), lds_bytes:
+ * LDS of one wave, paired_form: the variant can sweep several consecutive pairs per lane group, force_nch > 0: the chunks per row are
+ * given.  plan[5] = pairs per lane-group chunk (the longest), pairs per lane group of a paired batch, rows per launch (0: one launch;
+ * else the Gram is swept in launches of that many rows, each filling the chip exactly), lane groups, chunks per row.
+ * sk_plan_one_draw: the launch of the one-draw kernels (multi-band forward and adjoints, fused derivative solver) for P pairs: resident
+ * waves per CU from a wave's LDS bytes, the waves per workgroup wpb0, the variant's VGPR count and the waves-per-CU knob (0: none), then
+ * the shares for units = bands x units per row, pct per cent of the equal share dealt out up front, ws_stride workspace doubles per wave.
+ * plan[7] = waves per CU, waves, pairs per wave (the equal share), pairs a wave takes up front, the first pair drawn from the counter,
+ * whether the counter is used, workspace doubles in front of the counter.
+ * Both return an sk_status (SK_ERR_UNSUPPORTED: a 32-bit index guard refuses the launch). */
+int sk_plan_adjoint_chunks(int64_t A, int64_t B, int G, int NUp, int n_cu, int wpc, int wpb_knob, int64_t lds_bytes, int paired_form,
+                           int64_t force_nch, int64_t *plan);
+int sk_plan_one_draw(int64_t P, int64_t lds_bytes, int wpb0, int vgprs, int wpc_knob, int n_cu, int64_t units, int pct, int64_t ws_stride,
+                     int64_t *plan);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 
 #include "sk_internal.h"
 #include "sk_wave_common.h"
+#include "sk_pair_stream.h"
 
 using namespace sk;
 
@@ -305,7 +306,8 @@ extern "C" {
 
 // (340 still: sk_truncated_levels_{,paired_}{f64,f32}, sk_truncated_adjoint and its plan, sk_truncated_points_{f64,f32} and SK_OP_TRUNCATED_RBF,
 // sk_truncated_long_{f64,f32}, its plan and SK_OP_TRUNCATED_LONG, sk_truncated_long_adjoint, its plan and SK_OP_TRUNCATED_LONG_ADJOINT,
-// sk_truncated_wide_adjoint, its plan and SK_OP_TRUNCATED_WIDE_ADJOINT are additions, no exported signature changed)
+// sk_truncated_wide_adjoint, its plan and SK_OP_TRUNCATED_WIDE_ADJOINT, sk_plan_adjoint_chunks and sk_plan_one_draw are additions, no exported
+// signature changed)
 // 340: sk_static_increments_* serve any path dim (D > 32: k_static_wide_mfma); sk_static_adjoint_* kind 1 with D > 32 writes the first
 // pass H [P][M][ldh] of the rbf chain rule instead of dL/dX
 // 330 (round 6): sk_linear_adjoint_fused_f64 takes ypart / ypart_doubles / ycols_out (the second-argument sums, route FUSED_SWAP)
@@ -363,6 +365,32 @@ int sk_plan_group_chunks(int64_t A, int64_t B, int64_t PPG, int64_t max_groups, 
     const int64_t P = B > 0 ? A * B : A;
     for (int64_t gi = 0; gi < n_groups; ++gi) sk::chunk_share(cs, gi, A, B, P, first[gi], slot[gi], ppg[gi]);
     return cs.nr;
+}
+
+// (the launchers' own plan_adjoint_chunks and plan_one_draw, for the host tests of the plans; no device call)
+int sk_plan_adjoint_chunks(int64_t A, int64_t B, int G, int NUp, int n_cu, int wpc, int wpb_knob, int64_t lds_bytes, int paired_form,
+                           int64_t force_nch, int64_t *plan) {
+    if (!plan || A < 1 || B < 0 || A > 0x7fffffff || B > 0x7fffffff || G < 1 || G > 8 || NUp < 8 || (NUp & 7) || n_cu < 1 || wpc < 1 ||
+        wpb_knob < 0 || lds_bytes < 1 || force_nch < 0 || (force_nch > 0 && B == 0))
+        return SK_ERR_BAD_ARG;
+    sk::AdjointChunks pc;
+    if (const int rc = sk::plan_adjoint_chunks(A, B, G, NUp, n_cu, wpc, wpb_knob, (size_t)lds_bytes, paired_form != 0, force_nch, pc)) return rc;
+    const int64_t fields[5] = {pc.PPG, pc.ppp, pc.rows_per_launch, pc.groups, sk::chunks_of(B, pc.PPG)};
+    for (int i = 0; i < 5; ++i) plan[i] = fields[i];
+    return SK_OK;
+}
+
+int sk_plan_one_draw(int64_t P, int64_t lds_bytes, int wpb0, int vgprs, int wpc_knob, int n_cu, int64_t units, int pct, int64_t ws_stride,
+                     int64_t *plan) {
+    if (!plan || P < 1 || lds_bytes < 1 || lds_bytes > 160 * 1024 || wpb0 < 1 || wpb0 > 4 || vgprs < 1 || vgprs > 512 || wpc_knob < 0 ||
+        n_cu < 1 || units < 1 || pct < 1 || pct > 100 || ws_stride < 0)
+        return SK_ERR_BAD_ARG;
+    const int wpc = sk::one_draw_waves_per_cu((size_t)lds_bytes, wpb0, vgprs, wpc_knob);
+    sk::OneDrawPlan dp;
+    if (const int rc = sk::plan_one_draw(P, (int64_t)n_cu * wpc, units, pct, ws_stride, dp)) return rc;
+    const int64_t fields[7] = {wpc, dp.waves, dp.per, dp.C0, dp.q_first, dp.queue ? 1 : 0, dp.ws_doubles};
+    for (int i = 0; i < 7; ++i) plan[i] = fields[i];
+    return SK_OK;
 }
 
 const char *sk_status_string(int status) {

@@ -263,6 +263,21 @@ int launch_fused_screen(const double *kfinal, const double *scale, int64_t P, do
     return check_launch();
 }
 
+int arm_fused_rescue(const FusedRescue *rescue, const double *scale, int64_t P, double *err, hipStream_t s, const double *&sweep_scale,
+                     void *&rescue_ws, size_t &rescue_ws_bytes) {
+    sweep_scale = scale;
+    rescue_ws = nullptr;
+    rescue_ws_bytes = 0;
+    if (!rescue || !rescue->ws) return SK_OK;
+    const size_t head = sizeof(double) * (size_t)((P + 1) / 2 * 2);
+    if (rescue->ws_bytes <= head) return SK_ERR_WORKSPACE;
+    rescue_ws = (char *)rescue->ws + head;
+    rescue_ws_bytes = rescue->ws_bytes - head;
+    if (!rescue->kfinal) return SK_OK;
+    sweep_scale = (const double *)rescue->ws;
+    return launch_fused_screen(rescue->kfinal, scale, P, rescue->screen, (double *)rescue->ws, err, s);
+}
+
 int launch_fused_rescue(int kind, const double *Xs, const double *Ys, const double *scale, const double *err, double tol, double *part,
                         double *ypart, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g, int rows, int outw, int ycols,
                         double inv_sigma, const ChunkSplit &cs, int64_t n_groups, void *ws, size_t ws_bytes, hipStream_t s, int fd, double *n0,

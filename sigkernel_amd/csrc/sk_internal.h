@@ -306,6 +306,12 @@ int launch_adj_fused_rbf(const double *Xr, const double *Yt, int64_t A, int64_t 
 // ---- sk_adj_fused_rescue.hip: device-side rescue of the fused adjoints (exploding kernels) ----
 size_t fused_rescue_workspace_bytes(int kind, int64_t P, int Mc, int Nc, int dyadic, int blocks);
 int launch_fused_screen(const double *kfinal, const double *scale, int64_t P, double screen, double *scale_eff, double *err, hipStream_t s);
+// Arms the rescue for a sweep of P pairs: the workspace starts with the swept upstream gradient [P rounded up to 2] (with forward values
+// given, launch_fused_screen writes it -- screened pairs NaN -- and the sweep reads it instead of `scale`); what is behind it is
+// launch_fused_rescue's.  rescue == nullptr or without a workspace: sweep_scale = scale, rescue_ws = nullptr.  SK_ERR_WORKSPACE: nothing
+// behind the head.
+int arm_fused_rescue(const FusedRescue *rescue, const double *scale, int64_t P, double *err, hipStream_t s, const double *&sweep_scale,
+                     void *&rescue_ws, size_t &rescue_ws_bytes);
 int launch_fused_rescue(int kind, const double *Xs, const double *Ys, const double *scale, const double *err, double tol, double *part,
                         double *ypart, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g, int rows, int outw, int ycols,
                         double inv_sigma, const ChunkSplit &cs, int64_t n_groups, void *ws, size_t ws_bytes, hipStream_t s, int fd = 8, double *n0 = nullptr,

@@ -1,6 +1,9 @@
 // sk_pair_stream.h -- what the persistent-wave fused kernels share around their step loops: the LDS read helpers of the one-band
 // sweeps (sk_wave_fused.hip, sk_wave_prefix.hip), their pair -> (a, b) split, and the host arithmetic of their launchers
-// (launch plan, geometry; the VGPR query of every persistent-wave launcher is in sk_wave_common.h).
+// (launch plan, geometry; the VGPR query of every persistent-wave launcher is in sk_wave_common.h) -- and of the ONE-DRAW launchers
+// (sk_wave_fused_mb.hip, sk_wave_adj_fused_mb.hip, sk_wave_deriv_fused.hip): one_draw_waves_per_cu, plan_one_draw.  The one-band fused
+// adjoints' host arithmetic (plan_adjoint_chunks, sweep_gram_rows) is next to pick_chunk / chunk_split in sk_wave_common.h, the arming
+// of their device-side rescue (arm_fused_rescue) in sk_adj_fused_rescue.hip.
 // The step loops themselves are NOT shared: they sit at their kernels' register limits and are tuned per kernel.
 // Everything device-side here is __forceinline__ and keeps the evaluation order and the opaque moves of the per-file copies
 // it replaced, so the kernels' ISA is theirs: compare the ISA of the whole build when touching it.
@@ -104,7 +107,7 @@ __device__ __forceinline__ int64_t pair_split(const PRM &prm, int64_t p, bool wa
 // k_fwd_prefix, the one-draw one in k_fwd_fused_mb, k_deriv_fused and the two multi-band adjoints): moved into __forceinline__
 // functions that take the ring, `have` and `t_end` by reference and the kernel's parts as callables, behind the kernels'
 // unchanged lambdas, all 195 instances of these kernels came out with other ISA than the measured one; each file gives the
-// register numbers seen.  A fix to one copy goes into the others.
+// register numbers seen.  A fix to one copy goes into the others.  (Their HOST arithmetic has one copy: plan_pair_stream, plan_one_draw.)
 
 // ---- host: the launch arithmetic of these kernels ---------------------------------------------------------------------------------------
 // lanes per x window of the one-band sweeps: 8 (one window per y slab period), or 4 where four lanes' rows fill a whole 1 KiB LDS-DMA
@@ -224,6 +227,38 @@ inline int plan_pair_stream(int64_t P, int G, int NUp, int L, int lag, int waves
         o.q_first = P;
     }
     o.row_wprb = 0; o.row_rem = 0; o.row_q0 = 0; o.n_rb = 0;
+    return SK_OK;
+}
+
+// The launch plan of a ONE-DRAW stream (k_fwd_fused_mb outside split mode, k_deriv_fused, the two multi-band adjoints): a wave sweeps
+// one pair at a time and draws pair by pair.  Resident waves per CU of a variant: whole workgroups of wpb0 waves by LDS, by its
+// registers, by the family's knob (0: none), at most two per SIMD.
+inline int one_draw_waves_per_cu(size_t lds_bytes, int wpb0, int vgprs, int wpc_knob) {
+    int wpc = waves_by_vgprs((int)((160 * 1024) / (lds_bytes * wpb0)) * wpb0, vgprs);
+    if (wpc_knob > 0 && wpc > wpc_knob) wpc = wpc_knob;
+    if (wpc > 8) wpc = 8;
+    if (wpc >= wpb0) wpc = wpc / wpb0 * wpb0;
+    return wpc < 1 ? 1 : wpc;
+}
+struct OneDrawPlan {
+    int64_t waves, per;       // waves launched; the equal share, pairs per wave
+    int64_t q_first;          // the first pair the counter hands out
+    int C0;                   // pairs a wave takes up front
+    bool queue;               // the counter is used: the caller zeroes it before the launch (else it passes queue = nullptr)
+    int64_t ws_waves, ws_doubles;   // the waves the workspace holds a row for, and the doubles that takes: the counter sits behind them
+};
+// units: bands x units per row of a pair (a wave's steps are counted in 32 bits); pct: per cent of the equal share dealt out up front
+// when the launch fills the chip, the rest is drawn from the counter (100: never); ws_stride: workspace doubles per wave.
+inline int plan_one_draw(int64_t P, int64_t max_waves, int64_t units, int pct, int64_t ws_stride, OneDrawPlan &o) {
+    o.waves = o.ws_waves = P < max_waves ? P : max_waves;
+    if (P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;            // (pair indices are 32-bit inside the kernels)
+    o.per = (P + o.waves - 1) / o.waves;
+    if (o.per > 0x1fffffff / units) return SK_ERR_UNSUPPORTED;
+    o.ws_doubles = o.waves * ws_stride;
+    o.queue = o.waves == max_waves && o.per >= 8 && pct < 100;
+    o.C0 = (int)(o.queue ? o.per * pct / 100 : o.per);
+    o.q_first = o.queue ? o.waves * (int64_t)o.C0 : P;
+    if (!o.queue) o.waves = (P + o.per - 1) / o.per;             // no more waves than the pairs need
     return SK_OK;
 }
 

@@ -556,39 +556,12 @@ int launch_adj_fused_linear_rows(const double *dXr, const double *dYt, int64_t A
     // the resident lane groups: 8 waves per CU (the kernel holds ~230 VGPRs, two waves per SIMD)
     const int wpc = knobs().adjf_wpc > 0 ? knobs().adjf_wpc : 8;
     const int64_t max_groups = (int64_t)device_cu_count() * wpc * G;
-    // pairs per lane group: see pick_chunk (paired batches: every pair has its own x, one pair per lane group)
-    int64_t PPG = pick_chunk(A, B, max_groups);
-    // paired batches of more pairs than resident lane groups: several consecutive pairs per lane group (the kernel stores and clears its
-    // sums at every pair end: PAIRED), up to 64 -- the skew's fill and the wave's prologue are then paid once per group, not per pair
-    int64_t ppp = 1;
-    if (B <= 0 && !yside) {
-        ppp = g.P / max_groups;
-        ppp = ppp < 1 ? 1 : (ppp > 64 ? 64 : ppp);
-        PPG = ppp;
-    }
+    // pairs per lane group, pairs per group of a paired batch, rows per launch: plan_adjoint_chunks (sk_wave_common.h)
+    AdjointChunks pc;
+    if (plan_adjoint_chunks(A, B, G, NUp, device_cu_count(), wpc, knobs().adjf_wpb, lds_bytes, !yside, force_nch, pc)) return SK_ERR_UNSUPPORTED;
+    const int64_t PPG = pc.PPG, ppp = pc.ppp, groups = pc.groups;
     if (epair) *epair = st.NNp + st.MMp;
-    if (force_nch > 0) PPG = (B + force_nch - 1) / force_nch;
-    else if (rows_per_launch) {   // see launch_adj_fused_rbf_rows (sk_wave_adj_fused_rbf.hip)
-        *rows_per_launch = 0;
-        const int wpb = wave_group(lds_bytes, max_groups / G, knobs().adjf_wpb).wpb;
-        const int64_t gpr = (int64_t)device_cu_count() * wpb * G;
-        const int64_t nr = gpr > 0 && max_groups % gpr == 0 ? max_groups / gpr : 0;
-        const int64_t nch = chunks_of(B, PPG);
-        if (B > 0 && nr >= 2 && !(A * nch == max_groups && nch % nr == 0 && B % nch == 0)) {
-            // several exactly-filling launches of max_groups / m rows with m chunks per a, shares by wave age rank (~0.9 of the equal
-            // split's time each), against the one launch above: rounds x chunk length; the best m, the smallest among equals
-            const int64_t single_rounds = (A * nch + max_groups - 1) / max_groups;
-            double best = (double)single_rounds * (double)PPG;
-            for (int64_t m = nr; m <= B && m <= max_groups; m += nr)
-                if (m >= nch && B % m == 0 && max_groups % m == 0 && B / m >= 4 * nr) {
-                    const int64_t rpl = max_groups / m, launches = (A + rpl - 1) / rpl;
-                    const double t = 0.9 * (double)launches * (double)(B / m);
-                    if (A >= rpl && t < best * 0.97) { best = t; *rows_per_launch = rpl; PPG = B / m; }
-                }
-        }
-    }
-    if (PPG > 0x3fffffff / NUp || g.P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;   // (pair indices are divided in 32 bits inside the kernel)
-    const int64_t groups = B > 0 ? A * chunks_of(B, PPG) : (g.P + ppp - 1) / ppp;
+    if (rows_per_launch) *rows_per_launch = pc.rows_per_launch;
     if (ppg_out) *ppg_out = (int)PPG;
     if (rows_out) *rows_out = L * RC;
     if (ycols_out) *ycols_out = 2 * NUp;
@@ -653,39 +626,23 @@ int launch_adj_fused_linear(const double *dXr, const double *dYt, int64_t A, int
     if (ycols_out) *ycols_out = ycols;
     if (yside ? !ypart : !tpart) return SK_OK;
     if (ypart && ypart_doubles < (size_t)g.P * ycols * FD) return SK_ERR_WORKSPACE;
-    // device-side rescue (sk_adj_fused_rescue.hip): the workspace starts with the swept upstream gradient (screened pairs NaN)
-    const double *sweep_scale = scale;
-    void *rws = nullptr;
-    size_t rws_bytes = 0;
-    if (rescue && rescue->ws) {
-        const size_t head = sizeof(double) * (size_t)((g.P + 1) / 2 * 2);
-        if (rescue->ws_bytes <= head) return SK_ERR_WORKSPACE;
-        rws = (char *)rescue->ws + head;
-        rws_bytes = rescue->ws_bytes - head;
-        if (rescue->kfinal) {
-            rc = launch_fused_screen(rescue->kfinal, scale, g.P, rescue->screen, (double *)rescue->ws, err, s);
-            if (rc != SK_OK) return rc;
-            sweep_scale = (const double *)rescue->ws;
-        }
-    }
+    const double *sweep_scale;
+    void *rws;
+    size_t rws_bytes;
+    if ((rc = arm_fused_rescue(rescue, scale, g.P, err, s, sweep_scale, rws, rws_bytes)) != SK_OK) return rc;
     if (per_launch <= 0 || B <= 0)
         return launch_adj_fused_linear_rows(dXr, dYt, A, B, Mrows, Ncp, g, edges, sweep_scale, tpart, tpart_doubles, err, ypart, yside, nullptr,
                                             nullptr, nullptr, nullptr, nullptr, B > 0 ? chunks_of(B, ppg) : 0, rescue, scale, rws, rws_bytes, s);
-    // several launches of per_launch rows each, all with the same chunks per a (so that tpart keeps one layout)
     const int64_t nch = chunks_of(B, ppg), slot = (int64_t)rows * FD;
     if (!yside && tpart_doubles < (size_t)(A * nch * slot)) return SK_ERR_WORKSPACE;
-    for (int64_t a0 = 0; a0 < A; a0 += per_launch) {
-        const int64_t An = A - a0 < per_launch ? A - a0 : per_launch;
+    const GramRows all{dXr, edges, sweep_scale, scale, yside ? nullptr : tpart, err, ypart};
+    const GramRowStrides strides{(int64_t)Mrows * FD, epair, nch * slot, (int64_t)ycols * FD};
+    return sweep_gram_rows(all, strides, A, B, per_launch, [&](const GramRows &r, int64_t An) {
         Geom gs = g;
         gs.P = An * B;
-        rc = launch_adj_fused_linear_rows(dXr + a0 * Mrows * FD, dYt, An, B, Mrows, Ncp, gs, edges + a0 * B * epair,
-                                          sweep_scale ? sweep_scale + a0 * B : nullptr, yside ? nullptr : tpart + a0 * nch * slot,
-                                          (size_t)(An * nch * slot), err ? err + a0 * B : nullptr,
-                                          ypart ? ypart + a0 * B * (int64_t)ycols * FD : nullptr, yside, nullptr, nullptr, nullptr, nullptr,
-                                          nullptr, nch, rescue, scale ? scale + a0 * B : nullptr, rws, rws_bytes, s);
-        if (rc != SK_OK) return rc;
-    }
-    return SK_OK;
+        return launch_adj_fused_linear_rows(r.X, dYt, An, B, Mrows, Ncp, gs, r.edges, r.sweep_scale, r.part, (size_t)(An * nch * slot), r.err, r.ypart,
+                                            yside, nullptr, nullptr, nullptr, nullptr, nullptr, nch, rescue, r.scale, rws, rws_bytes, s);
+    });
 }
 
 }  // namespace sk

@@ -25,6 +25,7 @@
 // Replaces, for RBFKernel on long or wide paths, sk_static_increments + sk_solve_fwd(EDGES) + sk_solve_adj + sk_static_adjoint,
 // i.e. sigkernel.py:419-502 (prep_backward) + :404-416.
 #include "sk_wave_common.h"
+#include "sk_pair_stream.h"   // plan_one_draw
 
 namespace sk {
 namespace {
@@ -1209,35 +1210,19 @@ int launch_amb(AdjMbParams prm, const AmbPlan &pl, void *ws, size_t ws_bytes, hi
         else return k_adj_fused_rbf_mb<DY, RC, FD, Y32>;
     }();
     static const int vgprs = variant_vgprs(kern, 256);
-    // resident waves per CU: whole workgroups of wpb waves by LDS, by registers, at most two per SIMD
-    const int wpb0 = wave_group(pl.lds_bytes, 1 << 20, knobs().adjmb_wpb).wpb;
-    int wpc = waves_by_vgprs((int)((160 * 1024) / (pl.lds_bytes * wpb0)) * wpb0, vgprs);
-    if (knobs().adjmb_wpc > 0 && wpc > knobs().adjmb_wpc) wpc = knobs().adjmb_wpc;
-    if (wpc > 8) wpc = 8;
-    if (wpc >= wpb0) wpc = wpc / wpb0 * wpb0;
-    if (wpc < 1) wpc = 1;
-    const int64_t max_waves = (int64_t)device_cu_count() * wpc;
-    int64_t waves = prm.P < max_waves ? prm.P : max_waves;
-    const int64_t per = (prm.P + waves - 1) / waves;
-    if (prm.P >= 0x7ff00000LL || per > 0x1fffffff / ((int64_t)prm.nb * prm.NUp)) return SK_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < (size_t)waves * (size_t)pl.ws_stride * sizeof(double) + 64) return SK_ERR_WORKSPACE;
+    const int wpc = one_draw_waves_per_cu(pl.lds_bytes, wave_group(pl.lds_bytes, 1 << 20, knobs().adjmb_wpb).wpb, vgprs, knobs().adjmb_wpc);
     const int pct = knobs().adjmb_q_static > 0 ? (knobs().adjmb_q_static > 100 ? 100 : knobs().adjmb_q_static) : 50;
-    if (waves == max_waves && per >= 8 && pct < 100) {
-        // the launch fills the chip: `pct` per cent of the equal share is dealt out up front, the rest is drawn pair by pair
-        prm.C0 = (int)(per * pct / 100);
-        prm.queue = reinterpret_cast<unsigned long long *>(static_cast<double *>(ws) + (size_t)waves * (size_t)pl.ws_stride);
-        prm.q_first = waves * (int64_t)prm.C0;
-        if (hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
-    } else {
-        waves = (prm.P + per - 1) / per;
-        prm.C0 = (int)per;
-        prm.queue = nullptr;
-        prm.q_first = prm.P;
-    }
-    prm.per = (int)per;
+    OneDrawPlan dp;
+    if (const int rc = plan_one_draw(prm.P, (int64_t)device_cu_count() * wpc, (int64_t)prm.nb * prm.NUp, pct, pl.ws_stride, dp)) return rc;
+    if (!ws || ws_bytes < (size_t)dp.ws_doubles * sizeof(double) + 64) return SK_ERR_WORKSPACE;
+    prm.C0 = dp.C0;
+    prm.q_first = dp.q_first;
+    prm.queue = dp.queue ? reinterpret_cast<unsigned long long *>(static_cast<double *>(ws) + dp.ws_doubles) : nullptr;
+    if (dp.queue && hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
+    prm.per = (int)dp.per;
     prm.ws = static_cast<double *>(ws);
     prm.ws_stride = pl.ws_stride;
-    prm.wg = wave_group(pl.lds_bytes, waves, knobs().adjmb_wpb);
+    prm.wg = wave_group(pl.lds_bytes, dp.waves, knobs().adjmb_wpb);
     const size_t lds_block = wave_group_lds(prm.wg);
     if (lds_block > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_block);
@@ -1286,19 +1271,9 @@ int launch_adj_fused_rbf_mb(const double *Xr, const void *Yt_any, int yt_f32, in
     prm.naive = g.naive;
     // device-side rescue (sk_adj_fused_rescue.hip): the workspace starts with the swept upstream gradient (screened pairs NaN: the
     // sweep stores zeros for them), and their exact, stored-grid share is added to gpart afterwards -- one pair per chunk here
-    void *rws = nullptr;
-    size_t rws_bytes = 0;
-    if (rescue && rescue->ws && Yt64) {
-        const size_t head = sizeof(double) * (size_t)((g.P + 1) / 2 * 2);
-        if (rescue->ws_bytes <= head) return SK_ERR_WORKSPACE;
-        rws = (char *)rescue->ws + head;
-        rws_bytes = rescue->ws_bytes - head;
-        if (rescue->kfinal) {
-            const int rc = launch_fused_screen(rescue->kfinal, scale, g.P, rescue->screen, (double *)rescue->ws, err, s);
-            if (rc != SK_OK) return rc;
-            prm.scale = (const double *)rescue->ws;
-        }
-    }
+    void *rws;
+    size_t rws_bytes;
+    if (const int rc = arm_fused_rescue(Yt64 ? rescue : nullptr, scale, g.P, err, s, prm.scale, rws, rws_bytes)) return rc;
     int rc;
     if (y32 && g.dyadic == 0) return SK_ERR_UNSUPPORTED;
     if (y32) rc = g.dyadic == 1 ? launch_amb<1, 2, 16, true>(prm, pl, ws, ws_bytes, s) : launch_amb<2, 1, 16, true>(prm, pl, ws, ws_bytes, s);
@@ -1306,9 +1281,8 @@ int launch_adj_fused_rbf_mb(const double *Xr, const void *Yt_any, int yt_f32, in
     else if (g.dyadic == 1) rc = pl.fd == 8 ? launch_amb<1, 2, 8>(prm, pl, ws, ws_bytes, s) : launch_amb<1, 2, 16>(prm, pl, ws, ws_bytes, s);
     else rc = pl.fd == 8 ? launch_amb<2, 1, 8>(prm, pl, ws, ws_bytes, s) : launch_amb<2, 1, 16>(prm, pl, ws, ws_bytes, s);
     if (rc != SK_OK || !rws) return rc;
-    ChunkSplit cs{};          // one pair per chunk, slot = pair
-    cs.nr = 1; cs.nch = (int)(B > 0 ? B : 1); cs.cpr = cs.nch; cs.gpr = (int64_t)1 << 62; cs.size[0] = 1; cs.off[0] = 0;
-    return launch_fused_rescue(1, Xr, Yt64, scale, err, rescue->tol, gpart, nullptr, A, B, Mrows, Ncp, D, g, (int)rows, pl.fd + 2, 0, inv_sigma, cs,
+    return launch_fused_rescue(1, Xr, Yt64, scale, err, rescue->tol, gpart, nullptr, A, B, Mrows, Ncp, D, g, (int)rows, pl.fd + 2, 0, inv_sigma,
+                               one_pair_chunks(B),
                                g.P, rws, rws_bytes, s, pl.fd, n0, 2 * pl.NUp, rescue->kfinal);
 }
 
@@ -1329,19 +1303,9 @@ int launch_adj_fused_linear_mb(const double *dXr, const double *dYt, int64_t A, 
     prm.P = g.P; prm.B = B; prm.Mrows = Mrows; prm.Ncp = Ncp; prm.Mc = g.Mc; prm.Nc = g.Nc; prm.NUp = pl.NUp; prm.nb = pl.nb;
     prm.inv_sigma = 0.0;
     prm.naive = g.naive;
-    void *rws = nullptr;
-    size_t rws_bytes = 0;
-    if (rescue && rescue->ws) {
-        const size_t head = sizeof(double) * (size_t)((g.P + 1) / 2 * 2);
-        if (rescue->ws_bytes <= head) return SK_ERR_WORKSPACE;
-        rws = (char *)rescue->ws + head;
-        rws_bytes = rescue->ws_bytes - head;
-        if (rescue->kfinal) {
-            const int rc = launch_fused_screen(rescue->kfinal, scale, g.P, rescue->screen, (double *)rescue->ws, err, s);
-            if (rc != SK_OK) return rc;
-            prm.scale = (const double *)rescue->ws;
-        }
-    }
+    void *rws;
+    size_t rws_bytes;
+    if (const int rc = arm_fused_rescue(rescue, scale, g.P, err, s, prm.scale, rws, rws_bytes)) return rc;
     int rc;
     if (pl.fd == 8)
         rc = g.dyadic == 0 ? launch_amb<0, 4, 8, false, 0>(prm, pl, ws, ws_bytes, s)
@@ -1350,9 +1314,7 @@ int launch_adj_fused_linear_mb(const double *dXr, const double *dYt, int64_t A, 
         rc = g.dyadic == 0 ? launch_amb<0, 4, 16, false, 0>(prm, pl, ws, ws_bytes, s)
            : g.dyadic == 1 ? launch_amb<1, 2, 16, false, 0>(prm, pl, ws, ws_bytes, s) : launch_amb<2, 1, 16, false, 0>(prm, pl, ws, ws_bytes, s);
     if (rc != SK_OK || !rws) return rc;
-    ChunkSplit cs{};          // one pair per chunk, slot = pair
-    cs.nr = 1; cs.nch = (int)(B > 0 ? B : 1); cs.cpr = cs.nch; cs.gpr = (int64_t)1 << 62; cs.size[0] = 1; cs.off[0] = 0;
-    return launch_fused_rescue(0, dXr, dYt, scale, err, rescue->tol, gpart, nullptr, A, B, Mrows, Ncp, D, g, (int)rows, pl.fd, 0, 0.0, cs, g.P, rws,
+    return launch_fused_rescue(0, dXr, dYt, scale, err, rescue->tol, gpart, nullptr, A, B, Mrows, Ncp, D, g, (int)rows, pl.fd, 0, 0.0, one_pair_chunks(B), g.P, rws,
                                rws_bytes, s, pl.fd, nullptr, 0, rescue->kfinal);
 }
 

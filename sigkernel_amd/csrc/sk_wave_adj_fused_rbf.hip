@@ -787,7 +787,7 @@ namespace {
 int launch_adj_fused_rbf_rows(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
                               double inv_sigma, const double *edges, const double *scale, double *gpart, size_t gpart_doubles, double *err,
                               double *ypart, int ys, int *ppg_out, int *rows_out, int *outw_out, int *ycols_out, int64_t *rows_per_launch,
-                              int64_t force_nch, const FusedRescue *rescue, const double *scale_orig, void *rescue_ws, size_t rescue_ws_bytes,
+                              int64_t *epair, int64_t force_nch, const FusedRescue *rescue, const double *scale_orig, void *rescue_ws, size_t rescue_ws_bytes,
                               hipStream_t s) {
     // ys: 0 first-argument sums, 1 both, 2 the second-argument sums only (the kernel's YS)
     const int DY = g.dyadic;
@@ -826,39 +826,12 @@ int launch_adj_fused_rbf_rows(const double *Xr, const double *Yt, int64_t A, int
     const int n_cu = device_cu_count();
     const int wpc = knobs().adjr_wpc > 0 ? knobs().adjr_wpc : 8;
     const int64_t max_groups = (int64_t)n_cu * wpc * G;
-    // pairs per lane group: see pick_chunk (paired batches: every pair has its own x, one pair per lane group)
-    int64_t PPG = pick_chunk(A, B, max_groups);
-    // paired batches of more pairs than resident lane groups (dims <= 4): several consecutive pairs per lane group (PAIRED)
-    int64_t ppp = 1;
-    if (B <= 0 && ys == 0 && ND == 4) {
-        ppp = g.P / max_groups;
-        ppp = ppp < 1 ? 1 : (ppp > 64 ? 64 : ppp);
-        PPG = ppp;
-    }
-    if (force_nch > 0) PPG = (B + force_nch - 1) / force_nch;
-    else if (rows_per_launch) {
-        // Shares by wave age rank (ChunkSplit) need a launch that fills the chip exactly, with the chunks of an a a multiple of
-        // the ranks: when the equal split does not give that, the caller sweeps the rows in several such launches.
-        *rows_per_launch = 0;
-        const int wpb = wave_group(lds_bytes, max_groups / G, knobs().adjr_wpb).wpb;
-        const int64_t gpr = (int64_t)n_cu * wpb * G;
-        const int64_t nr = gpr > 0 && max_groups % gpr == 0 ? max_groups / gpr : 0;
-        const int64_t nch = chunks_of(B, PPG);
-        if (B > 0 && nr >= 2 && !(A * nch == max_groups && nch % nr == 0 && B % nch == 0)) {
-            // several exactly-filling launches of max_groups / m rows with m chunks per a, shares by wave age rank (~0.9 of the equal
-            // split's time each), against the one launch above: rounds x chunk length; the best m, the smallest among equals
-            const int64_t single_rounds = (A * nch + max_groups - 1) / max_groups;
-            double best = (double)single_rounds * (double)PPG;
-            for (int64_t m = nr; m <= B && m <= max_groups; m += nr)
-                if (m >= nch && B % m == 0 && max_groups % m == 0 && B / m >= 4 * nr) {
-                    const int64_t rpl = max_groups / m, launches = (A + rpl - 1) / rpl;
-                    const double t = 0.9 * (double)launches * (double)(B / m);
-                    if (A >= rpl && t < best * 0.97) { best = t; *rows_per_launch = rpl; PPG = B / m; }
-                }
-        }
-    }
-    if (PPG > 0x3fffffff / NUp || g.P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;   // (pair indices are divided in 32 bits inside the kernel)
-    const int64_t groups = B > 0 ? A * chunks_of(B, PPG) : (g.P + ppp - 1) / ppp;
+    // pairs per lane group, pairs per group of a paired batch (the PAIRED form: dims <= 4), rows per launch: plan_adjoint_chunks
+    AdjointChunks pc;
+    if (plan_adjoint_chunks(A, B, G, NUp, n_cu, wpc, knobs().adjr_wpb, lds_bytes, ys == 0 && ND == 4, force_nch, pc)) return SK_ERR_UNSUPPORTED;
+    const int64_t PPG = pc.PPG, ppp = pc.ppp, groups = pc.groups;
+    if (epair) *epair = st.NNp + st.MMp;
+    if (rows_per_launch) *rows_per_launch = pc.rows_per_launch;
     const int OUTW = ND + 2;
     if (ppg_out) *ppg_out = (int)PPG;
     if (rows_out) *rows_out = L * RC + 1;
@@ -918,17 +891,17 @@ int launch_adj_fused_rbf(const double *Xr, const double *Yt, int64_t A, int64_t 
                          double *ypart, size_t ypart_doubles, int want_yside, int *ppg_out, int *rows_out, int *outw_out, int *ycols_out,
                          const FusedRescue *rescue, hipStream_t s) {
     int ppg = 0, rows = 0, outw = 0, ycols = 0;
-    int64_t per_launch = 0;
+    int64_t per_launch = 0, epair = 0;
     const bool yside = want_yside || ypart;
     // the form of the sweep: both sets of sums (dims <= 4) unless the caller hands over no gpart; a pure size query (neither array)
     // answers for the form that exists -- the sizes it returns for the second-argument sums (*ycols_out) are the same in both
     int ys = !yside ? 0 : ((D > 4 || (ypart && !gpart)) ? 2 : 1);
     int rc = launch_adj_fused_rbf_rows(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, edges, scale, nullptr, 0, err, nullptr, ys, &ppg, &rows, &outw,
-                                       yside ? &ycols : nullptr, &per_launch, 0, nullptr, nullptr, nullptr, 0, s);
+                                       yside ? &ycols : nullptr, &per_launch, &epair, 0, nullptr, nullptr, nullptr, 0, s);
     if (rc == SK_ERR_UNSUPPORTED && ys == 1 && !gpart && !ypart) {
         ys = 2;
         rc = launch_adj_fused_rbf_rows(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, edges, scale, nullptr, 0, err, nullptr, ys, &ppg, &rows, &outw,
-                                       &ycols, &per_launch, 0, nullptr, nullptr, nullptr, 0, s);
+                                       &ycols, &per_launch, &epair, 0, nullptr, nullptr, nullptr, 0, s);
     }
     if (rc != SK_OK) return rc;
     if (ppg_out) *ppg_out = ppg;
@@ -938,41 +911,24 @@ int launch_adj_fused_rbf(const double *Xr, const double *Yt, int64_t A, int64_t 
     if (!gpart && !ypart) return SK_OK;      // (gpart NULL with ypart: the second-argument sums only)
     const int yw = yw_of(D <= 4 ? 4 : 8);
     if (ypart && ypart_doubles < (size_t)g.P * ycols * yw) return SK_ERR_WORKSPACE;
-    // device-side rescue (sk_adj_fused_rescue.hip): the workspace starts with the swept upstream gradient (screened pairs NaN)
-    const double *sweep_scale = scale;
-    void *rws = nullptr;
-    size_t rws_bytes = 0;
-    if (rescue && rescue->ws) {
-        const size_t head = sizeof(double) * (size_t)((g.P + 1) / 2 * 2);
-        if (rescue->ws_bytes <= head) return SK_ERR_WORKSPACE;
-        rws = (char *)rescue->ws + head;
-        rws_bytes = rescue->ws_bytes - head;
-        if (rescue->kfinal) {
-            rc = launch_fused_screen(rescue->kfinal, scale, g.P, rescue->screen, (double *)rescue->ws, err, s);
-            if (rc != SK_OK) return rc;
-            sweep_scale = (const double *)rescue->ws;
-        }
-    }
+    const double *sweep_scale;
+    void *rws;
+    size_t rws_bytes;
+    if ((rc = arm_fused_rescue(rescue, scale, g.P, err, s, sweep_scale, rws, rws_bytes)) != SK_OK) return rc;
     if (per_launch <= 0 || B <= 0)
         return launch_adj_fused_rbf_rows(Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, edges, sweep_scale, gpart, gpart_doubles, err, ypart, ys, nullptr,
-                                         nullptr, nullptr, nullptr, nullptr, B > 0 ? chunks_of(B, ppg) : 0, rescue, scale, rws, rws_bytes, s);
-    // several launches of per_launch rows each, all with the same chunks per a (so that gpart keeps one layout)
+                                         nullptr, nullptr, nullptr, nullptr, nullptr, B > 0 ? chunks_of(B, ppg) : 0, rescue, scale, rws, rws_bytes, s);
     const int64_t nch = chunks_of(B, ppg);
     const int64_t slot = (int64_t)rows * outw;
     if (gpart && gpart_doubles < (size_t)(A * nch * slot)) return SK_ERR_WORKSPACE;
-    const Strip st = strip_geom(rbf_edge_geom(g), 8);
-    const int64_t Epair = (int64_t)st.NUp * (2 << g.dyadic) + (int64_t)(1 << st.logL) * st.RC * (1 << g.dyadic);   // edge doubles per pair
-    for (int64_t a0 = 0; a0 < A; a0 += per_launch) {
-        const int64_t An = A - a0 < per_launch ? A - a0 : per_launch;
+    const GramRows all{Xr, edges, sweep_scale, scale, gpart, err, ypart};
+    const GramRowStrides strides{(int64_t)Mrows * RFD, epair, nch * slot, (int64_t)ycols * yw};
+    return sweep_gram_rows(all, strides, A, B, per_launch, [&](const GramRows &r, int64_t An) {
         Geom gs = g;
         gs.P = An * B;
-        rc = launch_adj_fused_rbf_rows(Xr + a0 * Mrows * RFD, Yt, An, B, Mrows, Ncp, D, gs, inv_sigma, edges + a0 * B * Epair,
-                                       sweep_scale ? sweep_scale + a0 * B : nullptr, gpart ? gpart + a0 * nch * slot : nullptr, (size_t)(An * nch * slot),
-                                       err ? err + a0 * B : nullptr, ypart ? ypart + a0 * B * (int64_t)ycols * yw : nullptr, ys, nullptr, nullptr,
-                                       nullptr, nullptr, nullptr, nch, rescue, scale ? scale + a0 * B : nullptr, rws, rws_bytes, s);
-        if (rc != SK_OK) return rc;
-    }
-    return SK_OK;
+        return launch_adj_fused_rbf_rows(r.X, Yt, An, B, Mrows, Ncp, D, gs, inv_sigma, r.edges, r.sweep_scale, r.part, (size_t)(An * nch * slot), r.err,
+                                         r.ypart, ys, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nch, rescue, r.scale, rws, rws_bytes, s);
+    });
 }
 
 }  // namespace sk

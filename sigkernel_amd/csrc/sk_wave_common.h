@@ -532,6 +532,9 @@ inline void rank_override(const RankW &family, int nr, double (&w)[4]) {
         for (int r = 0; r < nr; ++r) w[r] = o.w[r] / tot;
 }
 
+// measured finishing times with equal shares, per number of ranks (see above); SK_RANK_W="50,30,20" overrides (per cent)
+constexpr double RANK_SHARES[5][4] = {{1, 0, 0, 0}, {1, 0, 0, 0}, {0.66, 0.34, 0, 0}, {0.53, 0.30, 0.17, 0}, {0.40, 0.27, 0.19, 0.14}};
+
 struct RankSplit {
     int nranks;              // 1: every wave gets cnt[0] pairs per lane group (the plain equal split)
     int waves_per_rank;      // #CU * waves per workgroup
@@ -550,10 +553,8 @@ inline RankSplit rank_split(int64_t P, int G, int64_t waves, int64_t resident, i
     const int64_t wpr = (int64_t)n_cu * wpb;
     const int nr = wpr > 0 ? (int)(waves / wpr) : 0;
     if (waves != resident || nr < 2 || nr > 4 || (int64_t)nr * wpr != waves) return rs;
-    // measured finishing times with equal shares, per number of ranks (see above); SK_RANK_W="50,30,20" overrides (per cent)
-    static constexpr double dflt[5][4] = {{1, 0, 0, 0}, {1, 0, 0, 0}, {0.66, 0.34, 0, 0}, {0.53, 0.30, 0.17, 0}, {0.40, 0.27, 0.19, 0.14}};
     double w[4];
-    for (int r = 0; r < 4; ++r) w[r] = table ? table[nr][r] : dflt[nr][r];
+    for (int r = 0; r < 4; ++r) w[r] = table ? table[nr][r] : RANK_SHARES[nr][r];
     rank_override(family, nr, w);
     const int64_t T = (P + wpr * G - 1) / (wpr * G);   // pairs per lane group summed over the ranks of one SIMD slot
     if (T < 4 * nr) return rs;                          // too few pairs for the split to matter
@@ -613,9 +614,8 @@ inline ChunkSplit chunk_split(int64_t A, int64_t B, int64_t PPG, int64_t max_gro
     if (B <= 0 || gpr <= 0 || cs.uneven || A * nch != max_groups || max_groups % gpr) return cs;
     const int nr = (int)(max_groups / gpr);
     if (nr < 2 || nr > 4 || nch % nr || PPG < 4 * nr) return cs;
-    static constexpr double dflt[5][4] = {{1, 0, 0, 0}, {1, 0, 0, 0}, {0.66, 0.34, 0, 0}, {0.53, 0.30, 0.17, 0}, {0.40, 0.27, 0.19, 0.14}};
     double w[4];
-    for (int r = 0; r < 4; ++r) w[r] = dflt[nr][r];
+    for (int r = 0; r < 4; ++r) w[r] = RANK_SHARES[nr][r];
     rank_override(family, nr, w);
     const int cpr = (int)(nch / nr);
     const int64_t T = B / cpr;            // pairs of one a per "column" of ranks: sum of the sizes
@@ -629,6 +629,82 @@ inline ChunkSplit chunk_split(int64_t A, int64_t B, int64_t PPG, int64_t max_gro
     }
     cs.nr = nr; cs.cpr = cpr; cs.gpr = gpr;
     return cs;
+}
+inline ChunkSplit one_pair_chunks(int64_t B) {   // one pair per chunk, slot = pair: the multi-band adjoints' split, for launch_fused_rescue
+    ChunkSplit cs{};
+    cs.nr = 1; cs.nch = (int)(B > 0 ? B : 1); cs.cpr = cs.nch; cs.gpr = (int64_t)1 << 62; cs.size[0] = 1; cs.off[0] = 0;
+    return cs;
+}
+
+// The launch arithmetic of the one-band fused adjoints: an A x B Gram (B > 0) or a paired batch of A pairs (B == 0) on lane groups of
+// which n_cu wpc G are resident.  No HIP call, no global: CU count, waves per CU, the family's waves-per-workgroup knob and a wave's LDS
+// bytes are arguments (exported as sk_plan_adjoint_chunks; tests/test_adjoint_launch_plans.py holds it against a restatement).
+struct AdjointChunks {
+    int64_t PPG, ppp;          // the longest chunk, pairs per lane group (pick_chunk); paired batches: consecutive pairs per lane group
+    int64_t rows_per_launch;   // > 0: the Gram is swept in launches of this many rows (sweep_gram_rows); 0: one launch
+    int64_t groups;            // lane groups of all the launches together
+};
+// paired_form: the variant sweeps several consecutive pairs per lane group (it stores and clears its sums at every pair end), up to 64,
+// when a paired batch has more pairs than resident lane groups: the skew's fill and the wave's prologue are paid once per group.
+// force_nch > 0: the chunks per row are the caller's.  SK_ERR_UNSUPPORTED: pair indices are divided in 32 bits inside the kernels.
+inline int plan_adjoint_chunks(int64_t A, int64_t B, int G, int NUp, int n_cu, int wpc, int wpb_knob, size_t lds_bytes, bool paired_form,
+                               int64_t force_nch, AdjointChunks &o) {
+    const int64_t P = B > 0 ? A * B : A, max_groups = (int64_t)n_cu * wpc * G;
+    o.PPG = pick_chunk(A, B, max_groups);
+    o.ppp = 1;
+    o.rows_per_launch = 0;
+    if (B <= 0 && paired_form) {
+        o.ppp = P / max_groups;
+        o.PPG = o.ppp = o.ppp < 1 ? 1 : (o.ppp > 64 ? 64 : o.ppp);
+    }
+    if (force_nch > 0) o.PPG = (B + force_nch - 1) / force_nch;
+    else {
+        // Shares by wave age rank (ChunkSplit) need a launch that fills the chip exactly, with the chunks of an a a multiple of
+        // the ranks: when the equal split does not give that, the caller sweeps the rows in several such launches.
+        const int wpb = wave_group(lds_bytes, max_groups / G, wpb_knob).wpb;
+        const int64_t gpr = (int64_t)n_cu * wpb * G;
+        const int64_t nr = gpr > 0 && max_groups % gpr == 0 ? max_groups / gpr : 0;
+        const int64_t nch = chunks_of(B, o.PPG);
+        if (B > 0 && nr >= 2 && !(A * nch == max_groups && nch % nr == 0 && B % nch == 0)) {
+            // several exactly-filling launches of max_groups / m rows with m chunks per a, shares by wave age rank (~0.9 of the equal
+            // split's time each), against the one launch above: rounds x chunk length; the best m, the smallest among equals
+            const int64_t single_rounds = (A * nch + max_groups - 1) / max_groups;
+            double best = (double)single_rounds * (double)o.PPG;
+            for (int64_t m = nr; m <= B && m <= max_groups; m += nr)
+                if (m >= nch && B % m == 0 && max_groups % m == 0 && B / m >= 4 * nr) {
+                    const int64_t rpl = max_groups / m, launches = (A + rpl - 1) / rpl;
+                    const double t = 0.9 * (double)launches * (double)(B / m);
+                    if (A >= rpl && t < best * 0.97) { best = t; o.rows_per_launch = rpl; o.PPG = B / m; }
+                }
+        }
+    }
+    if (o.PPG > 0x3fffffff / NUp || P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;
+    o.groups = B > 0 ? A * chunks_of(B, o.PPG) : (P + o.ppp - 1) / o.ppp;
+    return SK_OK;
+}
+
+// A Gram swept in launches of rows_per_launch rows, all with the same chunks per row (the partial sums keep one layout): launch(r, An)
+// sweeps the An rows that r points at.  Strides in doubles: staged x per path; edges and second-argument sums per pair; partial sums
+// per row (a slot x the chunks of a row).
+struct GramRows {
+    const double *X, *edges, *sweep_scale, *scale;   // (the upstream gradient as swept / as given; nullable, as the three below)
+    double *part, *err, *ypart;
+};
+struct GramRowStrides { int64_t x, edge, part, ypart; };
+template <class Launch>
+int sweep_gram_rows(GramRows r, const GramRowStrides &st, int64_t A, int64_t B, int64_t rows_per_launch, Launch launch) {
+    for (int64_t a0 = 0; a0 < A; a0 += rows_per_launch) {
+        const int64_t An = A - a0 < rows_per_launch ? A - a0 : rows_per_launch;
+        if (const int rc = launch(r, An)) return rc;
+        r.X += An * st.x;
+        if (r.edges) r.edges += An * B * st.edge;
+        if (r.sweep_scale) r.sweep_scale += An * B;
+        if (r.scale) r.scale += An * B;
+        if (r.part) r.part += An * st.part;
+        if (r.err) r.err += An * B;
+        if (r.ypart) r.ypart += An * B * st.ypart;
+    }
+    return SK_OK;
 }
 
 // device (per lane): lane group gi -> its first pair, its slot in the partial-sum array, and the pairs it sweeps

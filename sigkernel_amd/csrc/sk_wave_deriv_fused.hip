@@ -16,6 +16,7 @@
 // contraction: the sums cancel eight orders of magnitude and their rounding is part of the result the fixtures pin.
 // Scope: fp64, dyadic <= 2, path dim <= 8, any M, second path of N >= 126 points (rows of >= 64 units).
 #include "sk_wave_common.h"
+#include "sk_pair_stream.h"   // plan_one_draw
 
 namespace sk {
 namespace {
@@ -670,34 +671,19 @@ template <int DY, int KIND, int FD, bool LDSB, bool SHIFT>
 int launch_df(DerivFusedParams prm, const DfPlan &pl, void *ws, size_t ws_bytes, hipStream_t s) {
     auto kern = k_deriv_fused<DY, KIND, FD, LDSB, SHIFT>;
     static const int vgprs = variant_vgprs(kern, 256);
-    const int wpb0 = wave_group(pl.lds_bytes, 1 << 20, knobs().derivf_wpb).wpb;
-    int wpc = waves_by_vgprs((int)((160 * 1024) / (pl.lds_bytes * wpb0)) * wpb0, vgprs);
-    if (knobs().derivf_wpc > 0 && wpc > knobs().derivf_wpc) wpc = knobs().derivf_wpc;
-    if (wpc > 8) wpc = 8;
-    if (wpc >= wpb0) wpc = wpc / wpb0 * wpb0;
-    if (wpc < 1) wpc = 1;
-    const int64_t P = prm.P;
-    const int64_t max_waves = (int64_t)device_cu_count() * wpc;
-    int64_t waves = P < max_waves ? P : max_waves;
-    if (P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;
-    const int64_t per = (P + waves - 1) / waves;
-    if (per > 0x1fffffff / ((int64_t)prm.nb * prm.NUp)) return SK_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < (size_t)waves * (size_t)pl.ws_stride * sizeof(double) + 64) return SK_ERR_WORKSPACE;
+    const int wpc = one_draw_waves_per_cu(pl.lds_bytes, wave_group(pl.lds_bytes, 1 << 20, knobs().derivf_wpb).wpb, vgprs, knobs().derivf_wpc);
+    // half the equal share up front when the launch fills the chip
+    OneDrawPlan dp;
+    if (const int rc = plan_one_draw(prm.P, (int64_t)device_cu_count() * wpc, (int64_t)prm.nb * prm.NUp, 50, pl.ws_stride, dp)) return rc;
+    if (!ws || ws_bytes < (size_t)dp.ws_doubles * sizeof(double) + 64) return SK_ERR_WORKSPACE;
     double *w = static_cast<double *>(ws);
-    if (waves == max_waves && per >= 8) {   // the launch fills the chip: half the equal share up front, the rest drawn pair by pair
-        prm.C0 = (int)(per / 2);
-        prm.queue = reinterpret_cast<unsigned long long *>(w + (size_t)waves * (size_t)pl.ws_stride);
-        prm.q_first = waves * (int64_t)prm.C0;
-        if (hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
-    } else {
-        waves = (P + per - 1) / per;
-        prm.C0 = (int)per;
-        prm.queue = nullptr;
-        prm.q_first = P;
-    }
+    prm.C0 = dp.C0;
+    prm.q_first = dp.q_first;
+    prm.queue = dp.queue ? reinterpret_cast<unsigned long long *>(w + dp.ws_doubles) : nullptr;
+    if (dp.queue && hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
     prm.ws = w;
     prm.ws_stride = pl.ws_stride;
-    prm.wg = wave_group(pl.lds_bytes, waves, knobs().derivf_wpb);
+    prm.wg = wave_group(pl.lds_bytes, dp.waves, knobs().derivf_wpb);
     const size_t lds_block = wave_group_lds(prm.wg);
     if (lds_block > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_block);

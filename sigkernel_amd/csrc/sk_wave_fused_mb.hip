@@ -31,6 +31,7 @@
 // the caller may swap the arguments when the first path is the longer one: the kernel is symmetric).
 // Replaces, for LinearKernel / RBFKernel on long or wide paths, static_kernels.py:26-33 / :58-73 + sigkernel.py:362-382.
 #include "sk_wave_common.h"
+#include "sk_pair_stream.h"   // plan_one_draw
 
 namespace sk {
 namespace {
@@ -834,11 +835,10 @@ int launch_mb_one(FusedMbParams prm, int64_t P, size_t lds_bytes, int waves_per_
     static const int vgprs = variant_vgprs(kern, 256);
     waves_per_cu = waves_by_vgprs(waves_per_cu, vgprs);
     const int64_t max_waves = (int64_t)device_cu_count() * waves_per_cu;
-    int64_t waves = P < max_waves ? P : max_waves;
-    if (P >= 0x7ff00000LL) return SK_ERR_UNSUPPORTED;            // (pair indices are 32-bit inside the kernel)
-    int64_t per = (P + waves - 1) / waves;                       // the equal share, pairs per wave
-    if (per > 0x1fffffff / ((int64_t)prm.nb * prm.NUp)) return SK_ERR_UNSUPPORTED;
     const int pct = knobs().fusedmb_q_static > 0 ? (knobs().fusedmb_q_static > 100 ? 100 : knobs().fusedmb_q_static) : 50;
+    OneDrawPlan dp;
+    if (const int rc = plan_one_draw(P, max_waves, (int64_t)prm.nb * prm.NUp, pct, prm.ws_stride, dp)) return rc;
+    const int64_t waves = prm.split ? dp.ws_waves : dp.waves;      // (split mode: every position is a ticket, all resident waves run)
     if (prm.split) {
         // every position is a ticket: [per-wave rows (only their chunk of ones is used)][item rows][progress counters][the counter]
         if constexpr (!SPLIT) return SK_ERR_UNSUPPORTED;
@@ -855,22 +855,16 @@ int launch_mb_one(FusedMbParams prm, int64_t P, size_t lds_bytes, int waves_per_
         // resident waves turn out to be, so that the caller finds it without knowing the layout)
         prm.status = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(ws) + (ws_bytes & ~(size_t)7)) - 1;
         if (hipMemsetAsync(prm.status, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
-    } else if (!ws || ws_bytes < (size_t)waves * (size_t)prm.ws_stride * sizeof(double) + 64) {
+    } else if (!ws || ws_bytes < (size_t)dp.ws_doubles * sizeof(double) + 64) {
         return SK_ERR_WORKSPACE;
-    } else if (waves == max_waves && per >= 8 && pct < 100) {
-        // the launch fills the chip: `pct` per cent of the equal share is dealt out up front, the rest is drawn pair by pair
-        prm.C0 = (int)(per * pct / 100);
-        prm.queue = reinterpret_cast<unsigned long long *>(ws + (size_t)waves * (size_t)prm.ws_stride);
-        prm.q_first = waves * (int64_t)prm.C0;
-        if (hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
     } else {
-        waves = (P + per - 1) / per;
-        prm.C0 = (int)per;
-        prm.queue = nullptr;
-        prm.q_first = P;
+        prm.C0 = dp.C0;
+        prm.q_first = dp.q_first;
+        prm.queue = dp.queue ? reinterpret_cast<unsigned long long *>(ws + dp.ws_doubles) : nullptr;
+        if (dp.queue && hipMemsetAsync(prm.queue, 0, sizeof(unsigned long long), s) != hipSuccess) return SK_ERR_LAUNCH;
     }
     prm.wg = wave_group(lds_bytes, waves, knobs().fusedmb_wpb);
-    prm.PPW = (int)per;
+    prm.PPW = (int)dp.per;
     prm.n_steps = 0;
     prm.ws = ws;
     const size_t lds_block = wave_group_lds(prm.wg);

@@ -70,6 +70,27 @@ def test_argument_errors_are_reported_without_a_device():
     assert lib.sk_linear_adjoint_fused_f64(p, p, 1, 2, 256, 4, 4, 16, 1, 0, p, None, p, 64, p, None, 0, None, None, None, p, 1e3, 1e-8, None, 0, None) == 1   # forward values without a rescue workspace
     assert lib.sk_linear_adjoint_fused_f64(p, p, 1, 2, 256, 4, 4, 16, 1, 0, p, None, None, 0, None, p, 64, None, None, None, None, 0.0, 0.0, None, 0, None) == 1   # second-argument sums without a residual array
     assert lib.sk_fused_rescue_workspace_bytes(1, 100, 63, 63, 2, 4) > 0 and lib.sk_fused_rescue_workspace_bytes(2, 100, 63, 63, 2, 4) == 0
+    # the host-only launch plans: (A, B, G, NUp, n_cu, wpc, wpb knob, LDS bytes, paired form, forced chunks, plan[5])
+    assert lib.sk_plan_adjoint_chunks(64, 64, 2, 16, 256, 8, 0, 20000, 1, 0, None) == 1                  # no plan array
+    assert lib.sk_plan_adjoint_chunks(0, 64, 2, 16, 256, 8, 0, 20000, 1, 0, p) == 1                      # no rows
+    assert lib.sk_plan_adjoint_chunks(64, -1, 2, 16, 256, 8, 0, 20000, 1, 0, p) == 1                     # B < 0
+    assert lib.sk_plan_adjoint_chunks(64, 64, 0, 16, 256, 8, 0, 20000, 1, 0, p) == 1                     # no lane group
+    assert lib.sk_plan_adjoint_chunks(64, 64, 2, 12, 256, 8, 0, 20000, 1, 0, p) == 1                     # units no multiple of a line
+    assert lib.sk_plan_adjoint_chunks(64, 64, 2, 16, 0, 8, 0, 20000, 1, 0, p) == 1                       # no compute unit
+    assert lib.sk_plan_adjoint_chunks(64, 64, 2, 16, 256, 0, 0, 20000, 1, 0, p) == 1                     # no resident wave
+    assert lib.sk_plan_adjoint_chunks(64, 64, 2, 16, 256, 8, 0, 0, 1, 0, p) == 1                         # no LDS
+    assert lib.sk_plan_adjoint_chunks(64, 0, 2, 16, 256, 8, 0, 20000, 1, 4, p) == 1                      # chunks per row of a paired batch
+    # (P, LDS bytes, waves per workgroup, VGPRs, wpc knob, n_cu, units, pct, workspace stride, plan[7])
+    assert lib.sk_plan_one_draw(100, 20000, 4, 256, 0, 256, 80, 50, 1000, None) == 1                     # no plan array
+    assert lib.sk_plan_one_draw(0, 20000, 4, 256, 0, 256, 80, 50, 1000, p) == 1                          # no pair
+    assert lib.sk_plan_one_draw(100, 0, 4, 256, 0, 256, 80, 50, 1000, p) == 1                            # no LDS
+    assert lib.sk_plan_one_draw(100, 200000, 4, 256, 0, 256, 80, 50, 1000, p) == 1                       # more LDS than a CU has
+    assert lib.sk_plan_one_draw(100, 20000, 5, 256, 0, 256, 80, 50, 1000, p) == 1                        # five waves per workgroup
+    assert lib.sk_plan_one_draw(100, 20000, 4, 0, 0, 256, 80, 50, 1000, p) == 1                          # no registers
+    assert lib.sk_plan_one_draw(100, 20000, 4, 256, 0, 0, 80, 50, 1000, p) == 1                          # no compute unit
+    assert lib.sk_plan_one_draw(100, 20000, 4, 256, 0, 256, 0, 50, 1000, p) == 1                         # no unit
+    assert lib.sk_plan_one_draw(100, 20000, 4, 256, 0, 256, 80, 0, 1000, p) == 1 and lib.sk_plan_one_draw(100, 20000, 4, 256, 0, 256, 80, 101, 1000, p) == 1
+    assert lib.sk_plan_one_draw(100, 20000, 4, 256, 0, 256, 80, 50, -1, p) == 1                          # negative stride
 
 
 def test_product_path_fails_loudly_on_cpu_tensors():

@@ -18,12 +18,12 @@ raises poison.UnauditedIntegerSite (AUDITED below is the table's first column).
   _queue: int64[8]                                 word 0, the launch's work counter            sk_wave_fused.hip:906 and sk_wave_prefix.hip:661 (hipMemsetAsync on the
     (one-band forward, prefix, ragged, loss and      (atomicAdd; draws become pair indices)       launch stream) when the plan draws from it; otherwise the launcher drops
     symmetric launches)                                                                           the pointer (sk_wave_fused.hip:908, sk_wave_prefix.hip:660) and nothing reads it
-  solve_fwd_fused_static: ws uint8                 the counter behind the per-wave rows;         sk_wave_fused_mb.hip:865 (counter); split mode: :853 (progress words and
+  solve_fwd_fused_static: ws uint8                 the counter behind the per-wave rows;         sk_wave_fused_mb.hip:864 (counter); split mode: :853 (progress words and
                                                    split mode: progress words [P], counter,       counter in one memset) and :857 (status word); every other byte is a
                                                    status word (last 8 bytes)                     double the wave that reads it has written
-  linear_adjoint_fused_mb / rbf_adjoint_fused_mb:  the counter behind the boundary rows          sk_wave_adj_fused_mb.hip:1230, or the pointer is dropped (:1234)
+  linear_adjoint_fused_mb / rbf_adjoint_fused_mb:  the counter behind the boundary rows          sk_wave_adj_fused_mb.hip:1221, or the pointer is dropped (:1220)
     ws uint8
-  solve_deriv_fused: ws uint8                      the counter behind the per-wave rows          sk_wave_deriv_fused.hip:691, or the pointer is dropped (:695)
+  solve_deriv_fused: ws uint8                      the counter behind the per-wave rows          sk_wave_deriv_fused.hip:683, or the pointer is dropped (:682)
   _fused_rescue_args: rescue ws uint8              none: [P] doubles of screened upstream        sk_adj_fused_rescue.hip:30 (k_screen writes all P entries before the sweep);
                                                    gradients, then stored grids per block         rescue_pair writes inc, G, Kf, Kr of its block before adj_pair reads them
   solve_adj: ws uint8 (fast adjoint)               none: strip edges and a dummy K vector,       launch_fwd_wave writes the edges the adjoint sweep reads (sk_abi.hip:77-78)
