@@ -1775,7 +1775,7 @@ class HipBackend:
         """(k, d/dgamma k, d2/dgamma2 k), (A,B) each, straight from the paths X0 = X, X1 = X + eps*gamma, X2 = X + 2*eps*gamma and Y:
         the three increment arrays are formed inside the solver (sk_solve_deriv_static_f64, csrc/sk_wave_deriv_fused.hip) with the
         arithmetic of static_deriv_increments and never exist in HBM.  None outside its scope (fp64, dim <= 8, dyadic <= 2, second
-        path of 126 points or more)."""
+        path of 113 points or more: df_plan's NUp >= 64)."""
         for t, n in ((X0, "X0"), (X1, "X1"), (X2, "X2"), (Y, "Y")):
             _dev(t, n)
         A, M, D = X0.shape

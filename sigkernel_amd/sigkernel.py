@@ -1121,7 +1121,11 @@ def k_kgrad(X, Y, gamma, dyadic_order, static_kernel, eps=1e-4, workspace_bytes=
     if M < 2 or N < 2:
         out[0] = 1.
         return out[0], out[1], out[2]
-    Xd, Yd, gd = X.detach(), Y.detach(), None if gamma is None else gamma.detach()
+    # (contiguous once, here: X + eps gamma takes the strides of a strided view -- the staging of the HIP routes refuses that --, and a
+    # static kernel evaluated by torch on a view may sum <x, y> in another order than on its contiguous copy)
+    Xd, Yd, gd = X.detach().contiguous(), Y.detach().contiguous(), None if gamma is None else gamma.detach().contiguous()
+    if nodes is not None:
+        nodes = tuple(t.contiguous() for t in nodes)
     fused = _fused_static(static_kernel, True) if hasattr(be, "static_deriv_increments") else None
     # transient bytes per row of X: three increment arrays (+ three static Gram matrices on the generic route)
     per_row = (3 if fused is not None else 6) * B * M * N * X.element_size()
