@@ -69,7 +69,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*, sk_truncated_wide_adjoint*, sk_plan_adjoint_chunks, sk_plan_one_draw) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*, sk_truncated_wide_adjoint*, sk_plan_adjoint_chunks, sk_plan_one_draw, sk_solve_prefix_resume_*, sk_prefix_state_pitch) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -537,6 +537,40 @@ int sk_solve_prefix_nodes_rbf_f64(const double *Xr, const double *Yt, int64_t A,
                                   int dyadic, int scheme, double inv_sigma, int nodes, double *out, int64_t ldo, void *queue, void *stream);
 int sk_solve_prefix_nodes_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                                   int dyadic, int scheme, double inv_sigma, int nodes, float *out, int64_t ldo, void *queue, void *stream);
+/* The LAST ROW over a second path that GROWS: the sweep of sk_solve_prefix_nodes_*(SK_NODES_LAST_ROW) RESUMED from a kept column, so
+ * that a stream y scored against complete paths x costs its new points, not its history.  All that crosses a column of a pair is one
+ * column of the fine grid; a launch over the piece y[s:] that starts from column s (col_in) instead of the ones repeats the cells of
+ * a launch over the whole of y, with the same operands in the same order:
+ *     out[p ldo + n] = k_sig(x, y[:s + n + 1]),   1 <= n <= Nc        (Nc + 1 = the points of the piece; Yt / dYt stage the PIECE)
+ * -- every element bit for bit the node sk_solve_prefix_* stores at global column s + n of the whole stream.  Element 0 of every slice
+ * is NOT written (with col_in it is not 1 but the last row's node at column s, which the caller has from the launch before).
+ *   col_in:  null (a first launch: s = 0, the column of ones) or [pairs][ld_col] doubles, pair p = a B + b (Gram) or a (paired):
+ *            element i of a slot = K at fine row i + 1, fine column s << dyadic, i < Mc << dyadic.  Read, never written.
+ *   col_out: null, or the same layout: the column behind unit state_unit - 1 of the launch, i.e. global coarse column
+ *            s + 2 state_unit, 1 <= state_unit <= Nc / 2 (SK_ERR_BAD_ARG otherwise; state_unit = 0 with col_out null).  The state sits at
+ *            an EVEN coarse column of the piece, so s must stay even from launch to launch: a caller keeps the
+ *            Nc + 1 - 2 state_unit (1 or 2) last points behind the state and passes them again in front of the next piece.
+ *            Elements i < Mc << dyadic of every slot are written, plain stores; nothing else is.
+ *   ld_col:  doubles between the slots, >= sk_prefix_state_pitch(Mc, dyadic, kind) and even; both arrays 16-byte aligned and not
+ *            overlapping (SK_ERR_BAD_ARG).  Elements [Mc << dyadic, ld_col) of a slot are the caller's: the kernel may read them from
+ *            col_in (any bits, uninitialised memory included: no result depends on them) and never writes them in col_out.
+ *   The state is fp64 whatever the output dtype: _f32 streams resume bit for bit too.
+ * Other arguments, scope and errors: as sk_solve_prefix_*. */
+int sk_solve_prefix_resume_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                      int dyadic, int scheme, double *out, int64_t ldo, const double *col_in, double *col_out, int64_t ld_col,
+                                      int state_unit, void *queue, void *stream);
+int sk_solve_prefix_resume_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                      int dyadic, int scheme, float *out, int64_t ldo, const double *col_in, double *col_out, int64_t ld_col,
+                                      int state_unit, void *queue, void *stream);
+int sk_solve_prefix_resume_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                   int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, const double *col_in, double *col_out,
+                                   int64_t ld_col, int state_unit, void *queue, void *stream);
+int sk_solve_prefix_resume_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                   int dyadic, int scheme, double inv_sigma, float *out, int64_t ldo, const double *col_in, double *col_out,
+                                   int64_t ld_col, int state_unit, void *queue, void *stream);
+/* Doubles of one pair's kept column for sk_solve_prefix_resume_*: the Mc << dyadic fine rows rounded up to whole lanes of the kernel
+ * (always even).  Host only.  0: dyadic outside 0 .. 2, kind outside 0 / 1 or Mc < 1. */
+int64_t sk_prefix_state_pitch(int Mc, int dyadic, int kind);
 /* ONE NODE per pair: batches of paths of unequal length, padded at their ends to a common length (any finite values).  The same sweep
  * of the same kernel over the padded pair, storing only
  *     out[p] = k_sig(x_a[:len_x[a]], y_b[:len_y[b]])        (node (len_x[a] - 1, len_y[b] - 1) of pair p's grid, bit for bit)

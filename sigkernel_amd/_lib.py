@@ -98,6 +98,11 @@ SIGNATURES = {
     "sk_solve_prefix_nodes_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_nodes_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _vp, _i64, _vp, _vp]),
     "sk_solve_prefix_nodes_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _int, _vp, _i64, _vp, _vp]),
+    "sk_solve_prefix_resume_linear_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp]),
+    "sk_solve_prefix_resume_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp]),
+    "sk_solve_prefix_resume_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp]),
+    "sk_solve_prefix_resume_rbf_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp]),
+    "sk_prefix_state_pitch": (_i64, [_int, _int, _int]),
     "sk_solve_prefix_at_linear_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sk_solve_prefix_at_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "sk_solve_prefix_at_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
@@ -660,6 +665,82 @@ class HipBackend:
         else:
             out[..., 0] = 1         # k of two one-point prefixes / of one against a whole path: the kernel stores elements >= 1
         return out
+
+    def stage_prefix_bank(self, kind, param, X, dyadic, gram):
+        """The first paths of solve_prefix_resume staged ONCE (sk_prep_paths_*, element for element what sk_prep_pair_* writes for them):
+        a stream that grows stages only its new piece per launch.  None outside the prefix kernel's scope."""
+        _dev(X, "X")
+        A, M, D = X.shape
+        if M < 2 or D > 8 or not 0 <= dyadic <= 2 or (kind == 1 and not float(param) > 0):
+            return None
+        Mrows = _stage_rows(kind, M, gram)
+        with _device(X.device):
+            if kind == 0:
+                kappa = float(load().sk_linear_prescale(int(dyadic)))
+                return _prep_paths(X, True, False, kappa * float(param) ** 2, Mrows)
+            return _prep_paths(X, False, False, 1.0, Mrows)
+
+    def solve_prefix_resume(self, kind, param, X, Y, dyadic, naive, gram, col_in, col_out, bank=None, out=None):
+        """The last row of every pair's prefix grid over a PIECE Y (B, n >= 2, D) of longer second paths, the sweep resumed from the kept
+        column `col_in` (None: Y starts the paths, the sweep starts from the ones) -- sk_solve_prefix_resume_{linear,rbf}_*, the resume
+        mode of k_fwd_prefix (csrc/sk_wave_prefix.hip): out (A, B, n) for gram, (A, n) paired, in the dtype of X, out[..., j] =
+        k_sig(x, y[:s + j + 1]) for j >= 1 with s the (even) coarse column col_in holds -- bit for bit the node a sweep of the whole of y
+        stores there.  Element 0 is NOT written (it is uninitialised memory: the caller has that node from the launch before).
+        col_in / col_out: contiguous fp64 tensors (pairs, pitch), pitch = state_pitch(...), two different tensors.  col_out receives the
+        column behind unit (n - 1) // 2 - 1 of the piece, coarse column s + 2 ((n - 1) // 2), when the piece holds a whole unit
+        ((n - 1) // 2 >= 1); else it is left as it is.  Returns (out, columns the state advanced by), or None outside the kernel's
+        scope (sk_route_query(SK_OP_PREFIX) != FUSED).  bank: stage_prefix_bank(...) of the same X, kind, param, dyadic, gram.  `out`:
+        write into this tensor instead (every pair's n elements dense, the pairs evenly spaced)."""
+        _dev(X, "X")
+        _dev(Y, "Y")
+        A, M, D = X.shape
+        B, N = Y.shape[0], Y.shape[1]
+        Mc, Nc = M - 1, N - 1
+        if Mc < 1 or Nc < 1 or (kind == 1 and not float(param) > 0) or \
+                self.route(OP_PREFIX, kind, D, M, N, dyadic, naive, X.element_size()) != ROUTE_FUSED:
+            return None
+        pairs = A * B if gram else A
+        pitch = self.state_pitch(kind, M, dyadic)
+        for name, t in (("col_in", col_in), ("col_out", col_out)):
+            if t is not None and (t.dtype != torch.float64 or t.device != X.device or tuple(t.shape) != (pairs, pitch) or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float64 tensor of shape (%d, %d) on %s" % (name, pairs, pitch, X.device))
+        if col_in is not None and col_out is not None and col_in.data_ptr() == col_out.data_ptr():
+            raise ValueError("col_in and col_out must be two tensors")
+        shape = ((A, B) if gram else (A,)) + (N,)
+        if out is None:
+            out = torch.empty(shape, dtype=X.dtype, device=X.device)
+        if tuple(out.shape) != shape or out.dtype != X.dtype or out.device != X.device:
+            raise ValueError("out must be a %s tensor of shape %s on %s" % (X.dtype, shape, X.device))
+        ldo = out.stride(1) if gram else out.stride(0)
+        if out.stride(-1) != 1 or ldo < N or (gram and A > 1 and out.stride(0) != B * ldo):
+            raise ValueError("out: every pair's slice must be dense and the pairs evenly spaced")
+        state_unit = Nc // 2 if col_out is not None else 0
+        if A == 0 or (gram and B == 0):
+            return out, 2 * state_unit
+        Mrows = _stage_rows(kind, M, gram)
+        Ncp = ((Nc if kind == 0 else N) + 15) // 16 * 16
+        dev = X.device
+        scheme = SCHEME_NAIVE if naive else SCHEME_DEFAULT
+        lib = load()
+        fn = getattr(lib, "sk_solve_prefix_resume_" + ("linear_" if kind == 0 else "rbf_") + _suffix(X))
+        more = (_ptr(out), ldo, _ptr(col_in), _ptr(col_out) if state_unit else None, pitch, state_unit, _ptr(_queue(dev, pairs)), _stream(X))
+        with _device(dev):
+            if bank is None:
+                bank = self.stage_prefix_bank(kind, param, X, dyadic, gram)
+            if tuple(bank.shape) != (A, Mrows, 8):
+                raise ValueError("bank was staged for another shape")
+            Yt = _prep_paths(Y, kind == 0, True, 1.0, Ncp)
+            sel = () if kind == 0 else (1.0 / float(param),)
+            rc = fn(_ptr(bank), _ptr(Yt), A, B if gram else 0, Mrows, Mc, Nc, Ncp, D, int(dyadic), scheme, *sel, *more)
+        if rc == 2:
+            return None
+        _check(rc, "sk_solve_prefix_resume")
+        return out, 2 * state_unit
+
+    @staticmethod
+    def state_pitch(kind, M, dyadic):
+        """doubles of one pair's kept column (sk_prefix_state_pitch) for first paths of M points"""
+        return int(load().sk_prefix_state_pitch(int(M) - 1, int(dyadic), int(kind)))
 
     def solve_prefix_at(self, kind, param, X, Y, len_x, len_y, dyadic, naive, gram):
         """Batches of paths of unequal length in ONE fused sweep (sk_solve_prefix_at_{linear,rbf}_*, the prefix kernel's store mode

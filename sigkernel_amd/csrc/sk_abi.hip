@@ -183,6 +183,25 @@ int solve_prefix_at(int kind, const double *Xr, const double *Yt, int64_t A, int
     return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, 1, queue, (hipStream_t)stream, SK_NODES_AT, len_x, len_y);
 }
 
+// the last row of every pair's prefix grid over a piece of a growing second path (sk_wave_prefix.hip, RESUME): the sweep starts from the
+// kept column col_in (null: from the ones) and leaves the column behind unit state_unit - 1 in col_out (null: nothing)
+template <typename TO>
+int solve_prefix_resume(int kind, const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D, int dyadic,
+                        int scheme, double inv_sigma, TO *out, int64_t ldo, const double *col_in, double *col_out, int64_t ld_col,
+                        int state_unit, void *queue, void *stream) {
+    if (D < 1 || !Xr || !Yt || !out || A < 0 || B < 0 || Mc < 1 || Nc < 1 || dyadic < 0 || dyadic > 16) return SK_ERR_BAD_ARG;
+    if (scheme != SK_SCHEME_DEFAULT && scheme != SK_SCHEME_NAIVE) return SK_ERR_BAD_ARG;
+    if (kind == 1 && (!(inv_sigma > 0.0) || !(inv_sigma < 1e300))) return SK_ERR_BAD_ARG;
+    if (ldo < (int64_t)Nc + 1) return SK_ERR_BAD_ARG;
+    if (col_out && (state_unit < 1 || 2 * (int64_t)state_unit > Nc)) return SK_ERR_BAD_ARG;
+    if (!col_out && state_unit != 0) return SK_ERR_BAD_ARG;
+    if ((col_in || col_out) && dyadic <= 2 && (ld_col < prefix_state_pitch(kind, Mc, dyadic) || (ld_col & 1))) return SK_ERR_BAD_ARG;
+    if (A == 0) return SK_OK;
+    const Geom g = make_geom(B > 0 ? A * B : A, Mc, Nc, dyadic, scheme);
+    return launch_fwd_prefix<TO>(kind, Xr, Yt, A, B, Mrows, Ncp, D, g, inv_sigma, out, ldo, queue, (hipStream_t)stream, SK_NODES_LAST_ROW, nullptr,
+                                 nullptr, col_in, col_out, ld_col, state_unit);
+}
+
 // the truncated signature kernel (sk_truncated.hip), every mode of its one launch; argument checks before any HIP call.  paired != 0: the
 // A pairs (x_p, y_p), B ignored; levels != 0: the level terms of every pair, sigma not read -- and only then may it be null; kind 1: the
 // RBF lift on POINTS with param = 1 / sigma
@@ -716,6 +735,28 @@ int sk_solve_prefix_nodes_rbf_f32(const double *Xr, const double *Yt, int64_t A,
                                   int dyadic, int scheme, double inv_sigma, int nodes, float *out, int64_t ldo, void *queue, void *stream) {
     return solve_prefix<float>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, queue, stream, nodes);
 }
+
+int sk_solve_prefix_resume_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                      int dyadic, int scheme, double *out, int64_t ldo, const double *col_in, double *col_out, int64_t ld_col,
+                                      int state_unit, void *queue, void *stream) {
+    return solve_prefix_resume<double>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, out, ldo, col_in, col_out, ld_col, state_unit, queue, stream);
+}
+int sk_solve_prefix_resume_linear_f32(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                      int dyadic, int scheme, float *out, int64_t ldo, const double *col_in, double *col_out, int64_t ld_col,
+                                      int state_unit, void *queue, void *stream) {
+    return solve_prefix_resume<float>(0, dXr, dYt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, 0.0, out, ldo, col_in, col_out, ld_col, state_unit, queue, stream);
+}
+int sk_solve_prefix_resume_rbf_f64(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                   int dyadic, int scheme, double inv_sigma, double *out, int64_t ldo, const double *col_in, double *col_out,
+                                   int64_t ld_col, int state_unit, void *queue, void *stream) {
+    return solve_prefix_resume<double>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, col_in, col_out, ld_col, state_unit, queue, stream);
+}
+int sk_solve_prefix_resume_rbf_f32(const double *Xr, const double *Yt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
+                                   int dyadic, int scheme, double inv_sigma, float *out, int64_t ldo, const double *col_in, double *col_out,
+                                   int64_t ld_col, int state_unit, void *queue, void *stream) {
+    return solve_prefix_resume<float>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, col_in, col_out, ld_col, state_unit, queue, stream);
+}
+int64_t sk_prefix_state_pitch(int Mc, int dyadic, int kind) { return prefix_state_pitch(kind, Mc, dyadic); }
 
 int sk_solve_prefix_at_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                                   int dyadic, int scheme, const int *len_x, const int *len_y, double *out, void *queue, void *stream) {

@@ -192,7 +192,8 @@ int launch_fwd_fused_rbf(const double *Xr, const double *Yt, int64_t A, int64_t 
 template <typename TO>
 int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
                       double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s, int nodes = 0, const int *len_x = nullptr,
-                      const int *len_y = nullptr);
+                      const int *len_y = nullptr, const double *col_in = nullptr, double *col_out = nullptr, int64_t ld_col = 0, int state_unit = 0);
+int64_t prefix_state_pitch(int kind, int Mc, int dyadic);   // doubles of one pair's kept column (the resume mode of the last row's store)
 bool prefix_in_scope(int kind, int D, int Mc, int dyadic);   // the kernel's scope = the SK_OP_PREFIX rule of sk_route_query
 
 // ---- sk_truncated.hip: the truncated signature kernel of Kiraly and Oberhauser, all levels in one sweep of the step grid ----

@@ -49,6 +49,27 @@
 //      [1, padded length] stores nothing or another node of the pair, never elsewhere: the only address formed is out + p.  No
 //      per-lane state is added to the step loop.
 //
+// RESUME (prm.col_in / prm.col_out, launch-time wave-uniform values; the last row's store mode only: no instance more).  All that crosses
+// a column of a pair is the lane's left[R] and its corner, so a stream y that GROWS is swept in pieces: a launch over y[s:] that loads
+// the fine column K[.][s << dyadic] where the sweep enters a pair continues the sweep of y[:s + 1] cell for cell -- the same operands in the
+// same order, so every node it stores is bit for bit the node a sweep of the whole of y stores there.
+//   col_in   pair p's column at col_in + p ld_col: element i = K at fine row i + 1 of the pair (row 0 is the ones).  Lane lam loads
+//            elements [lam R, lam R + R) into left[] -- the fine rows >= Mc << dyadic of the pair's last lane are not loaded: they keep
+//            the 1.0 of a first launch -- and its corner from element lam R - 1 (lane 0: the top boundary, 1.0).  In the block that
+//            runs once per pair and lane; nullptr: the ones.
+//   col_out  the same layout: a lane that finishes unit state_unit - 1 of its pair stores left[] there -- the column behind that unit,
+//            fine column 2 state_unit << dyadic of the launch, an even coarse column: a column inside a unit never exists as a whole in
+//            registers, and the padded second column of a half-filled unit must not enter the state (its zero increment still changes
+//            K).  Only the fine rows < Mc << dyadic are stored, two at a time (R is even, ld_col is even, the arrays 16-byte aligned).
+//   ld_col >= ceil(Mc / RC) R (prefix_state_pitch: whole lanes) and even.  Elements [Mc << dyadic, ld_col) of a slot are neither read
+//   nor written; lanes without rows of the pair, stream positions without a pair and the pairs of a padded lane group touch
+//   nothing.  col_in and col_out must not overlap: a lane reads its corner from the slot of the lane above, which may have left the
+//   state unit already.
+// REGISTERS: k_fwd_prefix<1, 2, 0> sits AT 168 VGPRs, the three-wave line.  Deriving the pair again where the state is stored (from the
+// stream cursor, or from o_ptr by a division) costs one register in that instance; so the block that opens a pair -- which has the
+// pair -- forms the lane's store address there and parks it in prev[0], a register the slice modes carry through the loop unused.
+// With that all four instances keep their counts (157 / 157 / 168 / 141, no scratch).
+//
 // Scope: kind 0 / 1, dim <= 8, one band per pair -- rows <= 64 RC with RC = 4 / 2 / 1 at dyadic 0 / 1 / 2, rows = M - 1 linear and
 // M rbf; rbf at dyadic 0 sweeps two rows per lane (rows <= 128: the four-row form with 8 staged dims spills) -- dyadic <= 2, any N.
 // PAIR ORDER, rings, producers: see sk_wave_fused.hip, whose comments are not repeated here.
@@ -57,6 +78,7 @@
 
 namespace sk {
 namespace {
+
 
 constexpr int FD = 8, ND = 8;      // dims carried (inputs are zero-padded to 8)
 constexpr int Y_SLAB_PITCH = y_slab_pitch(ND);   // 8 dimension rows of 8 units; odd slabs swap each pair of rows (sk_wave_fused.hip)
@@ -75,7 +97,14 @@ struct PrefixParams {
     int defer, wide;        // the store scheme (see THE STORE above): stores issued behind the window's DMA wait; shifted two-column pieces
     int slice;              // SK_NODES_*: 0 the full grid; 1 / 2 / 3: only the diagonal / the last row / the last column; 4: one node per
                             // pair, (len_x[a] - 1, len_y[b] - 1) (see SLICES above)
-    const int *len_x, *len_y;   // slice 4: points per path, [A] and [B] (paired launch: [A], indexed by the pair); nullptr otherwise
+    // slice 4: points per path, [A] and [B] (paired launch: [A], indexed by the pair), nullptr otherwise.  Slice 2 reads the same two
+    // kernel arguments as the RESUME mode's arrays (see RESUME above; kernel arguments live in scalar registers the loop has none to
+    // spare of): the kept column the sweep of a pair starts from / the column it leaves behind, pair p's fine rows at col + p ld_col;
+    // nullptr: start from the ones / keep nothing.  state_unit: col_out is the column behind unit state_unit - 1
+    union { const int *len_x; const double *col_in; };
+    union { const int *len_y; double *col_out; };
+    int ld_col;
+    int resume;          // RESUME: state_unit << 2 | (col_out != nullptr) << 1 | (col_in != nullptr); 0 in every other launch
     int u_f, lam_f;      // unit / lane of the last node (they end the wave's last pair)
     double inv_sigma;    // RBF: G = exp(-|x - y|^2 * inv_sigma)
     WaveGroup wg;
@@ -119,6 +148,13 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
     // inside the step loop's rare blocks the mode is re-derived from the ONE kernel argument behind an opaque move (sk_wave_fused.hip)
     auto shy_a = [&]() __attribute__((always_inline)) -> int {
         int v = prm.shy_A;
+        asm volatile("" : "+s"(v));
+        return v;
+    };
+    // RESUME: the mode's one word behind an opaque move, so that nothing derived from it is held in a scalar register of its own across the
+    // loop (the two arrays share the kernel arguments of slice 4's lengths)
+    auto resume_word = [&]() __attribute__((always_inline)) -> int {
+        int v = prm.resume;
         asm volatile("" : "+s"(v));
         return v;
     };
@@ -428,6 +464,18 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
         }
     };
 
+    // RESUME: left[] -- the fine column behind the unit this lane has just finished -- to the lane's part of the pair's slot of col_out,
+    // whose address the block that opened the pair left in prev[0].  Called by a lane with rows of a pair (o_ptr)
+    auto store_state = [&]() __attribute__((always_inline)) {
+        double *const co = reinterpret_cast<double *>(static_cast<uintptr_t>(__double_as_longlong(prev[0])));
+        const int n_fine = o_rows << DY;
+#pragma unroll
+        for (int i = 0; i < R; i += 2) {
+            if (i + 1 < n_fine) *reinterpret_cast<d2_t *>(co + i) = d2_t{left[i], left[i + 1]};
+            else if (i < n_fine) co[i] = left[i];
+        }
+    };
+
     d2_t dyn[ND];
     auto read_y = [&]() { lds_read_dims_issue(dyn, a_e, a_e ^ 128u); };
     unsigned x_rd_off = 0;   // ring slot the x rows of this XW-step window are read from: ((t / XW) % X_SLOTS) * JMAX * XSLAB
@@ -492,6 +540,35 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
                 const int at_k = (lx - 2) - (ln & ((1 << prm.logL) - 1)) * RC;
                 n_cols = ly - 1;
                 o_ptr = (pair_u != NOPAIR && at_k >= 0 && at_k < RC) ? static_cast<char *>(prm.out) + ((int64_t)pair_u * esz + at_k) : nullptr;
+            }
+            if (resume_word() != 0) {
+                // RESUME: the pair's kept column in place of the ones, and where this lane's part of the next one goes (o_ptr: the
+                // pair exists and this lane holds rows of it).  The lane number behind an opaque zero, as above; the rows are loaded
+                // under their own masks, straight into left[]
+                asm volatile("");
+                if (o_ptr != nullptr) {
+                    int z = 0;
+                    asm volatile("" : "+s"(z));
+                    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z)) & ((1 << prm.logL) - 1);
+                    const int64_t slot = (int64_t)pair_u * prm.ld_col + (int64_t)(ln * R);
+                    const int rw = resume_word();
+                    if (rw & 1) {
+                        const double *const ci = prm.col_in + slot;
+                        const int n_fine = o_rows << DY;
+#pragma unroll
+                        for (int i = 0; i < R; ++i)
+                            if (i < n_fine) left[i] = ci[i];
+                        if (ln != 0) corner = ci[-1];
+                        // the loads are waited for HERE: left open, the compiler's wait for them lands in front of the block sweep
+                        // of every macro-step, where it also drains the DMA and the deferred stores of the step before
+#pragma unroll
+                        for (int i = 0; i < R; ++i) asm volatile("" : "+v"(left[i]));
+                        asm volatile("" : "+v"(corner));
+                    }
+                    // the slice modes never read prev[] (the full grid's two-column pieces): its first register carries the address
+                    // through the pair's sweep, so that the store needs no pair and nothing new is held across the loop
+                    if (rw & 2) prev[0] = __longlong_as_double((long long)reinterpret_cast<uintptr_t>(prm.col_out + slot));
+                }
             }
         }
 
@@ -598,6 +675,10 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_prefix(const PrefixParams prm)
         if (prm.slice != 0) {      // (the launcher clears defer and wide then: nothing of the full grid's block runs)
             asm volatile("");   // a real branch around the full grid's stores
             store_slice(cand, uk_now);
+            if (resume_word() & 2) {
+                asm volatile("");
+                if (uk_now + 1 == (resume_word() >> 2) && o_ptr != nullptr) store_state();
+            }
         } else if (!defer) {
             store_nodes(cand, uk_now);
         }
@@ -676,16 +757,34 @@ bool prefix_in_scope(int kind, int D, int Mc, int dyadic) {
     return rows <= 64 * prefix_rc(kind, dyadic);
 }
 
+// doubles of one pair's kept column (RESUME): the fine rows of the lanes that hold rows of the pair, whole lanes -- ceil(Mc / RC) R
+int64_t prefix_state_pitch(int kind, int Mc, int dyadic) {
+    if ((kind != 0 && kind != 1) || dyadic < 0 || dyadic > 2 || Mc < 1) return 0;
+    const int RC = prefix_rc(kind, dyadic);
+    return ((int64_t)Mc + RC - 1) / RC * ((int64_t)RC << dyadic);
+}
+
 // KIND 0: dXr [A][Mrows][8] / dYt [Bn][8][Ncp] are path differences; KIND 1: the same layouts hold the path points.
 // nodes: 0 the full grid (ldo >= (Mc + 1) (Nc + 1)); 1 / 2 / 3 the diagonal / last row / last column alone (ldo >= its length);
 // 4 (SK_NODES_AT): node (len_x[a] - 1, len_y[b] - 1) of every pair alone, out + p (ldo is not used), len_x [A] / len_y [B] (paired: [A])
 // device int32.  The wave sweeps the padded pair whatever the lengths: the plan is the padded shape's.
+// col_in / col_out (nodes 2 only; either may be null): RESUME, see the head of this file -- [P][ld_col] doubles each, ld_col >=
+// prefix_state_pitch and even, 16-byte aligned, not overlapping; col_out is the column behind unit state_unit - 1, 2 state_unit <= Nc.
 // SK_ERR_UNSUPPORTED outside the kernel's scope.
 template <typename TO>
 int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Ncp, int D, const Geom &g,
-                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s, int nodes, const int *len_x, const int *len_y) {
+                      double inv_sigma, TO *out, int64_t ldo, void *queue, hipStream_t s, int nodes, const int *len_x, const int *len_y,
+                      const double *col_in, double *col_out, int64_t ld_col, int state_unit) {
     const int DY = g.dyadic;
     if (nodes < 0 || nodes > 4) return SK_ERR_BAD_ARG;
+    if (col_in || col_out) {
+        // RESUME: the last row's store mode; whole lanes per slot, 16-byte aligned slots, a state column inside the launch, two arrays
+        if (nodes != 2 || DY < 0 || DY > 2 || g.Mc < 1) return nodes != 2 ? SK_ERR_BAD_ARG : SK_ERR_UNSUPPORTED;
+        if (ld_col < prefix_state_pitch(kind, g.Mc, DY) || ld_col > 0x7fffffff || (ld_col & 1) || ((uintptr_t)col_in | (uintptr_t)col_out) % 16) return SK_ERR_BAD_ARG;
+        if (col_out && (state_unit < 1 || 2 * (int64_t)state_unit > g.Nc)) return SK_ERR_BAD_ARG;
+        const int64_t span = g.P * ld_col;
+        if (col_in && col_out && col_in < col_out + span && col_out < col_in + span) return SK_ERR_BAD_ARG;
+    }
     if (nodes == 4 && (!len_x || !len_y)) return SK_ERR_BAD_ARG;
     if (nodes == 4) ldo = 1;
     if (!prefix_in_scope(kind, D, g.Mc, DY)) return SK_ERR_UNSUPPORTED;
@@ -716,6 +815,9 @@ int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A,
     prm.slice = nodes;
     prm.len_x = nodes == 4 ? len_x : nullptr;
     prm.len_y = nodes == 4 ? len_y : nullptr;
+    if (nodes == 2) { prm.col_in = col_in; prm.col_out = col_out; }      // (they share the lengths' kernel arguments)
+    prm.ld_col = (int)ld_col;
+    prm.resume = nodes == 2 ? ((col_out ? state_unit : 0) << 2 | (col_out ? 2 : 0) | (col_in ? 1 : 0)) : 0;
     // (a slice is stored direct, one element at a time: the deferred scheme and the two-column pieces belong to the full grid)
     prm.defer = nodes == 0 && mode >= 2;
     prm.wide = nodes == 0 && mode >= 3 && can_wide;
@@ -734,8 +836,8 @@ int launch_fwd_prefix(int kind, const double *dXr, const double *dYt, int64_t A,
 }
 
 template int launch_fwd_prefix<double>(int, const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double, double *,
-                                       int64_t, void *, hipStream_t, int, const int *, const int *);
+                                       int64_t, void *, hipStream_t, int, const int *, const int *, const double *, double *, int64_t, int);
 template int launch_fwd_prefix<float>(int, const double *, const double *, int64_t, int64_t, int, int, int, const Geom &, double, float *,
-                                      int64_t, void *, hipStream_t, int, const int *, const int *);
+                                      int64_t, void *, hipStream_t, int, const int *, const int *, const double *, double *, int64_t, int);
 
 }  // namespace sk

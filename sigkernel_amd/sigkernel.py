@@ -20,7 +20,7 @@ from . import _lib
 from ._routes import routes
 from .static_kernels import LinearKernel, RBFKernel
 
-__all__ = ["SigKernel", "_SigKernel", "_SigKernelGram", "k_kgrad", "pad_paths"]
+__all__ = ["SigKernel", "SigKernelStream", "_SigKernel", "_SigKernelGram", "k_kgrad", "pad_paths"]
 
 _DEFAULT_WORKSPACE = 48 << 30  # bytes of transient HBM one call may use (288 GB part)
 
@@ -1475,6 +1475,136 @@ def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
 
 
+class SigKernelStream:
+    """Complete paths X scored against streams that GROW: ``SigKernel.open_stream(X, Y0)`` -> this, ``append(Ynew)`` -> the kernels
+    of X against every new prefix, in time linear in the stream.
+
+    X (A, M, D): the bank of complete paths.  Y0 (B, n0 >= 1, D): what the B streams hold so far.  ``paired=True``: stream a runs
+    against bank path a (B == A) and the pair axis below is one axis (A,) instead of (A, B).
+
+      ``append(Ynew)``   Ynew (B, c, D), the next c points of every stream -> (A, B, c): k(x_a, y_b[:n + 1]) for each NEW point n, in
+                         order -- bit for bit ``compute_Gram_prefixes(X, all of y, nodes="last_row")[..., -c:]``.  c == 0: an empty
+                         (A, B, 0) tensor.  Values in the dtype of the paths, no ``grad_fn``.
+      ``kernel``         (A, B): k(x_a, y_b) as the streams stand, ``compute_Gram(X, all of y)`` bit for bit
+      ``length``         points seen per stream
+      ``resumes``        True: every append sweeps only its new points (below); False: every append sweeps the whole history
+      ``state_bytes``    bytes the stream holds between appends (below)
+
+    ``resumes``: inside the fused prefix kernel's scope (exactly LinearKernel / RBFKernel, dim <= 8, dyadic_order <= 2, bank paths of one
+    band, the library back-end) all that crosses a column of a pair's PDE grid is that column, so the stream keeps one fine column per
+    pair -- fp64 whatever the paths' dtype -- and an append launches ONE sweep of the prefix kernel over the new points that starts
+    from it (csrc/sk_wave_prefix.hip, RESUME).  The kept column sits at an even point of the stream; the one or two points behind it
+    are kept too and swept again with the next chunk (at most one column more per append).  The bank is staged once, when the
+    stream is opened.  ``state_bytes`` = the two column arrays the sweeps alternate between (2 x pairs x pitch x 8 bytes, pitch = the bank
+    paths' fine rows rounded up to whole lanes) + the staged bank + the kept points: constant in the stream's length.  A launch has
+    a fixed cost of about as many macro-steps as a bank path has lanes, so appending point by point is far from free: see README.md
+    for the chunk size from which an append beats sweeping the history again.
+
+    Outside that scope (dim > 8, bank paths of more than one band, dyadic_order > 2, duck-typed or function-valued static kernels,
+    ``routes.no_fused_prefix``, a back-end without ``solve_prefix_resume``) the stream keeps its HISTORY and every append is
+    ``compute_Gram_prefixes(X, history, nodes="last_row")`` over all of it: the same values, time quadratic in the stream;
+    ``state_bytes`` = the history's bytes and grows with it.
+
+    Forward only: an input that requires grad raises ``NotImplementedError`` (outside ``torch.no_grad()``), on ``exact_gradient=True``
+    objects too, whose forward values are the same.  Not sharded (``process_group`` raises).  Only the streams grow: a bank whose
+    paths grow as well would need the kept last ROW too."""
+
+    def __init__(self, sk, X, Y0, paired=False):
+        if sk.process_group is not None:
+            raise NotImplementedError("streams are not sharded over a process group; open the stream on a SigKernel without process_group")
+        self._sk, self._gram = sk, not paired
+        raw = _functional(sk.static_kernel)      # (function-valued paths: (batch, length, Lx, d); the feature map checks them)
+        if not raw:
+            _check_inputs(X, Y0, paired=paired)
+        if Y0.shape[1] < 1:
+            raise ValueError("Y0 must hold at least one point per stream")
+        if _wants_grad(X, Y0, *_static_params(sk.static_kernel)):
+            raise NotImplementedError("streams are forward only: open them under torch.no_grad() or on detached paths")
+        self._X = X.detach()
+        self._tail_shape = tuple(Y0.shape[2:])
+        self._B, self.length = Y0.shape[0], 0
+        self._pairs_shape = (X.shape[0], Y0.shape[0]) if self._gram else (X.shape[0],)
+        self._col, self._cur, self._bank, self._tail, self._hist, self._kernel = None, None, None, None, None, None
+        be = _lib.get_backend()
+        fused = None if raw else _fused_static(sk.static_kernel, self._gram)
+        self.resumes = bool(
+            fused is not None and hasattr(be, "solve_prefix_resume") and hasattr(be, "route") and not routes.no_fused_prefix
+            and not (fused[0] == 1 and routes.no_fused_rbf) and X.shape[0] > 0 and Y0.shape[0] > 0 and X.shape[1] >= 2
+            and _route_query(be.route, _lib.OP_PREFIX, fused[0], X.shape[2], X.shape[1], 2, sk.dyadic_order, bool(sk._naive_solver),
+                             X.element_size()) == FUSED)
+        if self.resumes:
+            self._fused = fused
+            self._X = self._X.contiguous()
+            self._bank = be.stage_prefix_bank(fused[0], fused[1], self._X, sk.dyadic_order, self._gram)
+            pairs = X.shape[0] * (Y0.shape[0] if self._gram else 1)
+            pitch = be.state_pitch(fused[0], X.shape[1], sk.dyadic_order)
+            self._col = [torch.empty((pairs, pitch), dtype=torch.float64, device=X.device) for _ in range(2)]
+            self._kernel = torch.ones(self._pairs_shape, dtype=X.dtype, device=X.device)
+        self._push(Y0.detach(), first=True)
+
+    def _check(self, Ynew):
+        X = self._X
+        if not torch.is_tensor(Ynew) or Ynew.dim() != X.dim() or tuple(Ynew.shape[2:]) != self._tail_shape:
+            raise ValueError("Ynew must have shape (%d, c, %s): the streams' next c points" % (self._B, ", ".join(str(d) for d in self._tail_shape)))
+        if Ynew.shape[0] != self._B:
+            raise ValueError("Ynew must hold the next points of all %d streams, got a batch of %d" % (self._B, Ynew.shape[0]))
+        if Ynew.dtype != X.dtype or Ynew.device != X.device:
+            raise ValueError("Ynew must share dtype and device with the paths the stream was opened on (%s on %s)" % (X.dtype, X.device))
+        if _wants_grad(Ynew):
+            raise NotImplementedError("streams are forward only: append under torch.no_grad() or detached points")
+
+    def _push(self, Ynew, first=False):
+        """the kernels of the c new points, (pairs..., c); first: Ynew opens the streams (its first point has the kernel 1)"""
+        c = Ynew.shape[1]
+        self.length += c
+        if not self.resumes:
+            self._hist = Ynew.contiguous() if first else torch.cat((self._hist, Ynew), dim=1)
+            call = self._sk.compute_Gram_prefixes if self._gram else self._sk.compute_kernel_prefixes
+            with torch.no_grad():
+                row = call(self._X, self._hist, nodes="last_row")
+            self._kernel = row[..., -1]
+            return row[..., row.shape[-1] - c:]
+        # the one or two points behind the kept column, then the new ones: the piece the sweep resumes over
+        piece = Ynew.contiguous() if first else torch.cat((self._tail, Ynew), dim=1)
+        kept = 0 if first else self._tail.shape[1]
+        if piece.shape[1] < 2:      # one point in all: nothing to sweep yet
+            self._tail = piece
+            return self._kernel[..., None].clone()
+        be, sk = _lib.get_backend(), self._sk
+        col_in = None if self._cur is None else self._col[self._cur]
+        nxt = 0 if self._cur is None else 1 - self._cur
+        res = be.solve_prefix_resume(self._fused[0], self._fused[1], self._X, piece, sk.dyadic_order, sk._naive_solver, self._gram,
+                                     col_in, self._col[nxt], bank=self._bank)
+        if res is None:
+            raise RuntimeError("the prefix kernel refused a resumed launch inside its own scope (sk_solve_prefix_resume_*)")
+        row, advanced = res
+        if advanced:
+            self._cur = nxt
+        self._tail = piece[:, advanced:].contiguous()
+        self._kernel = row[..., -1].clone()
+        if first:
+            row[..., 0] = 1       # k against a one-point prefix
+            return row
+        return row[..., kept:]
+
+    def append(self, Ynew):
+        """Ynew (B, c, D): the streams' next c points -> (A, B, c) ((A, c) paired): k(x_a, y_b[:n + 1]) for every new point, in order."""
+        self._check(Ynew)
+        if Ynew.shape[1] == 0:
+            return torch.empty(self._pairs_shape + (0,), dtype=self._X.dtype, device=self._X.device)
+        return self._push(Ynew.detach())
+
+    @property
+    def kernel(self):
+        """(A, B) ((A,) paired): k(x_a, y_b) as the streams stand -- ``compute_Gram(X, all of y)`` bit for bit"""
+        return self._kernel
+
+    @property
+    def state_bytes(self):
+        held = [self._hist] if not self.resumes else list(self._col) + [self._bank, self._tail]
+        return sum(t.numel() * t.element_size() for t in held if t is not None)
+
+
 class SigKernel:
     """Signature kernel k_sig(x, y) = <S(f(x)), S(f(y))> for a static kernel k(x, y) = <f(x), f(y)>.
 
@@ -1528,6 +1658,12 @@ class SigKernel:
         inner = SigKernel(self.static_kernel.base_kernel, self.dyadic_order, self._naive_solver, self.workspace_bytes, self.process_group,
                           self.exact_gradient)
         return inner, _FeatureMap(self.static_kernel)
+
+    def open_stream(self, X, Y0, paired=False):
+        """X (A, M, D) complete paths, Y0 (B, n0 >= 1, D) what B streams hold so far -> a :class:`SigKernelStream`: ``append(Ynew)``
+        returns k(x_a, y_b[:n + 1]) for every new point of the streams -- ``compute_Gram_prefixes(X, y, nodes="last_row")`` as y
+        arrives, bit for bit, without sweeping the history again.  ``paired=True``: stream a against bank path a."""
+        return SigKernelStream(self, X, Y0, paired)
 
     def compute_kernel(self, X, Y, max_batch=100):
         """X (batch, len_x, dim), Y (batch, len_y, dim) -> (batch,) vector k(X^i_T, Y^i_T).
