@@ -431,6 +431,25 @@ int sk_solve_fwd_f64(const double *inc_c, int64_t ld, int64_t P, int Mc, int Nc,
 int sk_solve_fwd_f32(const float *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags,
                      float *out_final, float *out_grid, double *out_edges, void *stream);
 
+/* Forward solve of pairs of UNEQUAL length in one padded batch: ONE node per pair, no grid.  out[p] = K_p at node (mc << dyadic,
+ * nc << dyadic) of the padded pair's fine grid, i.e. the solution of pair p's own (mc, nc) coarse cells -- what sk_solve_fwd_* with
+ * out_grid stores at that node, without the (MM+1)(NN+1) elements per pair around it.
+ *   inc_c [P,Mc,ld]  as sk_solve_fwd_*: whatever cells a >= mc or b >= nc hold (NaN, inf) reaches no result
+ *   cells [P][2]     device int32 {mc, nc}: the coarse cells of pair p's own sub-grid, len - 1 on either side (the layout of
+ *                    SK_FLAG_RAGGED's table); values are clamped to [0, Mc] and [0, Nc]; the only address formed from an entry is out + p
+ *   out   [P]        a pair with mc == 0 or nc == 0 is left alone or stored as exactly 1: the CALLER fills out with ones first (the
+ *                    contract of sk_solve_prefix_at_*)
+ *   flags 0: the streaming kernel (csrc/sk_wave.hip) where it serves the shape and layout (dyadic <= 3, 16-byte aligned rows, cells
+ *            8-byte aligned) -- the PADDED sweep with the pair's own lane, unit and cell storing -- else the anti-diagonal kernel;
+ *         SK_FLAG_SIMPLE / SK_FLAG_EXACT: the anti-diagonal kernel (csrc/sk_simple.hip) over each pair's own sub-grid: the cost of the
+ *            pair's true lengths, and bit for bit the node of its stored grid;
+ *         SK_FLAG_FAST_ONLY: SK_ERR_UNSUPPORTED where the streaming kernel declines.
+ * No kernel instance of its own: a launch-time mode of k_fwd_wave's non-edge instances and of k_fwd_simple. */
+int sk_solve_fwd_at_f64(const double *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, const int *cells,
+                        double *out, void *stream);
+int sk_solve_fwd_at_f32(const float *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, const int *cells,
+                        float *out, void *stream);
+
 /* Forward solve with the LINEAR static kernel fused in (csrc/sk_wave_fused.hip): the increments
  * s^2 <x[p+1]-x[p], y[q+1]-y[q]> are formed inside the sweep, nothing of size P*M*N ever exists in HBM.
  * Replaces, for LinearKernel, the whole of sigkernel.py:362-382 (Gram) / :216-234 (paired).

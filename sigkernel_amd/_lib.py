@@ -81,6 +81,8 @@ SIGNATURES = {
     "sk_increments_adjoint_f32": (_int, [_vp, _i64, _vp, _i64, _int, _int, _vp, _vp]),
     "sk_solve_fwd_f64": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     "sk_solve_fwd_f32": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "sk_solve_fwd_at_f64": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "sk_solve_fwd_at_f32": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_solve_fwd_linear_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_solve_fwd_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_solve_fwd_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _vp]),
@@ -1629,6 +1631,29 @@ class HipBackend:
                       _ptr(out), _ptr(grid), _ptr(edges), _stream(inc_c)), "sk_solve_fwd")
         if want_grid or want_edges:
             return out, grid, edges
+        return out
+
+    def solve_fwd_at(self, inc_c, cells, dyadic, naive=False, flags=0):
+        """Pairs of unequal length in one padded batch, ONE node per pair and no grid (sk_solve_fwd_at_*): inc_c [..., Mc, Nc], cells
+        int32 [..., 2] on the same device, one row (mc, nc) per pair -- the coarse cells of the pair's own paths, length - 1 on either
+        side -> out [...], K at node (mc << dyadic, nc << dyadic) of the padded pair; exactly 1 where mc or nc is 0.  Whatever the
+        increments hold at cells a >= mc or b >= nc reaches no result.  flags = FLAG_SIMPLE: every pair's own sub-grid on the
+        anti-diagonal kernel -- bit for bit the node of solve_fwd(want_grid=True)'s grid, any dyadic order; flags = 0: the streaming
+        kernel's padded sweep with a per-pair end node where it serves the shape (dyadic <= 3; within the streamed route's tolerance of
+        the former, not its bits), else the anti-diagonal kernel -- dyadic orders above 3 are NOT refined to reach the streaming kernel
+        (solve_fwd's _refined), they take the anti-diagonal kernel; FLAG_FAST_ONLY: an error where the streaming kernel declines."""
+        inc_c, ld = _row_stride(inc_c, "inc_c")
+        Mc, Nc = inc_c.shape[-2:]
+        batch = inc_c.shape[:-2]
+        P = inc_c.numel() // (Mc * Nc)
+        if cells.dtype != torch.int32 or cells.device != inc_c.device or tuple(cells.shape) != tuple(batch) + (2,):
+            raise ValueError("cells must be an int32 tensor of shape %s on %s" % (tuple(batch) + (2,), inc_c.device))
+        cells = cells.contiguous()
+        out = torch.ones(batch, dtype=inc_c.dtype, device=inc_c.device)      # the kernels may leave a pair with an empty sub-grid alone
+        with _device(inc_c.device):
+            fn = getattr(load(), "sk_solve_fwd_at_" + _suffix(inc_c))
+            _check(fn(_ptr(inc_c), ld, P, Mc, Nc, int(dyadic), SCHEME_NAIVE if naive else SCHEME_DEFAULT, int(flags), _ptr(cells),
+                      _ptr(out), _stream(inc_c)), "sk_solve_fwd_at")
         return out
 
     def solve_fwd_keep_edges(self, inc_c, dyadic, naive=False):

@@ -27,6 +27,13 @@ the same with its SK_* knobs, sk_abi.hip):
                          SK_OP_TRUNCATED_LONG: order 1, any number of steps) where the plain launch declined both orientations and no
                          gradient is pending -- paths beyond 128 steps, which otherwise take the torch restatement.  Off by default:
                          every call then does what it did before the mode existed
+    SK_NO_RAGGED_NODES   compute_Gram_ragged / compute_kernel_ragged / compute_mmd_ragged outside the fused prefix kernel's scope through
+                         the solver's full fine grid of every padded pair and a gather of one node of it (default: one node per pair
+                         from sk_solve_fwd_at_*, no grid -- the same bits); the A/B base of that route
+    SK_RAGGED_STREAM     opt-in (adds a route, like SK_TRUNCATED_LONG): those calls hand their increments to the STREAMING solver with a
+                         per-pair end node where it serves the shape (dyadic <= 3), instead of the anti-diagonal kernel over every
+                         pair's own sub-grid -- values within the streamed route's tolerance (1e-11 relative in fp64) of the default's,
+                         not its bits.  Off by default; without effect under SK_NO_RAGGED_NODES
 
 A running process flips them through the attributes of `sigkernel_amd.routes` (tests: monkeypatch.setattr), or calls
 `routes.reload()` after changing the environment."""
@@ -35,7 +42,8 @@ import os
 _ENV = {"no_fused_rbf": "SK_NO_FUSED_RBF", "no_fused_mb": "SK_NO_FUSED_MB", "no_fused_adjoint": "SK_NO_FUSED_ADJOINT",
         "no_fused_deriv": "SK_NO_FUSED_DERIV", "no_stream": "SK_NO_STREAM", "no_mmd_streams": "SK_NO_MMD_STREAMS",
         "no_merged_loss": "SK_NO_MERGED_LOSS", "no_loss_launch": "SK_NO_LOSS_LAUNCH", "no_adjoint_swap": "SK_NO_ADJOINT_SWAP",
-        "no_fused_prefix": "SK_NO_FUSED_PREFIX", "truncated_long": "SK_TRUNCATED_LONG"}
+        "no_fused_prefix": "SK_NO_FUSED_PREFIX", "truncated_long": "SK_TRUNCATED_LONG",
+        "no_ragged_nodes": "SK_NO_RAGGED_NODES", "ragged_stream": "SK_RAGGED_STREAM"}
 
 
 class Routes:

@@ -45,6 +45,22 @@ int solve_fwd(const T *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic,
     return launch_fwd_simple<T>(inc_c, g, out_final, out_grid, out_edges, (hipStream_t)stream);
 }
 
+// One node per pair, (cells[p][0] << dyadic, cells[p][1] << dyadic), and no grid: the streaming kernel's per-pair end node or the simple
+// kernel's sweep of the pair's own sub-grid (launch-time modes of the instances solve_fwd launches).
+template <typename T>
+int solve_fwd_at(const T *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, const int *cells, T *out,
+                 void *stream) {
+    if (bad_common(inc_c, P, Mc, Nc, dyadic, scheme, flags) || (flags & SK_FLAG_EDGES_GIVEN) || (ld != 0 && ld < Nc)) return SK_ERR_BAD_ARG;
+    if (!cells || !out) return SK_ERR_BAD_ARG;
+    if (P == 0) return SK_OK;
+    const Geom g = make_geom(P, Mc, Nc, dyadic, scheme, ld);
+    if (!(flags & (SK_FLAG_EXACT | SK_FLAG_SIMPLE))) {
+        const int rc = launch_fwd_wave<T>(inc_c, g.ld, g, out, nullptr, (hipStream_t)stream, cells);
+        if (rc != SK_ERR_UNSUPPORTED || (flags & SK_FLAG_FAST_ONLY)) return rc;
+    }
+    return launch_fwd_simple<T>(inc_c, g, out, nullptr, nullptr, (hipStream_t)stream, cells);
+}
+
 // workspace of the fast adjoint: terminal edges in the strip layout [P, NNp + MMp] doubles + a dummy K[MM][NN] vector
 // [P] doubles; 0 when the strip kernels do not cover the shape
 size_t adj_fast_workspace_bytes(const Geom &g, int elem_size) {
@@ -325,8 +341,8 @@ extern "C" {
 
 // (340 still: sk_truncated_levels_{,paired_}{f64,f32}, sk_truncated_adjoint and its plan, sk_truncated_points_{f64,f32} and SK_OP_TRUNCATED_RBF,
 // sk_truncated_long_{f64,f32}, its plan and SK_OP_TRUNCATED_LONG, sk_truncated_long_adjoint, its plan and SK_OP_TRUNCATED_LONG_ADJOINT,
-// sk_truncated_wide_adjoint, its plan and SK_OP_TRUNCATED_WIDE_ADJOINT, sk_plan_adjoint_chunks and sk_plan_one_draw are additions, no exported
-// signature changed)
+// sk_truncated_wide_adjoint, its plan and SK_OP_TRUNCATED_WIDE_ADJOINT, sk_plan_adjoint_chunks, sk_plan_one_draw and sk_solve_fwd_at_{f64,f32}
+// are additions, no exported signature changed)
 // 340: sk_static_increments_* serve any path dim (D > 32: k_static_wide_mfma); sk_static_adjoint_* kind 1 with D > 32 writes the first
 // pass H [P][M][ldh] of the rbf chain rule instead of dL/dX
 // 330 (round 6): sk_linear_adjoint_fused_f64 takes ypart / ypart_doubles / ycols_out (the second-argument sums, route FUSED_SWAP)
@@ -543,6 +559,14 @@ int sk_solve_fwd_f64(const double *inc_c, int64_t ld, int64_t P, int Mc, int Nc,
 int sk_solve_fwd_f32(const float *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, float *out_final,
                      float *out_grid, double *out_edges, void *stream) {
     return solve_fwd<float>(inc_c, ld, P, Mc, Nc, dyadic, scheme, flags, out_final, out_grid, out_edges, stream);
+}
+int sk_solve_fwd_at_f64(const double *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, const int *cells,
+                        double *out, void *stream) {
+    return solve_fwd_at<double>(inc_c, ld, P, Mc, Nc, dyadic, scheme, flags, cells, out, stream);
+}
+int sk_solve_fwd_at_f32(const float *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, const int *cells,
+                        float *out, void *stream) {
+    return solve_fwd_at<float>(inc_c, ld, P, Mc, Nc, dyadic, scheme, flags, cells, out, stream);
 }
 
 // The fused forward without edges.  *_rows_*: `queue` holds queue_words 64-bit counters (the others: one) -- a plain Gram launch in the

@@ -88,7 +88,9 @@ inline Geom make_geom(int64_t P, int Mc, int Nc, int dyadic, int scheme, int64_t
 
 // ---- sk_simple.hip: one wavefront per pair, anti-diagonal sweep, FMA-free arithmetic -------
 template <typename T>
-int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, double *out_edges, hipStream_t s);
+int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, double *out_edges, hipStream_t s,
+                      const int *cells = nullptr);   // cells [P][2] {mc, nc}: out_final[p] = K at node (mc << d, nc << d), each pair swept
+// over its own sub-grid alone (no grid, no edges); values clamped to the pair's block
 template <typename T>
 int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes, hipStream_t s,
                       bool discrete = false, bool ragged = false, bool sources = false);   // discrete: the exact adjoint of the discrete
@@ -112,7 +114,9 @@ size_t simple_lds_bytes(const Geom &g);
 // [P][NNp + MMp] = K[MM][1..NNp], K[1..MMp][NN] that launch_adj_wave reads; strip_edge_doubles() gives NNp + MMp
 // (0 when the strip kernels do not cover the shape).
 template <typename T>
-int launch_fwd_wave(const T *inc_c, int64_t ld, const Geom &g, T *out_final, double *strip_edges, hipStream_t s);
+int launch_fwd_wave(const T *inc_c, int64_t ld, const Geom &g, T *out_final, double *strip_edges, hipStream_t s,
+                    const int *cells = nullptr);   // cells [P][2] {mc, nc} (8-byte aligned, never with strip_edges): the padded sweep
+// stores node (mc << d, nc << d) of pair p instead of its last one, nothing where mc == 0 or nc == 0; values clamped to the pair's block
 
 // Strip decomposition shared by the forward and adjoint wave kernels for dyadic 1..2 (where both use the same rows per
 // lane): NUp 16-byte units per padded row, L = 1 << logL lanes per pair, nb bands, RC coarse rows per lane.

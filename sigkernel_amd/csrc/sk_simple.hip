@@ -19,6 +19,14 @@ namespace sk {
 
 namespace {
 
+// `naive`: bit 0 the naive stencil.  Bit 1 (FWD_RAGGED, wave-uniform): `out_edges` is not an output but a table of P entries {int32 mc,
+// int32 nc}, the coarse cells of each pair's own sub-grid (len - 1 on either side; the layout of ADJ_RAGGED's table below).  Pair p is
+// swept over its (mc, nc) corner of the padded (Mc, Nc) block alone, with no grid and no edges -- out_final[p] = K at node (mc << d,
+// nc << d) of the padded pair, every cell from the same operands in the same order as in the padded sweep, so bit for bit the node a
+// stored grid holds there; an empty sub-grid (mc == 0 or nc == 0) gives 1.  A launch-time mode of the same two instances, in the
+// arguments they already have.
+constexpr int FWD_RAGGED = 2;
+
 template <typename T>
 __global__ __launch_bounds__(WAVE) void k_fwd_simple(const T *__restrict__ inc_c, int64_t ld, int64_t P, int Mc, int Nc, int d,
                                                      int naive, T *__restrict__ out_final, T *__restrict__ out_grid,
@@ -26,6 +34,18 @@ __global__ __launch_bounds__(WAVE) void k_fwd_simple(const T *__restrict__ inc_c
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int MM = Mc << d, NN = Nc << d;
     const int64_t gs = (int64_t)(MM + 1) * (NN + 1);
+    if (naive & FWD_RAGGED) {
+        const int *cells = reinterpret_cast<const int *>(out_edges);
+        for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
+            // clamped to the pair's block: a wrong table never reaches outside the pair's increments; the only address formed from it is out_final + p
+            const int mc = min(max(cells[2 * p], 0), Mc), nc = min(max(cells[2 * p + 1], 0), Nc);
+            double v = 1.;
+            if (mc > 0 && nc > 0) v = sweep_pair<T, T, false>(inc_c + p * (int64_t)Mc * ld, ld, mc, nc, d, naive & 1, lds, nullptr, nullptr);
+            if (threadIdx.x == 0) out_final[p] = (T)v;
+            __syncthreads();
+        }
+        return;
+    }
     for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
         const double v = sweep_pair<T, T, false>(inc_c + p * (int64_t)Mc * ld, ld, Mc, Nc, d, naive, lds,
                                                  out_grid ? out_grid + p * gs : nullptr,
@@ -216,13 +236,15 @@ size_t adj_simple_workspace_bytes(const Geom &g) {
 }
 
 template <typename T>
-int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, double *out_edges, hipStream_t s) {
+int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, double *out_edges, hipStream_t s, const int *cells) {
     const size_t lds = simple_lds_bytes(g);
     if (lds > 160 * 1024) return SK_ERR_UNSUPPORTED;
+    if (cells && (!out_final || out_grid || out_edges)) return SK_ERR_BAD_ARG;   // the table travels in the edges' argument (FWD_RAGGED)
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)k_fwd_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     SK_LAUNCH(k_fwd_simple<T>, dim3(pick_blocks(g.P)), dim3(WAVE), lds, s, inc_c, g.ld, g.P, g.Mc, g.Nc,
-                       g.dyadic, g.naive, out_final, out_grid, out_edges);
+                       g.dyadic, g.naive | (cells ? FWD_RAGGED : 0), out_final, out_grid,
+                       cells ? reinterpret_cast<double *>(const_cast<int *>(cells)) : out_edges);
     return check_launch();
 }
 
@@ -272,8 +294,8 @@ template int launch_adj_rescue<double>(const double *, const Geom &, const doubl
 template int launch_adj_rescue<float>(const float *, const Geom &, const double *, double, float *, float *, int64_t, void *, size_t,
                                       hipStream_t);
 
-template int launch_fwd_simple<double>(const double *, const Geom &, double *, double *, double *, hipStream_t);
-template int launch_fwd_simple<float>(const float *, const Geom &, float *, float *, double *, hipStream_t);
+template int launch_fwd_simple<double>(const double *, const Geom &, double *, double *, double *, hipStream_t, const int *);
+template int launch_fwd_simple<float>(const float *, const Geom &, float *, float *, double *, hipStream_t, const int *);
 template int launch_adj_simple<double>(const double *, const Geom &, double *, double *, int64_t, void *, size_t,
                                        hipStream_t, bool, bool, bool);
 template int launch_adj_simple<float>(const float *, const Geom &, float *, float *, int64_t, void *, size_t, hipStream_t, bool, bool,

@@ -44,6 +44,11 @@ struct WaveParams {
     int k_f;           // coarse row inside the lane's block that holds the pair's last row
     WaveGroup wg;      // workgroups of independent waves (sk_wave_common.h)
     RankSplit rs;      // pairs per wave by age rank (sk_wave_common.h); PPG / n_steps are the largest share's
+    // nullable [P][2] int32 {mc, nc}, 8-byte aligned (non-EDGES instances; a launch-time, wave-uniform mode): pair p stores K at node
+    // (mc << d, nc << d) of its padded grid instead of K[MM][NN] -- the sweep is the padded one, only the lane, the unit and the cell of
+    // the store are the pair's own (derived once per row unit from the table); mc == 0 or nc == 0: nothing is stored.  u_f / lam_f /
+    // sel_f are not read then.  The table entry of a row unit is loaded one row unit ahead, so that its wait finds it landed.
+    const int *cells;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -75,12 +80,26 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_wave(const WaveParams prm) {
         ps = floor_div(sig, nb);
         band = sig - ps * nb;
     }
-    const int my_uf = lam == prm.lam_f ? prm.u_f : -1;   // the unit at which this lane holds K[MM][NN] (if ever)
+    int my_uf = lam == prm.lam_f ? prm.u_f : -1;   // the unit at which this lane holds K[MM][NN] (if ever)
+    int my_sel = prm.sel_f;                        // ... and the cell of its block, k * CW + q (both per row unit with prm.cells)
     int PPG;               // this wave's pairs per lane group (by age rank, sk_wave_common.h), its first pair, the end of its rank
     int64_t first_pair, P_end;
     rank_share(prm.rs, wave_id, G, prm.P, PPG, first_pair, P_end);
     const int n_steps = PPG * nb * NUp + (L - 1);
     const int64_t pair0 = first_pair + (int64_t)(lane >> prm.logL) * PPG;
+    // prm.cells: {mc, nc} of pair q of this lane group, {0, 0} (= nothing to store) for a pair this wave does not have
+    auto cells_of = [&](int q) -> int2 {
+        int2 c = {0, 0};
+        if (q >= 0 && q < PPG && pair0 + q < P_end) c = reinterpret_cast<const int2 *>(prm.cells)[pair0 + q];
+        return c;
+    };
+    int2 cell_nxt = {0, 0};   // the entry of the row unit this lane starts next
+    if constexpr (!EDGES) {
+        if (prm.cells) {
+            my_uf = -1;
+            cell_nxt = cells_of((u == 0 || band < nb - 1) ? ps : ps + 1);
+        }
+    }
     const bool is_top = lam == 0, is_bot = lam == L - 1;
     // ring slot of the line this lane is reading: the line it started at macro-step ts sits in slot ts % NSLOT
     int slot = (((-(u & 7)) % NSLOT) + NSLOT) % NSLOT;
@@ -193,6 +212,16 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_wave(const WaveParams prm) {
             corner = 1.0;
 #pragma unroll
             for (int i = 0; i < R; ++i) left[i] = 1.0;
+            if constexpr (!EDGES) {
+                if (prm.cells) {   // (uniform) the pair's own end node: do I hold row mc - 1 in this band, and where is column nc - 1
+                    const int mc = min(max(cell_nxt.x, 0), prm.Mc), nc = min(max(cell_nxt.y, 0), prm.Nc);
+                    const int row = mc - 1, col = nc - 1, rl = row / RC;
+                    const bool mine = mc > 0 && nc > 0 && (rl >> prm.logL) == band && (rl & (L - 1)) == lam;
+                    my_uf = mine ? col / CW : -1;
+                    my_sel = (row & (RC - 1)) * CW + (col & (CW - 1));
+                    cell_nxt = cells_of(band < nb - 1 ? ps : ps + 1);
+                }
+            }
         }
 
         // -- top row of the block: bottom row of the lane above (previous macro-step), or the band boundary
@@ -297,7 +326,8 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_wave(const WaveParams prm) {
 
         // -- K[MM][NN] of a pair: one lane, once per pair (the asm keeps the select chain inside the branch)
         if (u == my_uf) {
-            if (band == nb - 1 && ps >= 0 && ps < PPG && pair0 + ps < P_end) {
+            const bool my_band = (!EDGES && prm.cells) ? true : band == nb - 1;   // (with prm.cells the band is part of my_uf)
+            if (my_band && ps >= 0 && ps < PPG && pair0 + ps < P_end) {
                 double v = cand[0][0];
 #pragma unroll
                 for (int k = 0; k < RC; ++k)
@@ -305,7 +335,7 @@ __global__ __launch_bounds__(4 * WAVE) void k_fwd_wave(const WaveParams prm) {
                     for (int q = 0; q < CW; ++q) {
                         double cv = cand[k][q];
                         asm volatile("" : "+v"(cv));
-                        if (k * CW + q == prm.sel_f) v = cv;
+                        if (k * CW + q == (EDGES ? prm.sel_f : my_sel)) v = cv;
                     }
                 static_cast<T *>(prm.out)[pair0 + ps] = (T)v;
             }
@@ -381,11 +411,13 @@ int launch_dy(const WaveParams &prm, bool multiband, int pf, int blocks, size_t 
 // Returns SK_ERR_UNSUPPORTED when the shape / layout is outside what this kernel handles; the caller
 // then falls back to the simple kernel.
 template <typename T>
-int launch_fwd_wave(const T *inc_c, int64_t ld, const Geom &g, T *out_final, double *strip_edges, hipStream_t s) {
+int launch_fwd_wave(const T *inc_c, int64_t ld, const Geom &g, T *out_final, double *strip_edges, hipStream_t s, const int *cells) {
     constexpr int CW = Unit<T>::CW;
     const int PF = 2;
     const int DY = g.dyadic;
     if (DY > 3) return SK_ERR_UNSUPPORTED;
+    if (cells && strip_edges) return SK_ERR_BAD_ARG;                                  // the per-pair end node is a mode of the non-EDGES instances
+    if (cells && (reinterpret_cast<uintptr_t>(cells) & 7)) return SK_ERR_UNSUPPORTED;   // one 8-byte load per entry
     if ((reinterpret_cast<uintptr_t>(inc_c) & 15) || ((ld * sizeof(T)) & 15)) return SK_ERR_UNSUPPORTED;
     const int NU = (g.Nc + CW - 1) / CW;
     if ((int64_t)NU * CW > ld) return SK_ERR_UNSUPPORTED;  // the last unit must stay inside the row
@@ -437,6 +469,7 @@ int launch_fwd_wave(const T *inc_c, int64_t ld, const Geom &g, T *out_final, dou
     prm.naive = g.naive;
     prm.edges = strip_edges;
     prm.k_f = (g.Mc - 1) % RC;
+    prm.cells = cells;
 
     // Workgroups.  With equal shares the HBM-bound streaming sweep gains nothing from even SIMD loads and is a few per cent
     // faster as single-wave workgroups (per 131072 pairs of 127 x 127: d = 0 2.70 vs 2.80 ms, with strip edges at d = 1 3.77
@@ -468,7 +501,7 @@ int launch_fwd_wave(const T *inc_c, int64_t ld, const Geom &g, T *out_final, dou
     }
 }
 
-template int launch_fwd_wave<double>(const double *, int64_t, const Geom &, double *, double *, hipStream_t);
-template int launch_fwd_wave<float>(const float *, int64_t, const Geom &, float *, double *, hipStream_t);
+template int launch_fwd_wave<double>(const double *, int64_t, const Geom &, double *, double *, hipStream_t, const int *);
+template int launch_fwd_wave<float>(const float *, int64_t, const Geom &, float *, double *, hipStream_t, const int *);
 
 }  // namespace sk

@@ -1380,8 +1380,11 @@ def _prefix_grid(be, static_kernel, Xd, Yd, dyadic, naive, gram, workspace_bytes
 def _prefix_at(be, static_kernel, Xd, Yd, lx, ly, dyadic, naive, gram, workspace_bytes):
     """out[a, b] = k_sig(x_a[:lx[a]], y_b[:ly[b]]) -- (A, B) for gram, (A,) paired -- for paths padded at their ends to common lengths;
     lx / ly: validated int32 lengths on the paths' device.  The fused prefix kernel storing ONE node per pair where the library says so
-    (sk_route_query(SK_OP_PREFIX); the same `routes` switches as _prefix_grid): nothing of size pairs x M x N exists.  Else the pieces
-    of _prefix_grid's fallback over row tiles within the budget -- increments, the streaming solver's full grid, its coarse nodes --
+    (sk_route_query(SK_OP_PREFIX); the same `routes` switches as _prefix_grid): nothing of size pairs x M x N exists.  Else, over row
+    tiles within the budget: increments, the table {lx - 1, ly - 1} of the tile's pairs, and be.solve_fwd_at -- one node per pair again,
+    no fine grid; by default every pair's own sub-grid on the anti-diagonal kernel (bit for bit the node of the stored grid), with
+    `routes.ragged_stream` the streaming kernel where it serves the shape.  A back-end without solve_fwd_at, or
+    `routes.no_ragged_nodes`: the pieces of _prefix_grid's fallback -- increments, the solver's full fine grid, its coarse nodes --
     with the node of every pair gathered from a tile's grid before the tile is dropped."""
     A, M, N = Xd.shape[0], Xd.shape[1], Yd.shape[1]
     B = Yd.shape[0] if gram else 1
@@ -1396,6 +1399,22 @@ def _prefix_at(be, static_kernel, Xd, Yd, lx, ly, dyadic, naive, gram, workspace
         if out is not None:
             return out
     out = torch.empty(shape, dtype=Xd.dtype, device=Xd.device)
+    if hasattr(be, "solve_fwd_at") and not routes.no_ragged_nodes:
+        # one node per pair and no fine grid: per row of the tile the increments (padded rows) and the table {mc, nc} alone.  By default
+        # the anti-diagonal kernel over every pair's own sub-grid (the bits of the stored grid's node, at the cost of the true lengths);
+        # routes.ragged_stream: the streaming kernel where it serves the shape (dyadic orders above 3 stay on the anti-diagonal kernel)
+        flags = 0 if routes.ragged_stream else _lib.FLAG_SIMPLE
+        cx, cy = lx.to(torch.int32) - 1, ly.to(torch.int32) - 1
+        per_row = B * ((M - 1) * (N + 16) * Xd.element_size() + 8)
+        for a0, a1 in _tiles(A, per_row, _budget(Xd.device, workspace_bytes)):
+            inc = _increments(be, static_kernel, Xd[a0:a1], Yd if gram else Yd[a0:a1], gram=gram)
+            if gram:
+                cells = torch.stack((cx[a0:a1, None].expand(a1 - a0, B), cy[None, :].expand(a1 - a0, B)), dim=-1)
+            else:
+                cells = torch.stack((cx[a0:a1], cy[a0:a1]), dim=-1)
+            out[a0:a1] = be.solve_fwd_at(inc, cells, dyadic, naive, flags)
+            del inc, cells
+        return out
     r = 1 << dyadic
     ix, iy = lx.long() - 1, ly.long() - 1
     per_row = B * ((M - 1) * (N + 16) + (((M - 1) << dyadic) + 1) * (((N - 1) << dyadic) + 1)) * Xd.element_size()
@@ -1782,7 +1801,9 @@ class SigKernel:
         their ends to common lengths (``pad_paths``; any padding), len_x (batch_X,) / len_y (batch_Y,) their point counts ->
         (batch_X, batch_Y): out[a, b] = k(X^a[:len_x[a]], Y^b[:len_y[b]]) -- node (len_x[a] - 1, len_y[b] - 1) of
         ``compute_Gram_prefixes``'s grid, bit for bit: one sweep of the padded pairs by the fused prefix kernel that stores that one node
-        per pair (dim <= 8, one band per pair; else gathered from row tiles of the streaming solver's grid within ``workspace_bytes``):
+        per pair (dim <= 8, one band per pair; else increments in row tiles within ``workspace_bytes`` and a solver that again stores
+        one node per pair and no grid -- by default every pair's own sub-grid, the same bits; ``routes.ragged_stream``: the streaming
+        solver's padded sweep, within 1e-11 of them):
         the (batch_X, batch_Y, Lx, Ly) tensor is never built.  A path of one point gives exactly 1.  The values past a path's length
         never reach its result, whatever they are -- huge, NaN or inf (a function-valued static kernel maps them through its feature
         map first: keep them finite there).  The lengths are integer tensors (any device) or sequences of ints, checked once on the host: a wrong
