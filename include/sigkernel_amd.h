@@ -69,7 +69,7 @@ typedef enum sk_status {
  * pair_tab argument (position 3) and added the sk_prep_cat_* / sk_solve_fwd_loss_f64 / sk_loss_* / sk_*_adjoint_finish_f64 family;
  * 320 -> 330 gave sk_linear_adjoint_fused_f64 its ypart / ypart_doubles / ycols_out arguments (the second-argument sums); 330 -> 340
  * widened sk_static_increments_* to any path dim and gave sk_static_adjoint_* kind 1 a different output beyond 32 dims (see there).  Entry
- * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*, sk_truncated_wide_adjoint*, sk_plan_adjoint_chunks, sk_plan_one_draw, sk_solve_prefix_resume_*, sk_prefix_state_pitch) leave the number where it is.  A binding
+ * points that are only ADDED (the prefix slices, sk_truncated_paired_*, sk_truncated_levels_*, sk_truncated_adjoint*, sk_truncated_points_*, sk_truncated_points_adjoint*, sk_truncated_long_*, sk_truncated_long_adjoint*, sk_truncated_wide_adjoint*, sk_plan_adjoint_chunks, sk_plan_one_draw, sk_solve_prefix_resume_*, sk_prefix_state_pitch, sk_solve_fwd_resume_*, sk_solve_fwd_resume_fits) leave the number where it is.  A binding
  * written against an older number must not load this library silently (sigkernel_amd/_lib.py checks it at load). */
 int sk_version(void);
 /* "sigkernel_amd gfx950; sources <hash>; <hipcc --version>; ISA hazard lint passed at build": the sources and the toolchain this
@@ -449,6 +449,29 @@ int sk_solve_fwd_at_f64(const double *inc_c, int64_t ld, int64_t P, int Mc, int 
                         double *out, void *stream);
 int sk_solve_fwd_at_f32(const float *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, int flags, const int *cells,
                         float *out, void *stream);
+
+/* Forward solve of a PIECE of Nc coarse columns that starts from a kept fine column instead of the constant 1: what a stream off the
+ * fused prefix kernel's scope appends with.  Pair p's grid has been swept up to some coarse column before; col_in holds K on that fine
+ * column, inc_c the increments of the Nc coarse columns behind it.  Every cell is evaluated from the same operands in the same order as
+ * in sk_solve_fwd_*'s one-shot sweep of the whole grid with out_grid (the anti-diagonal kernel, csrc/sk_simple.hip, -ffp-contract=off),
+ * so the piece's cells are that grid's bit for bit, any dyadic order, both schemes.  MM = Mc << dyadic, NN = Nc << dyadic.
+ *   inc_c   [P,Mc,ld]    as sk_solve_fwd_* (ld = 0: Nc), the piece's columns only
+ *   col_in  [P][MM + 1]  doubles (fp64 whatever the increments' type): element i = K at fine row i of the column the piece starts at,
+ *                        1 <= i <= MM.  Element 0 of a slot is NEVER READ (row 0 of a grid is the constant 1).  A first piece starts
+ *                        from a column of ones.
+ *   col_out [P][MM + 1]  doubles: element i = K[i][NN], the piece's terminal column, written for 1 <= i <= MM.  Element 0 of a slot is
+ *                        NOT WRITTEN: it is the caller's.  Must not overlap col_in (SK_ERR_BAD_ARG): callers alternate two arrays.
+ *   row     [P][NN + 1]  doubles: element j = K[MM][j], the terminal row over the piece, written for 1 <= j <= NN; element 0 (the
+ *                        corner K[MM][0] = col_in[MM]) is NOT WRITTEN.  The coarse nodes are elements (1..Nc) << dyadic.
+ * SK_ERR_UNSUPPORTED where a bank path does not fit the kernel's three LDS diagonals (sk_solve_fwd_resume_fits says so beforehand);
+ * every check comes before any device call.  No kernel instance of its own: a launch-time mode of k_fwd_simple. */
+int sk_solve_fwd_resume_f64(const double *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, const double *col_in,
+                            double *col_out, double *row, void *stream);
+int sk_solve_fwd_resume_f32(const float *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, const double *col_in,
+                            double *col_out, double *row, void *stream);
+/* 1 where first paths of Mc coarse cells at this dyadic order fit sk_solve_fwd_resume_* (3 * 8 * ((Mc << dyadic) + 1) bytes of LDS
+ * within 160 KiB), else 0.  Host only. */
+int sk_solve_fwd_resume_fits(int Mc, int dyadic);
 
 /* Forward solve with the LINEAR static kernel fused in (csrc/sk_wave_fused.hip): the increments
  * s^2 <x[p+1]-x[p], y[q+1]-y[q]> are formed inside the sweep, nothing of size P*M*N ever exists in HBM.

@@ -83,6 +83,9 @@ SIGNATURES = {
     "sk_solve_fwd_f32": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     "sk_solve_fwd_at_f64": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_solve_fwd_at_f32": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
+    "sk_solve_fwd_resume_f64": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "sk_solve_fwd_resume_f32": (_int, [_vp, _i64, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "sk_solve_fwd_resume_fits": (_int, [_int, _int]),
     "sk_solve_fwd_linear_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_solve_fwd_linear_f32": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp]),
     "sk_solve_fwd_rbf_f64": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, ctypes.c_double, _vp, _vp, _vp]),
@@ -1655,6 +1658,32 @@ class HipBackend:
             _check(fn(_ptr(inc_c), ld, P, Mc, Nc, int(dyadic), SCHEME_NAIVE if naive else SCHEME_DEFAULT, int(flags), _ptr(cells),
                       _ptr(out), _stream(inc_c)), "sk_solve_fwd_at")
         return out
+
+    @staticmethod
+    def resume_fits(M, dyadic):
+        """True where first paths of M points at this dyadic order fit solve_fwd_resume (sk_solve_fwd_resume_fits: the LDS limit)"""
+        return int(M) >= 2 and bool(load().sk_solve_fwd_resume_fits(int(M) - 1, int(dyadic)))
+
+    def solve_fwd_resume(self, inc_c, dyadic, naive, col_in, col_out):
+        """A PIECE of a pair's grid swept from a kept fine column (sk_solve_fwd_resume_*): inc_c [..., Mc, Nc] the increments of the
+        piece's Nc coarse columns, col_in / col_out fp64 [P, MM + 1] contiguous on the same device (P = the pairs, MM = Mc << dyadic),
+        not overlapping -> row fp64 [..., NN + 1]: row[..., j] = K[MM][j] over the piece for j >= 1, element 0 NOT written; col_out[:, i] =
+        K[i][NN] for i >= 1, element 0 not written; col_in[:, 0] is never read.  Bit for bit the cells of solve_fwd(want_grid=True)
+        over the whole grid."""
+        inc_c, ld = _row_stride(inc_c, "inc_c")
+        Mc, Nc = inc_c.shape[-2:]
+        batch = inc_c.shape[:-2]
+        P = inc_c.numel() // (Mc * Nc)
+        MM, NN = Mc << dyadic, Nc << dyadic
+        for name, c in (("col_in", col_in), ("col_out", col_out)):
+            if c.dtype != torch.float64 or c.device != inc_c.device or tuple(c.shape) != (P, MM + 1) or not c.is_contiguous():
+                raise ValueError("%s must be a contiguous float64 tensor of shape %s on %s" % (name, (P, MM + 1), inc_c.device))
+        row = torch.empty(batch + (NN + 1,), dtype=torch.float64, device=inc_c.device)
+        with _device(inc_c.device):
+            fn = getattr(load(), "sk_solve_fwd_resume_" + _suffix(inc_c))
+            _check(fn(_ptr(inc_c), ld, P, Mc, Nc, int(dyadic), SCHEME_NAIVE if naive else SCHEME_DEFAULT, _ptr(col_in), _ptr(col_out),
+                      _ptr(row), _stream(inc_c)), "sk_solve_fwd_resume")
+        return row
 
     def solve_fwd_keep_edges(self, inc_c, dyadic, naive=False):
         """Forward solve that keeps the terminal row/column of every pair for a later solve_adj(..., edges=...):

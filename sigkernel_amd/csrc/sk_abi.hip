@@ -61,6 +61,23 @@ int solve_fwd_at(const T *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyad
     return launch_fwd_simple<T>(inc_c, g, out, nullptr, nullptr, (hipStream_t)stream, cells);
 }
 
+// A piece of Nc coarse columns swept from a kept fine column (the RESUME mode of the anti-diagonal kernel; any dyadic order).
+template <typename T>
+int solve_fwd_resume(const T *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, const double *col_in, double *col_out,
+                     double *row, void *stream) {
+    if (bad_common(inc_c, P, Mc, Nc, dyadic, scheme, 0) || (ld != 0 && ld < Nc)) return SK_ERR_BAD_ARG;
+    if (!col_in || !col_out || !row) return SK_ERR_BAD_ARG;
+    const Geom g = make_geom(P, Mc, Nc, dyadic, scheme, ld);
+    {   // the two columns must not overlap: with NN == 1 a row reads col_in one anti-diagonal after the row above stored col_out
+        const uintptr_t a = (uintptr_t)col_in, b = (uintptr_t)col_out, bytes = (uintptr_t)P * (uintptr_t)(g.MM + 1) * sizeof(double);
+        if (((a | b) % sizeof(double)) || ((uintptr_t)row % sizeof(double))) return SK_ERR_BAD_ARG;
+        if (a == b || (a < b ? b - a < bytes : a - b < bytes)) return SK_ERR_BAD_ARG;
+    }
+    if (!sk_solve_fwd_resume_fits(Mc, dyadic)) return SK_ERR_UNSUPPORTED;
+    if (P == 0) return SK_OK;
+    return launch_fwd_simple_resume<T>(inc_c, g, col_in, col_out, row, (hipStream_t)stream);
+}
+
 // workspace of the fast adjoint: terminal edges in the strip layout [P, NNp + MMp] doubles + a dummy K[MM][NN] vector
 // [P] doubles; 0 when the strip kernels do not cover the shape
 size_t adj_fast_workspace_bytes(const Geom &g, int elem_size) {
@@ -781,6 +798,19 @@ int sk_solve_prefix_resume_rbf_f32(const double *Xr, const double *Yt, int64_t A
     return solve_prefix_resume<float>(1, Xr, Yt, A, B, Mrows, Mc, Nc, Ncp, D, dyadic, scheme, inv_sigma, out, ldo, col_in, col_out, ld_col, state_unit, queue, stream);
 }
 int64_t sk_prefix_state_pitch(int Mc, int dyadic, int kind) { return prefix_state_pitch(kind, Mc, dyadic); }
+
+int sk_solve_fwd_resume_fits(int Mc, int dyadic) {
+    if (Mc < 1 || dyadic < 0 || dyadic > 16 || ((int64_t)Mc << dyadic) > (1 << 24)) return 0;
+    return simple_lds_bytes(make_geom(1, Mc, 1, dyadic, SK_SCHEME_DEFAULT)) <= 160 * 1024;
+}
+int sk_solve_fwd_resume_f64(const double *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, const double *col_in,
+                            double *col_out, double *row, void *stream) {
+    return solve_fwd_resume<double>(inc_c, ld, P, Mc, Nc, dyadic, scheme, col_in, col_out, row, stream);
+}
+int sk_solve_fwd_resume_f32(const float *inc_c, int64_t ld, int64_t P, int Mc, int Nc, int dyadic, int scheme, const double *col_in,
+                            double *col_out, double *row, void *stream) {
+    return solve_fwd_resume<float>(inc_c, ld, P, Mc, Nc, dyadic, scheme, col_in, col_out, row, stream);
+}
 
 int sk_solve_prefix_at_linear_f64(const double *dXr, const double *dYt, int64_t A, int64_t B, int Mrows, int Mc, int Nc, int Ncp, int D,
                                   int dyadic, int scheme, const int *len_x, const int *len_y, double *out, void *queue, void *stream) {

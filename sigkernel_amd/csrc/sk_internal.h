@@ -91,6 +91,10 @@ template <typename T>
 int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, double *out_edges, hipStream_t s,
                       const int *cells = nullptr);   // cells [P][2] {mc, nc}: out_final[p] = K at node (mc << d, nc << d), each pair swept
 // over its own sub-grid alone (no grid, no edges); values clamped to the pair's block
+// the sweep of a piece of g.Nc coarse columns from a kept fine column (FWD_RESUME of the same instances): col_in / col_out [P][MM + 1]
+// doubles, row [P][NN + 1] doubles, element 0 of a slot neither read nor written; the caller has checked that the two columns do not overlap
+template <typename T>
+int launch_fwd_simple_resume(const T *inc_c, const Geom &g, const double *col_in, double *col_out, double *row, hipStream_t s);
 template <typename T>
 int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes, hipStream_t s,
                       bool discrete = false, bool ragged = false, bool sources = false);   // discrete: the exact adjoint of the discrete

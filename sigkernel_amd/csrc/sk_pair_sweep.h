@@ -65,6 +65,38 @@ __device__ double sweep_pair(const T *__restrict__ inc, int64_t ld, int Mc, int 
     return __shfl(last, owner, WAVE);
 }
 
+// Sweep a PIECE of one pair: Nc coarse columns of a grid whose columns to the left have been swept before.  The left boundary comes from
+// `col_in` (element i = K at fine row i of the column the piece starts at; element 0 is never read: row 0 is the constant 1) instead of the
+// constant 1; the top boundary stays the literal 1.  Every cell is evaluated from the same operands in the same order as in sweep_pair
+// over the whole grid, so the piece's cells are the one-shot sweep's bit for bit.  Outputs, fp64: row[j] = K[MM][j] for 1 <= j <= NN,
+// col_out[i] = K[i][NN] for 1 <= i <= MM; element 0 of either is NOT written.  col_in and col_out must not overlap (with NN == 1 row
+// i + 1 reads col_in[i] one anti-diagonal after row i stored col_out[i]).  The boundary is read from col_in, never from LDS, and every
+// LDS word read at j > 1 was written for this pair: what the previous pair of the block left in LDS reaches nothing.
+template <typename T>
+__device__ void sweep_pair_resume(const T *__restrict__ inc, int64_t ld, int Mc, int Nc, int d, int naive, double *lds,
+                                  const double *__restrict__ col_in, double *__restrict__ col_out, double *__restrict__ row) {
+    const int lane = threadIdx.x;
+    const int MM = Mc << d, NN = Nc << d;
+    const double rs = 1.0 / (double)(1 << d);
+    double *d0 = lds, *d1 = lds + (MM + 1), *d2 = lds + 2 * (MM + 1);
+    for (int s = 2; s <= MM + NN; ++s) {
+        const int ilo = max(1, s - NN), ihi = min(MM, s - 1);
+        for (int i = ilo + lane; i <= ihi; i += WAVE) {
+            const int j = s - i;
+            const double k10 = (j == 1) ? col_in[i] : d1[i];
+            const double k01 = (i == 1) ? 1. : d1[i - 1];
+            const double k00 = (i == 1) ? 1. : (j == 1) ? col_in[i - 1] : d0[i - 1];
+            const double g = ((double)inc[(int64_t)((i - 1) >> d) * ld + ((j - 1) >> d)] * rs) * rs;
+            const double v = cell_exact(k10, k01, k00, g, naive);
+            d2[i] = v;
+            if (i == MM) row[j] = v;
+            if (j == NN) col_out[i] = v;
+        }
+        __syncthreads();
+        double *t = d0; d0 = d1; d1 = d2; d2 = t;
+    }
+}
+
 // Robust adjoint of one pair: both solution grids are written to the block's scratch slot, then every
 // coarse cell sums its r*r products in the oracle's order (i-major), so W is bit-identical
 // to oracle/sigkernel_oracle.c:sk_oracle_adjoint_coarse.

@@ -26,6 +26,12 @@ namespace {
 // stored grid holds there; an empty sub-grid (mc == 0 or nc == 0) gives 1.  A launch-time mode of the same two instances, in the
 // arguments they already have.
 constexpr int FWD_RAGGED = 2;
+// Bit 2 (FWD_RESUME, wave-uniform, never with FWD_RAGGED): the sweep of a PIECE of Nc coarse columns that takes its left boundary from a
+// kept fine column instead of the constant 1 (sweep_pair_resume, sk_pair_sweep.h).  The three pointers travel in the output arguments,
+// none of which this mode uses as declared: `out_final` is col_in [P][MM + 1] doubles (read only), `out_grid` is col_out [P][MM + 1]
+// doubles, `out_edges` is the terminal row [P][NN + 1] doubles -- fp64 whatever T.  Element 0 of a slot is neither read nor written.
+// Every cell from the same operands in the same order as in the one-shot sweep of the whole grid: its bits.
+constexpr int FWD_RESUME = 4;
 
 template <typename T>
 __global__ __launch_bounds__(WAVE) void k_fwd_simple(const T *__restrict__ inc_c, int64_t ld, int64_t P, int Mc, int Nc, int d,
@@ -44,6 +50,14 @@ __global__ __launch_bounds__(WAVE) void k_fwd_simple(const T *__restrict__ inc_c
             if (threadIdx.x == 0) out_final[p] = (T)v;
             __syncthreads();
         }
+        return;
+    }
+    if (naive & FWD_RESUME) {
+        const double *col_in = reinterpret_cast<const double *>(out_final);
+        double *col_out = reinterpret_cast<double *>(out_grid);
+        for (int64_t p = blockIdx.x; p < P; p += gridDim.x)      // (the sweep ends on a barrier: the next pair's first diagonal waits for it)
+            sweep_pair_resume<T>(inc_c + p * (int64_t)Mc * ld, ld, Mc, Nc, d, naive & 1, lds, col_in + p * (int64_t)(MM + 1),
+                                 col_out + p * (int64_t)(MM + 1), out_edges + p * (int64_t)(NN + 1));
         return;
     }
     for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
@@ -247,6 +261,22 @@ int launch_fwd_simple(const T *inc_c, const Geom &g, T *out_final, T *out_grid, 
                        cells ? reinterpret_cast<double *>(const_cast<int *>(cells)) : out_edges);
     return check_launch();
 }
+
+// The RESUME mode of k_fwd_simple: col_in / col_out [P][MM + 1] doubles, row [P][NN + 1] doubles (the caller has checked the pointers).
+template <typename T>
+int launch_fwd_simple_resume(const T *inc_c, const Geom &g, const double *col_in, double *col_out, double *row, hipStream_t s) {
+    const size_t lds = simple_lds_bytes(g);
+    if (lds > 160 * 1024) return SK_ERR_UNSUPPORTED;
+    if (!col_in || !col_out || !row) return SK_ERR_BAD_ARG;
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void *)k_fwd_simple<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    // (the kernel reads col_in through a pointer of its first output's type and never writes through it)
+    SK_LAUNCH(k_fwd_simple<T>, dim3(pick_blocks(g.P)), dim3(WAVE), lds, s, inc_c, g.ld, g.P, g.Mc, g.Nc, g.dyadic, g.naive | FWD_RESUME,
+              reinterpret_cast<T *>(const_cast<double *>(col_in)), reinterpret_cast<T *>(col_out), row);
+    return check_launch();
+}
+template int launch_fwd_simple_resume<double>(const double *, const Geom &, const double *, double *, double *, hipStream_t);
+template int launch_fwd_simple_resume<float>(const float *, const Geom &, const double *, double *, double *, hipStream_t);
 
 template <typename T>
 int launch_adj_simple(const T *inc_c, const Geom &g, T *out_final, T *W, int64_t ldw, void *ws, size_t ws_bytes,

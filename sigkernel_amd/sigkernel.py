@@ -1508,6 +1508,7 @@ class SigKernelStream:
       ``length``         points seen per stream
       ``resumes``        True: every append sweeps only its new points (below); False: every append sweeps the whole history
       ``state_bytes``    bytes the stream holds between appends (below)
+      ``route``          "fused", "column" or "history": what an append runs (below; read-only)
 
     ``resumes``: inside the fused prefix kernel's scope (exactly LinearKernel / RBFKernel, dim <= 8, dyadic_order <= 2, bank paths of one
     band, the library back-end) all that crosses a column of a pair's PDE grid is that column, so the stream keeps one fine column per
@@ -1524,11 +1525,37 @@ class SigKernelStream:
     ``compute_Gram_prefixes(X, history, nodes="last_row")`` over all of it: the same values, time quadratic in the stream;
     ``state_bytes`` = the history's bytes and grows with it.
 
+    ``resume="always"`` (``open_stream(X, Y0, resume="always")``; the default is ``"fused"``, the behaviour above) resumes outside that
+    scope as well -- the column route, ``route == "column"``, ``resumes`` True.  Off the fused scope the values come from the
+    anti-diagonal solver (csrc/sk_simple.hip), which sweeps in fp64 and evaluates every cell from the same operands in the same order
+    whatever the grid's extent: a sweep over a piece of y that takes its left boundary from the kept fine column instead of the
+    constant 1 reproduces the one-shot sweep's cells bit for bit (``sk_solve_fwd_resume_*``, a launch-time mode of the same kernel).
+    A kernel of function-valued paths is its ``base_kernel`` on the features (as in every other method): under "always" its stream is
+    the stream of the features -- the bank mapped once at open, every piece as it arrives -- and so takes the fused resume where the
+    FEATURES lie in the fused scope (RBF_ID_Kernel on (4, 2)-valued points: dim 8, ``route == "fused"``, the route whose bits the one-shot
+    call on such paths has) and the column route elsewhere.
+    The stream keeps the bank (function-valued kernels: its features), two fp64 column arrays
+    (pairs, ((M - 1) << dyadic_order) + 1) that the sweeps alternate between, and the streams' last point: ``state_bytes`` is their sum,
+    constant in the stream's length.  An append forms the increments of the piece [last point] + Ynew alone (row-tiled under
+    ``workspace_bytes``), one launch per tile, and returns the coarse nodes of the terminal row.  Any path dim, dyadic order and static
+    kernel; the bank's fine rows must fit the solver's LDS limit (3 x 8 x (((M - 1) << dyadic_order) + 1) bytes within 160 KiB), and the
+    back-end must have ``solve_fwd_resume`` -- else the stream keeps its history as under "fused" (``route == "history"``).  Inside
+    the fused scope "always" is the fused resume (``route == "fused"``).  Bits: exactly LinearKernel / RBFKernel, and Linear_ID_Kernel /
+    RBF_ID_Kernel / RBF_SQR_Kernel over them, give ``compute_Gram_prefixes(X, y, nodes="last_row")`` bit for bit -- an increment of a
+    piece is computed from its own two points of y alone, and these feature maps act on each time point alone, element by element.
+    RBF_CEXP_Kernel's ``features`` is a matmul along the space axis: also each time point alone, so it takes the column route, but the
+    matmul's rounding may depend on how many points it maps at once; a duck-typed kernel's ``Gram_matrix`` likewise.  Those agree with
+    the one-shot call to rounding (1e-12 relative in fp64), not to the bit.  No feature map of static_kernels.py mixes time points;
+    a user-defined one that does must not be streamed with "always".  Thin chunks fill few of the solver's 64 lanes (an
+    anti-diagonal of a piece of c points has at most c << dyadic_order cells): see README.md for the measured chunk sizes.
+
     Forward only: an input that requires grad raises ``NotImplementedError`` (outside ``torch.no_grad()``), on ``exact_gradient=True``
     objects too, whose forward values are the same.  Not sharded (``process_group`` raises).  Only the streams grow: a bank whose
     paths grow as well would need the kept last ROW too."""
 
-    def __init__(self, sk, X, Y0, paired=False):
+    def __init__(self, sk, X, Y0, paired=False, resume="fused"):
+        if resume not in ("fused", "always"):
+            raise ValueError("resume must be 'fused' or 'always', not %r" % (resume,))
         if sk.process_group is not None:
             raise NotImplementedError("streams are not sharded over a process group; open the stream on a SigKernel without process_group")
         self._sk, self._gram = sk, not paired
@@ -1544,6 +1571,15 @@ class SigKernelStream:
         self._B, self.length = Y0.shape[0], 0
         self._pairs_shape = (X.shape[0], Y0.shape[0]) if self._gram else (X.shape[0],)
         self._col, self._cur, self._bank, self._tail, self._hist, self._kernel = None, None, None, None, None, None
+        self._column, self._on = False, None
+        if raw and resume == "always":
+            # a kernel of function-valued paths IS its base kernel on the features (SigKernel._on_features): the stream of the features,
+            # bank mapped once here, every piece as it arrives -- the fused resume where the features lie in its scope, else the column
+            inner = SigKernel(sk.static_kernel.base_kernel, sk.dyadic_order, sk._naive_solver, sk.workspace_bytes, None, sk.exact_gradient)
+            with torch.no_grad():
+                self._on = SigKernelStream(inner, sk.static_kernel.features(self._X), sk.static_kernel.features(Y0.detach()), paired, resume)
+            self.resumes, self.length = self._on.resumes, self._on.length
+            return
         be = _lib.get_backend()
         fused = None if raw else _fused_static(sk.static_kernel, self._gram)
         self.resumes = bool(
@@ -1558,6 +1594,19 @@ class SigKernelStream:
             pairs = X.shape[0] * (Y0.shape[0] if self._gram else 1)
             pitch = be.state_pitch(fused[0], X.shape[1], sk.dyadic_order)
             self._col = [torch.empty((pairs, pitch), dtype=torch.float64, device=X.device) for _ in range(2)]
+            self._kernel = torch.ones(self._pairs_shape, dtype=X.dtype, device=X.device)
+        self._column = bool(
+            resume == "always" and not self.resumes and hasattr(be, "solve_fwd_resume") and X.shape[0] > 0 and Y0.shape[0] > 0
+            and X.shape[1] >= 2 and (not hasattr(be, "resume_fits") or be.resume_fits(X.shape[1], sk.dyadic_order)))
+        if self._column:
+            # the column route: the anti-diagonal solver resumed from a kept fine column, behind any static kernel
+            self.resumes = True
+            self._bank = self._X.contiguous()
+            pairs = X.shape[0] * (Y0.shape[0] if self._gram else 1)
+            fine = ((X.shape[1] - 1) << sk.dyadic_order) + 1
+            self._col = [torch.ones((pairs, fine), dtype=torch.float64, device=X.device),
+                         torch.empty((pairs, fine), dtype=torch.float64, device=X.device)]
+            self._cur = 0
             self._kernel = torch.ones(self._pairs_shape, dtype=X.dtype, device=X.device)
         self._push(Y0.detach(), first=True)
 
@@ -1583,6 +1632,8 @@ class SigKernelStream:
                 row = call(self._X, self._hist, nodes="last_row")
             self._kernel = row[..., -1]
             return row[..., row.shape[-1] - c:]
+        if self._column:
+            return self._push_column(Ynew, first)
         # the one or two points behind the kept column, then the new ones: the piece the sweep resumes over
         piece = Ynew.contiguous() if first else torch.cat((self._tail, Ynew), dim=1)
         kept = 0 if first else self._tail.shape[1]
@@ -1606,20 +1657,62 @@ class SigKernelStream:
             return row
         return row[..., kept:]
 
+    def _push_column(self, Ynew, first):
+        """the column route's append: the increments of the piece [last point] + Ynew alone -- c coarse columns --, one
+        solve_fwd_resume launch per row tile from the kept fine column, the coarse nodes of the terminal row"""
+        be, sk = _lib.get_backend(), self._sk
+        X, d = self._bank, sk.dyadic_order
+        piece = Ynew.contiguous() if first else torch.cat((self._tail, Ynew), dim=1)
+        self._tail = piece[:, -1:].clone()      # the streams' last point
+        c = piece.shape[1] - 1
+        if c == 0:      # a first chunk of one point: nothing to sweep, the column of ones stands
+            return self._kernel[..., None].clone()
+        A, M, B, r = X.shape[0], X.shape[1], (self._B if self._gram else 1), 1 << d
+        col_in, col_out = self._col[self._cur], self._col[1 - self._cur]
+        out = torch.empty(self._pairs_shape + (c,), dtype=X.dtype, device=X.device)
+        # per row of the tile: the increments of the piece (padded rows) and the fp64 terminal row; the columns are pair-major, so a
+        # row tile is a contiguous slice of them
+        per_row = B * ((M - 1) * (c + 16) * X.element_size() + 8 * ((c << d) + 1))
+        for a0, a1 in _tiles(A, per_row, _budget(X.device, sk.workspace_bytes)):
+            inc = _increments(be, sk.static_kernel, X[a0:a1], piece if self._gram else piece[a0:a1], gram=self._gram)
+            row = be.solve_fwd_resume(inc, d, sk._naive_solver, col_in[a0 * B:a1 * B], col_out[a0 * B:a1 * B])
+            out[a0:a1] = row[..., r::r]      # nodes (1..c) << d, rounded to the paths' dtype as a stored grid's are
+            del inc, row
+        self._cur = 1 - self._cur
+        self._kernel = out[..., -1].clone()
+        if first:      # k against a one-point prefix, then the swept nodes
+            return torch.cat((torch.ones_like(out[..., :1]), out), dim=-1)
+        return out
+
     def append(self, Ynew):
         """Ynew (B, c, D): the streams' next c points -> (A, B, c) ((A, c) paired): k(x_a, y_b[:n + 1]) for every new point, in order."""
         self._check(Ynew)
         if Ynew.shape[1] == 0:
             return torch.empty(self._pairs_shape + (0,), dtype=self._X.dtype, device=self._X.device)
+        if self._on is not None:      # function-valued paths under resume="always": the piece's features, as they arrive
+            with torch.no_grad():
+                new = self._on.append(self._sk.static_kernel.features(Ynew.detach()))
+            self.length = self._on.length
+            return new
         return self._push(Ynew.detach())
 
     @property
     def kernel(self):
         """(A, B) ((A,) paired): k(x_a, y_b) as the streams stand -- ``compute_Gram(X, all of y)`` bit for bit"""
-        return self._kernel
+        return self._kernel if self._on is None else self._on.kernel
+
+    @property
+    def route(self):
+        """"fused": the prefix kernel resumed from its kept column; "column": the anti-diagonal solver resumed from a kept fine column
+        (``resume="always"`` off the fused scope); "history": every append sweeps the kept history again"""
+        if self._on is not None:
+            return self._on.route
+        return "column" if self._column else "fused" if self.resumes else "history"
 
     @property
     def state_bytes(self):
+        if self._on is not None:
+            return self._on.state_bytes
         held = [self._hist] if not self.resumes else list(self._col) + [self._bank, self._tail]
         return sum(t.numel() * t.element_size() for t in held if t is not None)
 
@@ -1678,11 +1771,15 @@ class SigKernel:
                           self.exact_gradient)
         return inner, _FeatureMap(self.static_kernel)
 
-    def open_stream(self, X, Y0, paired=False):
+    def open_stream(self, X, Y0, paired=False, resume="fused"):
         """X (A, M, D) complete paths, Y0 (B, n0 >= 1, D) what B streams hold so far -> a :class:`SigKernelStream`: ``append(Ynew)``
         returns k(x_a, y_b[:n + 1]) for every new point of the streams -- ``compute_Gram_prefixes(X, y, nodes="last_row")`` as y
-        arrives, bit for bit, without sweeping the history again.  ``paired=True``: stream a against bank path a."""
-        return SigKernelStream(self, X, Y0, paired)
+        arrives, bit for bit, without sweeping the history again.  ``paired=True``: stream a against bank path a.
+        ``resume``: "fused" (default) resumes inside the fused prefix kernel's scope only and keeps the history elsewhere; "always"
+        resumes outside that scope too, from a kept fine column of the anti-diagonal solver (``route == "column"``: any path dim, bank
+        length within the solver's LDS limit, dyadic order and static kernel; see :class:`SigKernelStream`).  Any other string raises
+        ``ValueError``."""
+        return SigKernelStream(self, X, Y0, paired, resume)
 
     def compute_kernel(self, X, Y, max_batch=100):
         """X (batch, len_x, dim), Y (batch, len_y, dim) -> (batch,) vector k(X^i_T, Y^i_T).

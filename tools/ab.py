@@ -45,13 +45,18 @@ if len(sys.argv) > 1 and sys.argv[1] == "--one":
             Xg = X.detach().requires_grad_(True); sk.compute_mmd(Xg, Y).backward(); return Xg.grad
     elif cfg.startswith("shard"):      # rows of the headline Gram one of 512 / rows ranks solves
         X, Y = walk(int(cfg[5:]), 128, 8), walk(512, 128, 8); sk = sigkernel_amd.SigKernel(sigkernel_amd.LinearKernel(), 1); fn = lambda: sk.compute_Gram(X, Y)
+    elif cfg in ("grid", "at"):      # the ordinary launches of k_fwd_simple: a full-grid call; one node per pair on every pair's own sub-grid
+        from sigkernel_amd import _lib
+        inc = (torch.randn(4096, 64, 64, generator=gen, dtype=torch.float64) / 64).cuda(); be = _lib.get_backend()
+        cells = torch.randint(1, 65, (4096, 2), generator=gen).to(torch.int32).cuda()
+        fn = (lambda: be.solve_fwd(inc, 1, want_grid=True)[1]) if cfg == "grid" else (lambda: be.solve_fwd_at(inc, cells, 1, False, _lib.FLAG_SIMPLE))
     elif cfg == "c4fwd":
         X, Y = walk(2048, 64, 4), walk(2048, 64, 4); sk = sigkernel_amd.SigKernel(sigkernel_amd.RBFKernel(1.0), 2); fn = lambda: sk.compute_Gram(X, Y)
     else:
         X, Y = walk(2048, 64, 4), walk(2048, 64, 4); sk = sigkernel_amd.SigKernel(sigkernel_amd.RBFKernel(1.0), 2)
         def fn():
             Xg = X.detach().requires_grad_(True); sk.compute_mmd(Xg, Y).backward(); return Xg.grad
-    n = 30 if cfg in ("c3", "c2", "c2big") or cfg.startswith("mmd") or cfg.startswith("shard") else 6
+    n = 30 if cfg in ("c3", "c2", "c2big", "grid", "at") or cfg.startswith("mmd") or cfg.startswith("shard") else 6
     if ":" in cfg: n = 10
     for _ in range(max(3, n // 3)): out = fn()
     torch.cuda.synchronize()

@@ -11,7 +11,13 @@ measurement runs in a process of its own, base and new alternating, so that only
              append that staging the bank again would be (stage_prefix_bank, paid once when the stream is opened)
 
 CALL times, event-timed, medians of --repeats calls after warm-ups.
-usage: SK_AB_BASE=<name> python tools/time_stream.py [--rounds 7] [--repeats 9] [--out profiles/stream_resume.txt]"""
+usage: SK_AB_BASE=<name> python tools/time_stream.py [--rounds 7] [--repeats 9] [--out profiles/stream_resume.txt]
+
+  --column   OFF the fused scope (profiles/stream_column.txt; no base build needed): st.append(chunk) after 64 / 256 / 1024 points of
+             history on a stream opened with resume="always" (the column route) against the same append on a stream opened with the
+             default (the history route: the parent commit's behaviour), chunks of 1, 16, 64, 256 points, with peak memory; host clock
+             around a call that ends in a synchronise.
+usage: python tools/time_stream.py --column [--rounds 3] [--repeats 3] [--out profiles/stream_column.txt]"""
 import json
 import os
 import subprocess
@@ -84,10 +90,112 @@ def one(which, what, repeats):
     print("RESULT " + json.dumps(res))
 
 
+COLUMN = [("256 x 256 pairs, bank of 64 points, dim 20, RBF, dyadic 1", "rbf", 256, 256, 64, 20, 1),
+          ("256 x 256 pairs, bank of 300 points, dim 3, Linear, dyadic 1", "linear", 256, 256, 300, 3, 1),
+          ("128 x 128 pairs, bank of 64 points, dim 40, RBF, dyadic 1", "rbf", 128, 128, 64, 40, 1)]
+HISTORIES = [64, 256, 1024]
+
+
+def one_column(shape, repeats):
+    """one shape of COLUMN on this build: st.append(chunk) after `history` points on a stream opened with resume="always" (the column
+    route) and on one opened with the default (the history route: what the parent commit does off the fused scope)"""
+    sys.path.insert(0, ROOT)
+    import time
+    import numpy as np
+    import torch
+    import sigkernel_amd
+    name, kind, A, B, M, D, d = COLUMN[shape]
+    gen = torch.Generator().manual_seed(0)
+
+    def walk(n, L):
+        return (torch.cumsum(torch.randn(n, L, D, generator=gen, dtype=torch.float64), dim=1) / np.sqrt(L * D)).cuda()
+
+    X, Y = walk(A, M), walk(B, max(HISTORIES) + max(CHUNKS))
+    sk = sigkernel_amd.SigKernel(sigkernel_amd.LinearKernel() if kind == "linear" else sigkernel_amd.RBFKernel(1.0), d)
+    res = {}
+    for H in HISTORIES:
+        for c in CHUNKS:
+            chunk = Y[:, H:H + c].contiguous()
+            for route in ("column", "history"):
+                st = sk.open_stream(X, Y[:, :H].contiguous(), resume="always" if route == "column" else "fused")
+                assert st.route == route, st.route
+                hist0 = st._hist
+                ts = []
+                for i in range(repeats + 1):
+                    if route == "history":      # (put back to H points: the job must not grow from repeat to repeat)
+                        st._hist, st.length = hist0, H
+                    torch.cuda.synchronize()
+                    if i == 1:
+                        torch.cuda.reset_peak_memory_stats()
+                        base = torch.cuda.memory_allocated()
+                    t0 = time.perf_counter()
+                    out = st.append(chunk)
+                    torch.cuda.synchronize()
+                    if i >= 1:
+                        ts.append(1e3 * (time.perf_counter() - t0))
+                    del out
+                res["%s|%d|%d" % (route, H, c)] = [float(np.median(ts)), min(ts), max(ts), (torch.cuda.max_memory_allocated() - base) / 1e6,
+                                                   st.state_bytes / 1e6]
+                del st
+    print("RESULT " + json.dumps(res))
+
+
+def main_column(args):
+    """profiles/stream_column.txt: the column route against the history route, every shape in a process of its own, `rounds` times"""
+    rounds = int(args[args.index("--rounds") + 1]) if "--rounds" in args else 3
+    repeats = int(args[args.index("--repeats") + 1]) if "--repeats" in args else 3
+    out = args[args.index("--out") + 1] if "--out" in args else None
+    lines = ["SigKernelStream off the fused scope: st.append(chunk) after `history` points, resume=\"always\" (column route) against the default",
+             "(history route: the parent commit's behaviour), this build.  Call times in ms: host clock around a call that ends in",
+             "torch.cuda.synchronize(), after one warm-up call; every shape in a process of its own, %d rounds in one job; a cell is the median over"
+             % rounds, "the rounds of each round's median of %d calls, [min .. max] over ALL calls of all rounds = the run-to-run spread.  peak = growth of" % repeats,
+             "torch.cuda.max_memory_allocated() over the timed calls.", "command: python tools/time_stream.py " + " ".join(args), ""]
+    for s, shape in enumerate(COLUMN):
+        runs = []
+        for r in range(rounds):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one-column", str(s), str(repeats)], capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                print(p.stdout + p.stderr)
+                return p.returncode
+            runs.append(json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][-1][7:]))
+            print("shape %d round %d of %d done" % (s, r + 1, rounds), flush=True)
+        pairs = shape[2] * shape[3]
+        lines.append(shape[0] + "   (state of the column route: %.1f MB, constant)" % runs[0]["column|%d|%d" % (HISTORIES[0], CHUNKS[0])][4])
+        lines.append("  chunk  history |   column: median [min .. max]   peak MB |   history route: median [min .. max]   peak MB | history / column")
+
+        def cell(route, H, c):
+            meds = sorted(r["%s|%d|%d" % (route, H, c)][0] for r in runs)
+            return (meds[len(meds) // 2], min(r["%s|%d|%d" % (route, H, c)][1] for r in runs), max(r["%s|%d|%d" % (route, H, c)][2] for r in runs),
+                    max(r["%s|%d|%d" % (route, H, c)][3] for r in runs))
+        for c in CHUNKS:
+            cols = []
+            for H in HISTORIES:
+                a, b = cell("column", H, c), cell("history", H, c)
+                cols.append(a)
+                lines.append("  %5d  %7d | %9.3f [%9.3f .. %9.3f] %9.1f | %10.3f [%10.3f .. %10.3f] %9.1f | %8.1fx"
+                             % (c, H, a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3], b[0] / a[0]))
+            meds = [a[0] for a in cols]
+            spread = max(a[2] - a[1] for a in cols)
+            lines.append("         column route over the histories: medians span %.3f ms, the widest run-to-run spread of a cell %.3f ms: %s; "
+                         "%.3f us per pair and append" % (max(meds) - min(meds), spread, "inside" if max(meds) - min(meds) <= spread else "OUTSIDE",
+                                                         1e3 * meds[0] / pairs))
+        lines.append("")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+    return 0
+
+
 def main():
     args = sys.argv[1:]
     if args and args[0] == "--one":
         return one(args[1], args[2], int(args[3]))
+    if args and args[0] == "--one-column":
+        return one_column(int(args[1]), int(args[2]))
+    if "--column" in args:
+        return main_column(args)
     rounds = int(args[args.index("--rounds") + 1]) if "--rounds" in args else 7
     repeats = int(args[args.index("--repeats") + 1]) if "--repeats" in args else 9
     out = args[args.index("--out") + 1] if "--out" in args else None
